@@ -12,18 +12,27 @@ The batch of one step is `--nchains` independent chains (default 4 = the referen
 experiments/toy/gp_gibbs.py:25, which vmaps gibbs_kernel over chains :172-173).  A batch of four or more chains is
 driven as two groups of half the chains, each group's launches on its own stream (fbs_amd.LGSweep): the step kernels are
 latency-bound, the groups' launches interleave (+6 % at 4 chains, +18-27 % at 16-32; FBSMI_CHAIN_GROUPS=1 keeps one
-group) -- same results bit for bit.  The single-chain rate is measured too and reported in `single_chain`.
+group) -- same results bit for bit.  With `--full` the single-chain rate is measured too and reported in `single_chain`.
 
 Multi-GPU (--gpus N under torch.distributed.run): every GPU runs its own batch of chains -- the
 reference's own parallel axes (nchains, --id replicas) -- no data-path collective, weak scaling: that is `value`.
-The SAME run also times one particle ensemble SHARDED over the N ranks (`sharded_c5`: BASELINE config 5's
+The SAME run with `--full` also times one particle ensemble SHARDED over the N ranks (`sharded_c5`: BASELINE config 5's
 16 384 particles, fbs_amd/sharded.py: RCCL all_gather of the log-weights + ancestor rows by all_gather or by
 all_to_all), strong scaling, so a 1 -> 8 GPU series carries both axes.
 
-Extra objects of the line (all measured in this process unless they say otherwise): `single_chain`, `batch_scan`,
+A plain run measures the headline only: it builds, warms up, times `--steps` sweeps, writes the timed path's outputs if
+`--dump-outputs DIR` is given, and prints one JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, the workload).  `--full` adds everything else, each piece measured in this process after the headline
+unless it says otherwise: `roofline` (per-kernel durations), `cpu_baseline`, `single_chain`, `batch_scan`,
 `spill` (a working set beyond the Infinity Cache), `gp100` (the reference's d = 100 toy), `c3` / `c4_shard` /
 `c5_shard` (the image configurations per SMC step, network and sampler time apart), `em_finish` (roofline of the
-fused score-network step kernel at config 5's per-GPU shape), `sharded_c5`.
+fused score-network step kernel at config 5's per-GPU shape), `sharded_c5`, `sharded_lg`.  The `--no-*`, `--batch-scan`,
+`--image-*`, `--sharded-*` and `--cpu-sweeps` options shape those `--full` legs only.
+
+`--dump-outputs DIR` writes, after the timed sweeps, what a caller of the timed `sweep.chain` call receives (rank 0's
+batch): `x0.npy` (C, du) and `x0s.npy` (steps, C, du) float32, `bs_star.npy` (C, T + 1) and `key.npy` (2,) as float64
+(exact: int32 indices, uint32 key words); with `--nchains 1` the chain axis is absent.  The inputs are fixed by the
+arguments, so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -63,6 +72,14 @@ def max_over_ranks(dt, dist, dev):
     tt = torch.tensor([dt], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     return float(tt.item())
+
+
+def dump_outputs(path, arrays):
+    """Write every array as path/<name>.npy: floating arrays as float32, integer ones as float64 (exact)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype.kind == "f" else np.float64))
 
 
 def gp100_leg(dev):
@@ -361,12 +378,19 @@ def main():
     ap.add_argument("--sharded-lg-steps", type=int, default=20,
                     help="SMC steps of the sharded linear-Gaussian ensembles (`sharded_lg`; 0: skip)")
     ap.add_argument("--no-spill", action="store_true", help="skip the beyond-the-Infinity-Cache leg (`spill`)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other measurement (roofline, CPU baseline, single chain, batch "
+                         "scan, spill, gp100, image and sharded legs); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # native pieces are built before anything touches the GPU (hipcc / gcc children must not inherit a profiler's preload)
     from fbs_amd import _lib as _fbsmi_lib
     _fbsmi_lib.build_dist()   # libfbsmi, then the exchange library that links it
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import oracle as _oracle_build
         _oracle_build.build()
 
@@ -423,8 +447,29 @@ def main():
     psteps = float(N) * T * C * args.steps * world
     value = psteps / dt
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x0": x0, "x0s": x0s, "bs_star": bs, "key": key})
 
     out = None
+    if rank == 0:
+        out = {"metric": "particle-steps/sec (N x T per Gibbs sweep)", "value": value, "unit": "particle-steps/s",
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+               "data": "synthetic",
+               "config": {"workload": f"2-D Gaussian bridge toy (BASELINE config 2): N={N} particles, T={T} steps, "
+                          "ts=linspace(0,2), analytic score, gibbs_kernel eb=True ef=False marg_y=False, "
+                          f"conditional killing resampling; one step = one Gibbs sweep of a batch of {C} chain(s) "
+                          "(reference driver default nchains=4, vmapped)",
+                          "nparticles": N, "nsteps": T, "nchains": C, "du": br.du, "dv": br.dv,
+                          "parallelism": f"{world} GPU(s) x {C} independent chain(s) each, no collective"},
+               "x0_mean_of_timed_sweeps": float(x0s.float().mean().item())}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     if rank == 0:
         # ---- per-kernel durations with HIP events on the launch stream (untimed extra sweeps) ----
         # A batch of >= 4 chains runs as two groups of half the chains on two streams (fbs_amd.LGSweep): the launches that
@@ -582,20 +627,9 @@ def main():
                    "kind": "port", "sample": f"{sweeps} single-chain sweeps of the same workload (N={N}, T={T}) on the "
                    f"C oracle with OpenMP over independent particle loops, {used} host thread(s), {cdt:.1f} s",
                    "note": "CPU restatement of the reference algorithm (not JAX: JAX is not installable here)"}
-        out = {"metric": "particle-steps/sec (N x T per Gibbs sweep)", "value": value, "unit": "particle-steps/s",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-               "data": "synthetic",
-               "config": {"workload": f"2-D Gaussian bridge toy (BASELINE config 2): N={N} particles, T={T} steps, "
-                          "ts=linspace(0,2), analytic score, gibbs_kernel eb=True ef=False marg_y=False, "
-                          f"conditional killing resampling; one step = one Gibbs sweep of a batch of {C} chain(s) "
-                          "(reference driver default nchains=4, vmapped)",
-                          "nparticles": N, "nsteps": T, "nchains": C, "du": br.du, "dv": br.dv,
-                          "parallelism": f"{world} GPU(s) x {C} independent chain(s) each, no collective"},
-               "roofline": roofline, "cpu_baseline": cpu,
-               "value_single_chain": single["value"] if single else None, "single_chain": single, "batch_scan": scan,
-               "spill": spill, "gp100": gp100, "em_finish": emroof,
-               "x0_mean_of_timed_sweeps": float(x0s.float().mean().item())}
+        out.update({"roofline": roofline, "cpu_baseline": cpu,
+                    "value_single_chain": single["value"] if single else None, "single_chain": single, "batch_scan": scan,
+                    "spill": spill, "gp100": gp100, "em_finish": emroof})
         if images:
             out.update(images)
     # every rank takes part in the sharded ensemble (collectives); rank 0 reports.  The headline above is already measured:

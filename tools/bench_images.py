@@ -1,7 +1,7 @@
 """BASELINE configs 3-5 in shape (fbs_amd/image_configs.py): time per SMC step of gibbs_kernel over the image closures
 with a randomly initialised UNet, split into network time (torch events around every network call) and sampler time
 (everything else: resampling, fbsmi_em_concat / fbsmi_em_finish, normalisation, host loop).  One JSON line per
-configuration.  Not the headline benchmark (bench.py), which carries the same legs with fewer steps."""
+configuration.  Not the headline benchmark (bench.py), whose `--full` run carries the same legs with fewer steps."""
 import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -3,8 +3,8 @@ export TMPDIR=/tmp
 python3 -c "from fbs_amd import _lib; _lib.build(); import oracle; oracle.build()"   # build before any profiler preload exists
 out=$PWD/gpurun_out
 rm -rf $out/q_prof $out/q_valu
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/q_prof -o run -- python3 bench.py --no-cpu-baseline --no-single-chain --batch-scan "" > $out/q_prof.log 2>&1
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --output-format csv -d $out/q_valu -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-single-chain --batch-scan "" > $out/q_valu.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/q_prof -o run -- python3 bench.py --full --no-cpu-baseline --no-single-chain --batch-scan "" > $out/q_prof.log 2>&1
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --output-format csv -d $out/q_valu -o run -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-single-chain --batch-scan "" > $out/q_valu.log 2>&1
 find $out/q_prof -name "*kernel_trace.csv" -delete
 python3 - <<'PY'
 import csv,glob,collections

@@ -1,4 +1,4 @@
-"""The `spill` workload of bench.py alone (BASELINE config 2's model at N = 2^22 particles x 4 chains: ~400 MB of per-step
+"""The `spill` workload of `bench.py --full` alone (BASELINE config 2's model at N = 2^22 particles x 4 chains: ~400 MB of per-step
 arrays, beyond the Infinity Cache), for rocprofv3:
 
     rocprofv3 --kernel-trace --stats -d gpurun_out/spill_prof -o run -- python3 tools/spill_run.py

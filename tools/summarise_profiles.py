@@ -122,7 +122,7 @@ def main():
     fkb, wkb = fetch[k][0], write.get(k, (0.0, 0))[0]
     f4 = calib["4_bytes_per_lane"]["true_over_reported"] if calib and "4_bytes_per_lane" in calib else None
     traffic = {
-        "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python3 bench.py "
+        "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python3 bench.py --full "
                    "--steps 1 --warmup 1 --no-cpu-baseline --no-single-chain --batch-scan '' --image-steps 0 --sharded-steps 0 --sharded-lg-steps 0",
         "workload_text": cfg.get("workload"),
         "workload": {"nparticles": cfg.get("nparticles"), "nsteps": cfg.get("nsteps"), "nchains": cfg.get("nchains")},
