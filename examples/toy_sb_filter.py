@@ -3,7 +3,8 @@
 Counterpart of the reference driver experiments/sb/filter.py (same flags incl. `--x0 proper|heuristic`, key schedule and .npz
 schema `filter-<x0>-<nparticles>-<id>.npz`): the forward observation path is an Euler-Maruyama simulation of the bridge's
 drift from (x0, y0) with x0 a GP-posterior draw ('proper') or N(0, I) ('heuristic'); every sample is one bootstrap_filter run
-on the closure tier (resampling, gathers, normalisation: libfbsmi kernels)."""
+on the closure tier (resampling, gathers, normalisation: libfbsmi kernels).  With --fused the closures come from
+fbs_amd.GaussianSBBridge: the forward path is one Euler-Maruyama kernel and every filter one hipGraph replay."""
 import argparse
 import os
 
@@ -13,7 +14,6 @@ import torch
 from toy_sb_gibbs import common_args, sb_setting
 from fbs_amd import ops
 from fbs_amd.samplers import bootstrap_filter, stratified
-from fbs_amd.sdes import euler_maruyama
 
 
 def main(argv=None):
@@ -29,8 +29,7 @@ def main(argv=None):
     def fwd_ys_sampler(key_):                                                        # sb/filter.py:137-148
         key_x0, key_em = ops.split(key_)
         x0_ = g.gp_posterior_sampler(key_x0) if args.x0 == 'proper' else ops.normal(key_x0, (d,), device=dev)
-        xy0 = torch.cat([x0_, g.y0])
-        return euler_maruyama(key_em, xy0, g.ts, g.drift, lambda t: 1., integration_nsteps=10, return_path=True)[:, d:]
+        return g.em_path(key_em, x0_, g.y0)[:, d:]
 
     def conditional_sampler(key_):                                                   # :152-164
         key_fwd, key_bwd, key_bf = ops.split(key_, 3)

@@ -5,7 +5,9 @@ Counterpart of the reference driver experiments/sb/gibbs.py (same flags, key sch
 samples (nsamples, d), gp_mean, gp_cov).  The forward process is an Euler-Maruyama simulation of the bridge's
 affine drift (10 sub-steps per interval) and the closures are written out by the experiment, as in the reference,
 so this runs on the closure tier: the T-loop is a host loop, every sampler-owned operation in it a libfbsmi
-kernel."""
+kernel.  With --fused the setting is built from fbs_amd.GaussianSBBridge instead: the same bridge as affine tables, every
+Gibbs sweep one hipGraph replay of the fused engine (Euler-Maruyama forward paths included), the chain driven on the
+device with the reference's key schedule."""
 import argparse
 import math
 import os
@@ -28,6 +30,7 @@ def common_args(parser):
     parser.add_argument('--id', type=int, default=666, help='The id of independent MC experiment.')
     parser.add_argument('--outdir', type=str, default='./sb/results')
     parser.add_argument('--quiet', action='store_true')
+    parser.add_argument('--fused', action='store_true', help='Run on the fused engine (fbs_amd.GaussianSBBridge).')
     return parser
 
 
@@ -127,10 +130,24 @@ def sb_setting(args, dev):
         chol = torch.as_tensor(np.linalg.cholesky(gp_cov), dtype=torch.float32, device=dev)
         return torch.as_tensor(gp_mean, dtype=torch.float32, device=dev) + ops.normal(key_, (d,), device=dev) @ chol   # (z @ L, as the reference writes it)
 
+    bridge = None
+    if getattr(args, 'fused', False):
+        # the same bridge as float64-built tables on the device; its closures are what the samplers dispatch on
+        from fbs_amd import GaussianSBBridge
+        bridge = GaussianSBBridge(joint_mean, joint_cov, ref_m, ref_cov, ts, du=d, sig=1., nsub=10, device=dev)
+        transition_sampler, transition_logpdf = bridge.transition_sampler, bridge.transition_logpdf
+        likelihood_logpdf, ref_sampler = bridge.likelihood_logpdf, bridge.ref_sampler
+        fwd_sampler, unpack = bridge.fwd_sampler, bridge.unpack
+
+    def em_path(key_, x0_, y0_):                                                    # euler_maruyama(key, (x0, y0), ts, drift, 1, 10)
+        if bridge is not None:
+            return bridge.fwd_sampler(key_, x0_, y0_)
+        return euler_maruyama(key_, torch.cat([x0_, y0_]), ts, drift, lambda t: 1., integration_nsteps=10, return_path=True)
+
     return SimpleNamespace(key=key, d=d, y0=y0, ts=ts, nsteps=nsteps, dt=dt, drift=drift, gp_mean=gp_mean, gp_cov=gp_cov,
                            transition_sampler=transition_sampler, transition_logpdf=transition_logpdf,
                            likelihood_logpdf=likelihood_logpdf, ref_sampler=ref_sampler, fwd_sampler=fwd_sampler,
-                           unpack=unpack, gp_posterior_sampler=gp_posterior_sampler)
+                           unpack=unpack, gp_posterior_sampler=gp_posterior_sampler, em_path=em_path, bridge=bridge)
 
 
 def main(argv=None):
@@ -146,9 +163,7 @@ def main(argv=None):
     def gibbs_init(key_):                                                           # :150-161
         key_fwd, key_bwd, key_bf = ops.split(key_, 3)
         key_x0, key_em = ops.split(key_fwd)
-        xy0 = torch.cat([ops.normal(key_x0, (d,), device=dev), y0])
-        vs = torch.flip(euler_maruyama(key_em, xy0, ts, drift, lambda t: 1., integration_nsteps=10, return_path=True)[:, d:],
-                        [0])
+        vs = torch.flip(g.em_path(key_em, ops.normal(key_x0, (d,), device=dev), y0)[:, d:], [0])
         uss = bootstrap_filter(transition_sampler, likelihood_logpdf, vs, ts, ref_sampler, key_bf, args.nparticles,
                                stratified, log=True, return_last=False)[0]
         return uss[-1, 0], bootstrap_backward_smoother(key_bwd, uss, vs, ts, transition_logpdf), \
@@ -158,7 +173,11 @@ def main(argv=None):
     x0, us_star, bs_star = gibbs_init(subkey)
     samples = torch.empty((args.nsamples, d), device=dev)
     accs = np.zeros(args.nsamples, bool)
-    for i in range(args.nsamples):                                                  # :176-184
+    if g.bridge is not None:
+        # the whole loop on the device: per sweep key, subkey = split(key); gibbs_kernel(subkey, ...) (:176-184)
+        sweep = g.bridge.sweep_handle(args.nparticles, args.explicit_backward, False)
+        _, _, _, samples = sweep.chain(key, x0, y0, bs_star, args.nsamples)
+    for i in range(0 if g.bridge is not None else args.nsamples):                   # :176-184
         key, subkey = ops.split(key)
         x0, us_star, bs_star, acc = gibbs_kernel(subkey, x0, y0, us_star, bs_star, ts, fwd_sampler, None, unpack,
                                                  args.nparticles, transition_sampler, transition_logpdf, likelihood_logpdf,
@@ -169,7 +188,8 @@ def main(argv=None):
     if not args.quiet:
         burn = min(100, args.nsamples // 2)
         err = np.abs(samples[burn:].mean(axis=0) - gp_mean).max()
-        print(f'ID: {args.id} | SB Gibbs | {args.nsamples} sweeps | acc rate {accs.mean():.3f} | max |mean - gp_mean| = {err:.3f}')
+        acc = 'fused chain' if g.bridge is not None else f'acc rate {accs.mean():.3f}'
+        print(f'ID: {args.id} | SB Gibbs | {args.nsamples} sweeps | {acc} | max |mean - gp_mean| = {err:.3f}')
     os.makedirs(args.outdir, exist_ok=True)
     np.savez(os.path.join(args.outdir, f'gibbs{"-eb" if args.explicit_backward else ""}-{args.nparticles}-{args.id}'),
              samples=samples, gp_mean=gp_mean, gp_cov=gp_cov)                      # :187-188

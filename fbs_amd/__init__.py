@@ -9,8 +9,9 @@ from . import _lib  # noqa: F401
 from .ops import PRNGKey, split  # noqa: F401
 from . import ops, sdes, samplers  # noqa: F401
 from .linear_gaussian import LinearGaussianBridge  # noqa: F401
+from .gaussian_sb import GaussianSBBridge  # noqa: F401
 
-__all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "PRNGKey", "split", "build"]
+__all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "GaussianSBBridge", "PRNGKey", "split", "build"]
 
 
 def build(force: bool = False) -> str:

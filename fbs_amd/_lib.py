@@ -13,6 +13,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", "fbsmi_device.h"), os.path.join(_HERE, "csrc", "fbsmi_host.h"),
+                os.path.join(_HERE, "csrc", "fbsmi_em_path.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi.h"), os.path.join(_HERE, "..", "include", "fbsmi_math.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi_nn.h")]
 LIB_PATH = os.path.join(_HERE, "lib", "libfbsmi.so")
@@ -136,6 +137,10 @@ class LGModelStruct(C.Structure):
                 ("F", C.c_void_p), ("sqQ", C.c_void_p)]
 
 
+class EMForwardStruct(C.Structure):
+    _fields_ = [("nsub", C.c_int32), ("M", C.c_void_p), ("c", C.c_void_p), ("ddt", C.c_void_p), ("s", C.c_void_p)]
+
+
 class EMMaskStruct(C.Structure):
     _fields_ = [("du", C.c_int32), ("dv", C.c_int32), ("u_off", C.c_void_p), ("v_off", C.c_void_p),
                 ("role", C.c_void_p)]
@@ -169,6 +174,7 @@ SIGNATURES = {
     "fbsmi_backtrace": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
     "fbsmi_linear_path": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _vp, _vp]),
     "fbsmi_affine_em_path": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, C.c_int, _vp, _vp]),
+    "fbsmi_lg_em_path": (C.c_int, [_vp, C.POINTER(EMForwardStruct), _vp, _i32, _i64, _vp, _vp]),
     "fbsmi_em_update": (C.c_int, [_vp, _vp, _f, _f, _u32, _u32, _i64, _i64, _i64, _vp, _vp]),
     "fbsmi_lg_transition_sampler": (C.c_int, [C.POINTER(LGModelStruct), _i32, _f, _f, _vp, _vp, _u32, _u32, _i64, _vp, _vp]),
     "fbsmi_lg_transition_sampler_rows": (C.c_int, [C.POINTER(LGModelStruct), _i32, _f, _f, _vp, _vp, _u32, _u32, _i64, _i64, _i64, _vp, _vp]),
@@ -179,6 +185,7 @@ SIGNATURES = {
     "fbsmi_lg_gibbs_sweep": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fbsmi_lg_gibbs_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_int, _vp]),
     "fbsmi_lg_sweep_set_group": (C.c_int, [_vp, _i32, _i32]),
+    "fbsmi_lg_sweep_set_em_forward": (C.c_int, [_vp, C.POINTER(EMForwardStruct)]),
     "fbsmi_lg_gibbs_chain_groups": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, C.c_int, _vp]),
     "fbsmi_lg_sweep_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
     "fbsmi_lg_filter_create": (C.c_int, [C.POINTER(LGModelStruct), _i32, C.c_int, C.c_int, C.c_int, _i32, C.POINTER(_vp)]),

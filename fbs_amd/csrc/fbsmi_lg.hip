@@ -47,6 +47,7 @@
 
 #include "../../include/fbsmi.h"
 #include "fbsmi_device.h"
+#include "fbsmi_em_path.h"
 #include "fbsmi_host.h"
 
 namespace fbsmi {
@@ -331,6 +332,61 @@ __global__ void k_lg_path(LgDev dd, int which) {
     }
     if (which) {
         for (int k = blockIdx.x * blockDim.x + threadIdx.x; k <= d.T; k += gridDim.x * blockDim.x) {
+            const int32_t b = randint_at(d.misc[8], d.misc[9], (uint64_t)d.T + 1, (uint64_t)k, 0, d.nparticles);
+            d.acc[k] = b != d.bs[k];
+            d.bsn[k] = b;
+        }
+    }
+}
+
+// Euler-Maruyama forward process (fbsmi_lg_sweep_set_em_forward): the sweep's two forward paths are euler_maruyama
+// (fbs/sdes/simulators.py:53-106) of a matrix-affine drift with nsub sub-steps per interval, not the exact scalar transition
+// of k_lg_path.  The keys are euler_maruyama's: interval k of a path with key K draws normal(split(K, T)[k], (nsub, D)).
+struct EmDev {
+    EmTables t;
+    float* xi;   // [C][2][T*nsub*D]: the noise of both paths, drawn by k_lg_em_noise beside the key derivation's successors
+};
+
+// replaces k_lg_noise: both paths' noise, sub-step by sub-step ([k][j][i]), path 2 only with explicit_backward
+__global__ void k_lg_em_noise(LgDev dd, EmDev e) {
+    const LgDev d = chain_view(dd, blockIdx.y);
+    const uint64_t per = (uint64_t)e.t.nsub * d.D, n = (uint64_t)d.T * per;
+    float* xi = e.xi + 2 * n * blockIdx.y;
+    for (uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; q < n; q += (uint64_t)gridDim.x * blockDim.x) {
+        const int k = (int)(q / per);
+        const uint64_t o = q - (uint64_t)k * per;
+        uint32_t a0, a1;
+        split_at(d.misc[0], d.misc[1], d.T, k, a0, a1);
+        xi[q] = normal_at(a0, a1, per, o);
+        if (d.eb) {
+            split_at(d.misc[6], d.misc[7], d.T, k, a0, a1);
+            xi[n + q] = normal_at(a0, a1, per, o);
+        }
+    }
+}
+
+// replaces k_lg_path, one workgroup per chain: which = 0 from (x0, y0) -> us_star, vs time-reversed (gibbs.py:127-130);
+// which = 1 from (x0n, y0) -> usn (gibbs.py:155), bs_next, acc (gibbs.py:156,168)
+__global__ void __launch_bounds__(kEmPathMaxD) k_lg_em_path(LgDev dd, EmDev e, int which) {
+    __shared__ float xs[2 * kEmPathMaxD];
+    const LgDev d = chain_view(dd, blockIdx.y);
+    const int c = threadIdx.x;
+    const size_t per = (size_t)e.t.nsub * d.D;
+    const float* xi = e.xi + 2 * (size_t)d.T * per * blockIdx.y + (which ? (size_t)d.T * per : 0);
+    float x = 0.0f;
+    float* dst = nullptr;
+    int stride = 0, col = 0;
+    if (c < d.D) {
+        x = c < d.du ? (which ? d.x0n[c] : d.x0[c]) : d.y0[c - d.du];
+        dst = c < d.du ? (which ? d.usn : d.us_star) : (which ? nullptr : d.vs);
+        stride = c < d.du ? d.du : d.dv;
+        col = c < d.du ? c : c - d.du;
+        if (dst) dst[(size_t)d.T * stride + col] = x;
+    }
+    em_path_run(e.t, d.T, d.D, x, xs, [&](int k, int j) { return xi[((size_t)k * e.t.nsub + j) * d.D + c]; },
+                [&](int k, float v) { if (dst) dst[(size_t)(d.T - 1 - k) * stride + col] = v; });
+    if (which) {
+        for (int k = threadIdx.x; k <= d.T; k += blockDim.x) {
             const int32_t b = randint_at(d.misc[8], d.misc[9], (uint64_t)d.T + 1, (uint64_t)k, 0, d.nparticles);
             d.acc[k] = b != d.bs[k];
             d.bsn[k] = b;
@@ -3685,6 +3741,8 @@ struct fbsmi_lg_sweep {
     bool tree_step = true;  // FBSMI_TREE_STEP=0: keep the cdf launch also where the two-launch step applies
     int tree_halves = -1;   // FBSMI_TREE_HALVES=1|2|4: tiles per workgroup of k_lg_prop1t (unset: as many as there are tiles per CU, up to 4)
     int debug_mask = 7;  // FBSMI_DEBUG_STEP_MASK: bit0 norm, bit1 cdf, bit2 prop (timing experiments only)
+    bool em = false;     // fbsmi_lg_sweep_set_em_forward: Euler-Maruyama forward paths (k_lg_em_noise, k_lg_em_path)
+    EmDev emd{};
     std::vector<hipEvent_t> prof_ev[kNumProfKernels];  // pairs (start, stop)
     double prof_us[kNumProfKernels] = {0, 0, 0};
     int64_t prof_n[kNumProfKernels] = {0, 0, 0};
@@ -3775,14 +3833,21 @@ int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
     const int nb = d.nb;
     const dim3 gone(1, d.C), gtile(nb, d.C);
     k_lg_keys<<<gone, kBlock, 0, st>>>(d, chain);
-    {
+    const unsigned em_block = (unsigned)((d.D + 63) / 64 * 64);
+    if (s->em) {
+        const int64_t n = (int64_t)d.T * s->emd.t.nsub * d.D;
+        int g = (int)((n + 255) / 256);
+        g = g < 1 ? 1 : (g > 1024 ? 1024 : g);
+        k_lg_em_noise<<<dim3(g, d.C), 256, 0, st>>>(d, s->emd);
+    } else {
         const int64_t n = (int64_t)d.T * d.D;
         int g = (int)((n + 255) / 256);
         g = g < 1 ? 1 : (g > 1024 ? 1024 : g);
         k_lg_noise<<<dim3(g, d.C), 256, 0, st>>>(d);
     }
     const int gpath = (d.D + 63) / 64;
-    k_lg_path<<<dim3(gpath, d.C), 64, 0, st>>>(d, 0);
+    if (s->em) k_lg_em_path<<<dim3(1, d.C), em_block, 0, st>>>(d, s->emd, 0);
+    else k_lg_path<<<dim3(gpath, d.C), 64, 0, st>>>(d, 0);
     // wide models: MFMA drift, one workgroup per (32 slots, 32 drift rows)
     const int w_nrt = (d.D + kWideTile - 1) / kWideTile, w_Kp = (d.D + 15) / 16 * 16;
     const int w_S = wide_plane_row(w_Kp);
@@ -3909,7 +3974,8 @@ int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
         LG_DISPATCH(s, (void)DMAX; (k_lg_norm<ITEMS, 1><<<gtile, kBlock, 0, st>>>(d, d.T)));
         LG_DISPATCH(s, (void)DMAX; (k_lg_cdf<ITEMS, 1><<<gtile, kBlock, 0, st>>>(d, d.T)));
         k_lg_force_move<<<gone, 64, 0, st>>>(d);
-        k_lg_path<<<dim3(gpath > (d.T + 64) / 64 ? gpath : (d.T + 64) / 64, d.C), 64, 0, st>>>(d, 1);
+        if (s->em) k_lg_em_path<<<dim3(1, d.C), em_block, 0, st>>>(d, s->emd, 1);
+        else k_lg_path<<<dim3(gpath > (d.T + 64) / 64 ? gpath : (d.T + 64) / 64, d.C), 64, 0, st>>>(d, 1);
     } else {
         LG_DISPATCH(s, (void)DMAX; (k_lg_norm<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T)));
         LG_DISPATCH(s, (void)DMAX; (k_lg_cdf<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T)));
@@ -4260,6 +4326,20 @@ int fbsmi_lg_gibbs_chain(fbsmi_lg_sweep* s, uint32_t* key, float* x0, const floa
         if (rc) return rc;
     }
     return chain_end(s, key, x0, bs_star, ust);
+}
+
+int fbsmi_lg_sweep_set_em_forward(fbsmi_lg_sweep* s, const fbsmi_em_forward* f) {
+    if (!s || !f || f->nsub < 1 || !f->M || !f->c || !f->ddt || !f->s)
+        return fail(FBSMI_ERR_ARG, "lg_sweep_set_em_forward: bad arguments");
+    if (s->graph_single || s->graph_chain || s->em)
+        return fail(FBSMI_ERR_ARG, "lg_sweep_set_em_forward: call it once, before the handle's first sweep");
+    const LgDev& d = s->d;
+    float* xi = nullptr;
+    if (dev_alloc(s, &xi, 2 * (size_t)d.C * d.T * (size_t)f->nsub * d.D)) return FBSMI_ERR_HIP;
+    s->emd.t = EmTables{f->nsub, f->M, f->c, f->ddt, f->s};
+    s->emd.xi = xi;
+    s->em = true;
+    return FBSMI_OK;
 }
 
 int fbsmi_lg_sweep_set_group(fbsmi_lg_sweep* s, int32_t nchains_total, int32_t first_chain) {

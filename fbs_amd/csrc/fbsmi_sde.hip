@@ -8,6 +8,9 @@
 //                           (fbs/sdes/simulators.py:53-106) specialised to the Doob bridge drift of
 //                           a scalar linear SDE (linear.py:36-45,83-92; simulators.py:126-160),
 //                           i.e. bridge_sampler of fbs/samplers/gibbs.py:17-20
+//   fbsmi_lg_em_path      : Euler-Maruyama with sub-steps for a time-dependent MATRIX-affine drift,
+//                           x += (M_r x + c_r) ddt + s_r xi (the forward process of the Gaussian Schrodinger bridge,
+//                           experiments/sb/gibbs.py:137-139), one workgroup per path (fbsmi_em_path.h)
 //   fbsmi_lg_transition_sampler / _likelihood_logpdf / _transition_logpdf :
 //                           the closures of experiments/toy/gp_gibbs.py:120-135 on (n, du) row-major
 //                           particles, same arithmetic as the fused sweep
@@ -17,6 +20,7 @@
 
 #include "../../include/fbsmi.h"
 #include "fbsmi_device.h"
+#include "fbsmi_em_path.h"
 #include "fbsmi_host.h"
 
 namespace fbsmi {
@@ -58,6 +62,19 @@ __global__ void k_affine_em_path(const uint32_t* keys, const float* A, const flo
         out[(int64_t)(k + 1) * D + c] = x;
     }
     if (replace_last) out[(int64_t)T * D + c] = tg;
+}
+
+// Matrix-affine Euler-Maruyama path (include/fbsmi.h, fbsmi_em_forward): one workgroup; the noise of sub-step j of interval
+// k is element j*D + i of normal(keys[k], (nsub, D)), drawn one sub-step ahead of its use.
+__global__ void __launch_bounds__(kEmPathMaxD) k_lg_em_path_solo(const uint32_t* keys, EmTables t, const float* x0, int T,
+                                                                 int D, float* out) {
+    __shared__ float xs[2 * kEmPathMaxD];
+    const int i = threadIdx.x;
+    const uint64_t n = (uint64_t)t.nsub * (uint64_t)D;
+    if (i < D) out[i] = x0[i];
+    em_path_run(t, T, D, i < D ? x0[i] : 0.0f, xs,
+                [&](int k, int j) { return normal_at(keys[2 * k], keys[2 * k + 1], n, (uint64_t)j * D + i); },
+                [&](int k, float x) { out[(size_t)(k + 1) * D + i] = x; });
 }
 
 // One Euler-Maruyama sub-step for a drift the caller evaluated (any closure: a score network, an SDE's drift):
@@ -185,6 +202,17 @@ int fbsmi_em_update(const float* x, const float* drift, float ddt, float c, uint
     FBSMI_NEED(blocks <= 0x7fffffff, "em_update: too many elements");
     k_em_update<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, drift, ddt, c, k0, k1, (uint64_t)n_total,
                                                                              (uint64_t)offset, n, out);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_lg_em_path(const uint32_t* keys, const fbsmi_em_forward* f, const float* x0, int32_t T, int64_t D, float* out,
+                     void* stream) {
+    FBSMI_NEED(keys && f && x0 && out && T >= 1 && D >= 1, "lg_em_path: bad arguments");
+    FBSMI_NEED(f->nsub >= 1 && f->M && f->c && f->ddt && f->s, "lg_em_path: bad forward tables");
+    if (D > kEmPathMaxD) return fail(FBSMI_ERR_UNSUPPORTED, "lg_em_path: D > 256 is not supported");
+    const EmTables t{f->nsub, f->M, f->c, f->ddt, f->s};
+    k_lg_em_path_solo<<<1, (unsigned)((D + 63) / 64 * 64), 0, (hipStream_t)stream>>>(keys, t, x0, T, (int)D, out);
     FBSMI_LAUNCH_CHECK();
     return FBSMI_OK;
 }

@@ -73,12 +73,15 @@ class _Closure:
 
 class LinearGaussianBridge:
     def __init__(self, m0, cov0, sde: LinearSDE, ts, du: int, device=None, dt: Optional[float] = None):
-        self.device = torch.device(device) if device is not None else ops._default_device()
         self.sde = sde
-        self.ts_np = np.asarray(ts, np.float64).reshape(-1)
         self.m0 = np.asarray(m0, np.float64).reshape(-1)
         self.cov0 = np.asarray(cov0, np.float64)
-        tab = lg_tables(m0, cov0, sde, ts, du, dt)
+        self._setup(lg_tables(m0, cov0, sde, ts, du, dt), ts, device)
+
+    def _setup(self, tab: dict, ts, device):
+        """Device copies of the per-step tables `tab` (lg_tables' keys) on the grid ts, and the closures on them."""
+        self.device = torch.device(device) if device is not None else ops._default_device()
+        self.ts_np = np.asarray(ts, np.float64).reshape(-1)
         self.tables64 = tab
         self.du, self.dv = tab["du"], tab["dv"]
         self.D = self.du + self.dv
@@ -283,7 +286,10 @@ class LGSweep:
         with torch.cuda.device(model.device):
             _lib.call("fbsmi_lg_sweep_create", C.byref(model.struct), nparticles, int(eb), int(ef), int(store),
                       self.C, C.byref(h))
-        self.h = h
+            self.h = h
+            em = getattr(model, "em_struct", None)   # Euler-Maruyama forward process (fbs_amd.gaussian_sb.GaussianSBBridge)
+            if em is not None:
+                _lib.call("fbsmi_lg_sweep_set_em_forward", self.h, C.byref(em))
         if _group is not None:
             _lib.call("fbsmi_lg_sweep_set_group", self.h, int(_group[0]), int(_group[1]))
 

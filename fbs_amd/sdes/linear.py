@@ -217,13 +217,18 @@ def make_gaussian_bw_sb(mean0, cov0, mean1, cov1, sig: float = 1.):
         qt = (1 - t) * cov0 + t * C_sig
         return pt - qt.T - sig ** 2 * t * eye
 
-    def drift(x, t):
+    def drift_affine(t):
+        """drift(x, t) = M x + const: (M, const) in float64."""
         t = float(t)
         M = s(t).T @ np.linalg.inv(marginal_cov(t))          # (d, d)
-        const = mean1 - mean0 - M @ marginal_mean(t)
+        return M, mean1 - mean0 - M @ marginal_mean(t)
+
+    def drift(x, t):
+        M, const = drift_affine(t)
         if isinstance(x, torch.Tensor):
             Mt = torch.as_tensor(M, dtype=x.dtype, device=x.device)
             return x @ Mt.T + torch.as_tensor(const, dtype=x.dtype, device=x.device)
         return np.asarray(x) @ M.T + const
 
+    drift.affine = drift_affine      # the coefficients themselves (fbs_amd.gaussian_sb tabulates them)
     return marginal_mean, marginal_cov, drift

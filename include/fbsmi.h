@@ -115,6 +115,30 @@ int fbsmi_affine_em_path(const uint32_t* keys, const float* A, const float* B, c
                          const float* target, const float* x0, int32_t T, int32_t nsub, int64_t D, int replace_last,
                          float* out, void* stream);
 
+/* Euler-Maruyama with nsub sub-steps per interval for a time-dependent MATRIX-affine drift -- euler_maruyama
+ * (fbs/sdes/simulators.py:53-106) of the Gaussian Schrodinger bridge's forward drift (experiments/sb/gibbs.py:137-139,
+ * fbs/sdes/linear.py:397-457).  Numeric specification:
+ *   interval k of a grid ts (T+1 points): h64 = |ts[k+1] - ts[k]| / nsub (float64), ddt[k] = float32(h64), sub-step
+ *   times tau_{k,j} = linspace(ts[k], ts[k+1] - h64, nsub)[j];
+ *   sub-step r = k*nsub + j has float32 tables built in float64 on the host and rounded once:
+ *     M[r] (D x D, row-major), c[r] (D), s[r] = float32(dispersion(tau_{k,j}) * sqrt(h64));
+ *   noise xi_k = normal(split(key, T)[k], (nsub, D)), row j for sub-step j (euler_maruyama's key schedule);
+ *   f_i  = c[r][i] + sum_c M[r][i][c] * x_c      -- one fbsmi_fmaf chain started at c[r][i], c = 0 .. D-1
+ *   x_i <- (x_i + f_i * ddt[k]) + s[r] * xi_k[j][i]   -- separate float32 operations, nothing else fused
+ *   out[0] = x0, out[k+1] = x after interval k.
+ * Tables are device arrays covering T*nsub sub-steps of dimension D. */
+typedef struct fbsmi_em_forward {
+    int32_t nsub;
+    const float* M;    /* [T*nsub][D][D] */
+    const float* c;    /* [T*nsub][D] */
+    const float* ddt;  /* [T] */
+    const float* s;    /* [T*nsub] */
+} fbsmi_em_forward;
+
+/* One path, one workgroup: keys (T,2) uint32 = split(key, T), x0 (D), out (T+1, D); D <= 256. */
+int fbsmi_lg_em_path(const uint32_t* keys, const fbsmi_em_forward* f, const float* x0, int32_t T, int64_t D, float* out,
+                     void* stream);
+
 /* One Euler-Maruyama sub-step for a drift tensor the caller evaluated (a score network, any closure):
  *   out[e] = (x[e] + drift[e] * ddt) + c * xi[offset + e],  xi = jax.random.normal(key, (n_total,)) drawn in the kernel,
  * the loop body of euler_maruyama (fbs/sdes/simulators.py:94-99) with c = dispersion(t) * sqrt(ddt); sub-step j of an interval
@@ -188,6 +212,12 @@ int fbsmi_lg_gibbs_chain(fbsmi_lg_sweep* s, uint32_t* key, float* x0, const floa
 int fbsmi_lg_sweep_set_group(fbsmi_lg_sweep* s, int32_t nchains_total, int32_t first_chain);
 int fbsmi_lg_gibbs_chain_groups(fbsmi_lg_sweep* const* groups, int32_t ngroups, uint32_t* key, float* x0, const float* y0,
                                 int32_t* bs_star, int32_t nsweeps, float* x0s, int use_graph, void* stream);
+/* Forward process by Euler-Maruyama: the sweep's two forward paths (key_fwd from (x0, y0) and, with explicit_backward,
+ * the fresh reference path from (x0_next, y0)) follow fbsmi_lg_em_path on these tables instead of the exact transition
+ * F / sqQ, which the handle then never reads (an SB model passes placeholders).  The CSMC part reads G, g, sd, lognorm as
+ * always.  Call once, before the handle's first sweep; the tables must cover the model's T and D = du + dv and outlive the
+ * handle.  Allocates the handle's noise workspace (2 * nchains * T * nsub * D floats). */
+int fbsmi_lg_sweep_set_em_forward(fbsmi_lg_sweep* s, const fbsmi_em_forward* f);
 /* Parity views of the last sweep: copies view `which` into dst (device, nullable) and reports its
  * element count.  which: 0 final particles (n,du) row-major, 1 final normalised log-weights (n),
  * 2 As (T,n) int32, 3 uss (T+1,n,du), 4 log_wss (T+1,n) [2-4 only with store_path],
