@@ -38,8 +38,11 @@
 //   N = 2^k + 1 (explicit_final on such an ensemble) : the same two kernels over the first 2^k slots' tree + one extra tile
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdlib>
+#include <map>
+#include <mutex>
 #include <new>
 #include <string>
 #include <utility>
@@ -102,7 +105,7 @@ struct LgDev {
     float* lpw;                             // [N][dv rounded up to 4] per-row log-density terms of the wide path
     int32_t* anc;                           // [N] ancestors of the current step (wide path)
     float* xiw;                             // [2][N][du] a step's noise, drawn ahead of the launch that uses it (wide models): slot s & 1
-                                            // for the one-tile Gibbs step (drawn DURING the previous launch), slot 0 for k_lgw_noise
+                                            // for the one-tile Gibbs step (drawn DURING the previous launch), slot 0 for the fat drift kernel
     float* uw;                              // [2][2][N] one-tile wide Gibbs step: the kill-test and redraw uniforms of every source slot
                                             // (resamplings.py:71-74), drawn ahead like the noise: slot s & 1, u1 then u2 (nullable)
     int lh_w, lh_j;                         // their depths
@@ -123,35 +126,12 @@ struct LgDev {
     // chain bookkeeping
     float** x0s_slot;  // device slot holding the x0s pointer (or null)
     int32_t* counter;  // device sweep counter
-    unsigned long long* dbg;  // [64] in-kernel stamps (diagnostic build -DFBSMI_STAMPS only)
     // fused particle filters (bootstrap_filter / pmcmc_filter_step)
     int flow;        // 0 bootstrap_filter (smc.py:58-74), 1 pmcmc_filter_step (smc.py:138-152)
     int systematic;  // resampling: 0 stratified, 1 systematic (resampling.py:43-59)
     float logn;      // log(nparticles)
     float* ell;      // [C] running log-likelihood (flow 1) / negative log-likelihood (flow 0)
 };
-
-#ifdef FBSMI_STAMPS
-// diagnostic build: one lane of the middle workgroup records (100 MHz wall clock, shader clock)
-#define FBSMI_STAMP(i)                                                                   \
-    if (blockIdx.x == gridDim.x / 2 && blockIdx.y == 0 && threadIdx.x == 0) {            \
-        d.dbg[2 * (i)] = __builtin_amdgcn_s_memrealtime();                               \
-        d.dbg[2 * (i) + 1] = __builtin_amdgcn_s_memtime();                               \
-    }
-// ... and every workgroup of the LAST step of the LAST sweep of a chain call records its entry / exit time in a slot of its
-// own (in the cdfJ array, which the two-launch step does not use; view 8): how far a launch's first and last workgroup are
-// apart.  (A shared minimum / maximum would serialise 256 atomics at the end of the launch and measure itself.)
-#define FBSMI_SPAN_IN(i, step, last_sweep)                                                                   \
-    if (threadIdx.x == 0 && (step) == d.T - 1 && *d.counter == (last_sweep))                                  \
-        reinterpret_cast<unsigned long long*>(d.cdfJ)[(i) * 1024 + 2 * (blockIdx.x + gridDim.x * blockIdx.y)] = __builtin_amdgcn_s_memrealtime();
-#define FBSMI_SPAN_OUT(i, step, last_sweep)                                                                  \
-    if (threadIdx.x == 0 && (step) == d.T - 1 && *d.counter == (last_sweep))                                  \
-        reinterpret_cast<unsigned long long*>(d.cdfJ)[(i) * 1024 + 2 * (blockIdx.x + gridDim.x * blockIdx.y) + 1] = __builtin_amdgcn_s_memrealtime();
-#else
-#define FBSMI_STAMP(i)
-#define FBSMI_SPAN_IN(i, step, last_sweep)
-#define FBSMI_SPAN_OUT(i, step, last_sweep)
-#endif
 
 // The view of chain c: every per-chain array advanced to that chain's slice (all per-chain arrays
 // are laid out [C][...]).
@@ -648,8 +628,6 @@ __global__ void __launch_bounds__(kBlock) k_lg_norm(LgDev dd, int s) {
         bx = blockIdx.x >> 3;
     }
     const LgDev d = chain_view(dd, blockIdx.y);
-    if (MODE == 0) { FBSMI_STAMP(2) }
-    if (MODE == 0 && PUB) { FBSMI_SPAN_IN(0, s, 4) }
     __shared__ float xch[4][4];
     const int base = (bx * kBlock + threadIdx.x) * ITEMS;
     const int i_ref = d.bs[MODE == 0 ? s : d.T];
@@ -659,7 +637,6 @@ __global__ void __launch_bounds__(kBlock) k_lg_norm(LgDev dd, int s) {
     // two-level logsumexp: combine the per-workgroup (max, sumexp) pairs the previous kernel published
     float lse, Mraw;
     lse_from_partials(d.bmax, d.bsumexp, d.nb, xch[0], xch[1], lse, Mraw);
-    if (MODE == 0) { FBSMI_STAMP(14) }
     const float w_max = fbsmi_expf(Mraw - lse);  // == max_i w_i: fbsmi_expf is monotone
     const float w_k = MODE == 1 ? fbsmi_expf(l_ref - lse) : 0.0f;
     float xw[ITEMS], xj[ITEMS];
@@ -714,15 +691,13 @@ __global__ void __launch_bounds__(kBlock) k_lg_norm(LgDev dd, int s) {
             d.scal[2] = w_k;
         }
     }
-    if (MODE == 0) { FBSMI_STAMP(3) }
-    if (MODE == 0 && PUB) { FBSMI_SPAN_OUT(0, s, 4) }
 }
 
 // (Round 3 also built this kernel with ONE WAVE PER TILE -- four tiles per workgroup, four consecutive elements per lane, the
 // chunk sum as levels 0-1 of the tile tree and the wave's butterfly as levels 2-7, no exchange between waves, the logsumexp combine
 // once per four tiles; bit-exact -- on the theory that launching a quarter of the waves would shorten the launch.  It does not:
-// the workgroups of a launch enter over 0.6-1.1 us whether there are 64 or 256 of them (per-workgroup stamps, tools/stamps), and a
-// lone wave issues one instruction per ~4.4 clocks, so ~1000 instructions in one wave instead of ~370 in each of four cost
+// the workgroups of a launch enter over 0.6-1.1 us whether there are 64 or 256 of them (per-workgroup stamps), and a lone wave
+// issues one instruction per ~4.4 clocks, so ~1000 instructions in one wave instead of ~370 in each of four cost
 // 3.7 us after the normaliser is known instead of 0.9.  One chain 22.7 against 13.0 us per step, 32 chains 83 against 52.
 // Dropped: on this chip latency wants MORE, thinner waves, not fewer.)
 // ------------------------------------------------------------------------------------------
@@ -736,7 +711,6 @@ __global__ void __launch_bounds__(kBlock) k_lg_cdf(LgDev dd, int s) {
         return;
     }
     const LgDev d = chain_view(dd, blockIdx.y);
-    if (MODE == 0) { FBSMI_STAMP(4) }
     __shared__ float xch[8][4];
     __shared__ float bc[4][2];
     constexpr int TILE = kBlock * ITEMS;
@@ -797,7 +771,6 @@ __global__ void __launch_bounds__(kBlock) k_lg_cdf(LgDev dd, int s) {
     float s3[3] = {chunk_total<kTopItems>(pw), chunk_total<kTopItems>(pj), chunk_total<ITEMS>(wv)}, t3[3];
     TreePath p3[3];
     block_upsweep_n<3>(s3, p3, xch[0], t3);
-    FBSMI_STAMP(15)
     // J_prob[i*] = max(1 - sum(J_prob with [i*] = 0), 0)   (resamplings.py:80-82)
     const float Ji = fmaxf(1.0f - t3[1], 0.0f);
     // phase 2: the tile that holds i* (its tree sum changes) and this workgroup's own J tile
@@ -839,7 +812,6 @@ __global__ void __launch_bounds__(kBlock) k_lg_cdf(LgDev dd, int s) {
         }
         __syncthreads();
     }
-    FBSMI_STAMP(16)
     float P = bc[0][0], E = bc[0][1];
     float c[ITEMS];
     block_descend(P, E, p3[2]);
@@ -852,114 +824,13 @@ __global__ void __launch_bounds__(kBlock) k_lg_cdf(LgDev dd, int s) {
     chunk_scan<ITEMS>(xo, P, E, c);
     chunk_store<ITEMS>(d.cdfJ, base, d.N, c);
     if (ITEMS == 1 && hp_node && hp_depth < d.lh_j) d.hpJ[hp_node] = c[0];
-    FBSMI_STAMP(5)
 }
 
 // ------------------------------------------------------------------------------------------
 // prop: resample (killing, conditional) + gather + Euler-Maruyama + pin + log-weight
 // ------------------------------------------------------------------------------------------
-template <int ITEMS, int DMAX>
-__global__ void __launch_bounds__(kBlock) k_lg_prop(LgDev dd, int s) {
-    const LgDev d = chain_view(dd, blockIdx.y);
-    __shared__ float xch[2][4];
-    __shared__ float heapW[kHeapSize], heapJ[kHeapSize];
-    const int N = d.N;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
-    const float lastJ = d.cdfJ[N - 1];
-    const float last = d.cdf[N - 1];
-    const float w_max = d.scal[1];
-    float hw = 0.0f, hj = 0.0f;
-    if (threadIdx.x >= 1 && threadIdx.x < kHeapSize) {
-        const int mid = heap_node_mid(threadIdx.x, N);
-        hw = d.cdf[mid];
-        hj = d.cdfJ[mid];
-    }
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const int base = (blockIdx.x * kBlock + threadIdx.x) * ITEMS;
-    // the slot's own noise depends on nothing that is still in flight: draw it while the heap
-    // gathers are outstanding
-    constexpr bool kHoistNoise = ITEMS * DMAX <= 16;   // more than that would spill
-    float xi[kHoistNoise ? ITEMS : 1][kHoistNoise ? DMAX : 1];
-    const float u3 = __uint_as_float(kt[4]);
-    if (kHoistNoise) {
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i)
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r)
-                xi[kHoistNoise ? i : 0][kHoistNoise ? r : 0] =
-                    (r < d.du && base + i < N) ? normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)(base + i) * d.du + r)
-                                              : 0.0f;
-    }
-    if (threadIdx.x < kHeapSize) {
-        heapW[threadIdx.x] = hw;
-        heapJ[threadIdx.x] = hj;
-    }
-    __syncthreads();
-    // J = choice(key_3, N, (), p=J_prob)  (resamplings.py:84); roll by j - J (:85).  Every thread
-    // repeats the (identical, broadcast-served) search: no further barrier is needed.
-    int shift;
-    {
-        const int J = bisect_heap(d.cdfJ, N, d.levels, heapJ, lastJ * (1.0f - u3));
-        shift = (j_ref - J) % N;
-        if (shift < 0) shift += N;
-    }
-    float lv[ITEMS];
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        const int m = base + i;
-        lv[i] = -__builtin_inff();
-        if (m < N) {
-            int src = m - shift;
-            if (src < 0) src += N;
-            const float ws = d.w[src];
-            const float u1 = uniform_at(a0, a1, (uint64_t)N, (uint64_t)src);
-            int a = src;
-            if (u1 * w_max >= ws) {  // killed (resamplings.py:71): redraw from Cat(w) (:73-74)
-                const float u2 = uniform_at(b0, b1, (uint64_t)N, (uint64_t)src);
-                a = bisect_heap(d.cdf, N, d.levels, heapW, last * (1.0f - u2));
-            }
-            if (m == j_ref) a = i_ref;  // :86
-            if (d.As) d.As[(size_t)s * N + m] = a;
-            float u[DMAX];
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * N + a] : 0.0f;
-            // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) {
-                if (r < d.du) {
-                    const float dr = drift_row<DMAX>(t, r, u, v_prev);
-                    const float z = kHoistNoise ? xi[kHoistNoise ? i : 0][kHoistNoise ? r : 0]
-                                                : normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
-                    float x = (u[r] + dr * t.dt) + t.sd * z;
-                    if (m == j_ref) x = ustar[r];
-                    un[(size_t)r * N + m] = x;
-                    if (d.uss) d.uss[((size_t)(s + 1) * N + m) * d.du + r] = x;
-                }
-            }
-            // likelihood_logpdf on the gathered particle (csmc.py:145)
-            const float l = lg_loglik<DMAX>(t, u, v, v_prev);
-            d.lw[m] = l;
-            lv[i] = l;
-        }
-    }
-    float mx, sx;
-    block_lse_partial<ITEMS>(lv, xch[0], xch[1], mx, sx);
-    if (threadIdx.x == 0) {
-        d.bmax[blockIdx.x] = mx;
-        d.bsumexp[blockIdx.x] = sx;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// prop, one slot per thread (N <= 131072): the same step as k_lg_prop, arranged around what bounds
-// it -- the number of dependent memory round trips when one chain runs alone, and the number of
+// One slot per thread (N <= 131072): the step arranged around what bounds it --
+// the number of dependent memory round trips when one chain runs alone, and the number of
 // scattered (one cache line per lane) loads when several chains fill the CUs:
 //   0. everything addressable at entry: the compact heaps the cdf kernel published (coalesced:
 //      2^11 nodes of cdf, 2^8 of cdfJ), tables, the reference row; the slot's own noise is drawn in
@@ -976,7 +847,6 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop1(LgDev dd, int s) {
     __shared__ __attribute__((aligned(16))) float heapW[kHeapSizeW];
     __shared__ float heapJ[kHeapSizeJ];
     __shared__ float win[kBlock];
-    FBSMI_STAMP(6)
     const int N = d.N;
     const uint32_t* kt = d.keytab + 8 * s;
     const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
@@ -1009,9 +879,7 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop1(LgDev dd, int s) {
     reinterpret_cast<float4*>(heapW)[2 * threadIdx.x] = hw0;
     reinterpret_cast<float4*>(heapW)[2 * threadIdx.x + 1] = hw1;
     heapJ[threadIdx.x] = hj;
-    FBSMI_STAMP(7)
     __syncthreads();
-    FBSMI_STAMP(8)
     // ---- round 1: J = choice(key_3, N, (), p=J_prob) (resamplings.py:84); roll by j - J (:85)
     const int J = bisect_uniform(d.cdfJ, N, d.levels, d.lh_j, heapJ, win, lastJ * (1.0f - u3));
     int shift = (j_ref - J) % N;
@@ -1019,7 +887,6 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop1(LgDev dd, int s) {
     int src = m - shift;
     if (src < 0) src += N;
     if (!live) src = 0;
-    FBSMI_STAMP(9)
     // ---- round 2
     const float ws = d.w[src];
     float u[DMAX];
@@ -1031,13 +898,11 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop1(LgDev dd, int s) {
     int lo, hi;
     bisect_lds_levels(N, d.lh_w, heapW, qK, lo, hi);
     const bool killed = live && (u1 * w_max >= ws);                         // :71
-    FBSMI_STAMP(10)
     // ---- rounds 3, 4
 #pragma unroll 1
     for (int rem = d.levels - d.lh_w; rem > 0; rem -= 3) bisect_round3(d.cdf, lo, hi, qK, killed);
     const bool pinned = m == j_ref;
     const int a = pinned ? i_ref : (killed ? hi : src);                     // :86
-    FBSMI_STAMP(11)
     // ---- round 5
     if (killed && !pinned) {
 #pragma unroll
@@ -1066,25 +931,21 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop1(LgDev dd, int s) {
         d.lw[m] = l;
         lv[0] = l;
     }
-    FBSMI_STAMP(12)
     float mx, sx;
     block_lse_partial<1>(lv, xch[0], xch[1], mx, sx);
     if (threadIdx.x == 0) {
         d.bmax[blockIdx.x] = mx;
         d.bsumexp[blockIdx.x] = sx;
     }
-    FBSMI_STAMP(13)
 }
 
 // ------------------------------------------------------------------------------------------
-// Several slots per thread (N > 131072: tiles of 1024 / 4096 slots, ITEMS = 4 / 16), the HBM-resident regime.
-// k_lg_prop above walks a thread's slots one after the other, each with its own chain of dependent probes (the search of
-// a killed slot alone is five global round trips behind eight LDS levels) and with the thread's ITEMS slots CONSECUTIVE
-// in memory -- a wave's load touches 64 cache lines.  Measured at 4 x 2^22 particles: 1.3 ms per step, 0.05 of the HBM
-// roof, the CUs waiting on ~160 serial round trips per thread.  Here:
+// Several slots per thread (N > 131072: tiles of 1024 / 4096 slots, ITEMS = 4 / 16), the HBM-resident regime: a thread
+// that walked its slots one after the other, each search with its own chain of dependent probes (a killed slot alone is
+// five global round trips behind eight LDS levels), and with its ITEMS slots CONSECUTIVE in memory (a wave's load touches
+// 64 cache lines) waits on ~160 serial round trips per step.  So:
 //   * slot i of thread t is element tile0 + i * 256 + t: every access of a wave is one contiguous run;
-//   * the slots are taken four at a time, all loads of a stage issued before the first is used, the four searches in
-//     lockstep (bisect_round3_xn): a batch costs the round trips of ONE slot;
+//   * the slots are taken four at a time, all loads of a stage issued before the first is used;
 //   * the compact heaps of both CDFs (11 / 8 levels) come from k_lg_heaps, a launch of eight workgroups behind k_lg_cdf,
 //     so a workgroup stages them with two coalesced loads per thread and a search leaves LDS with 2048 candidates left;
 //   * the tile's (max, sumexp) wants the canonical chunk order (thread t owns elements t * ITEMS ..): the new log-weights
@@ -1101,139 +962,14 @@ __global__ void __launch_bounds__(kBlock) k_lg_heaps(LgDev dd) {
     if (t < kHeapSizeJ && depth < d.lh_j) d.hpJ[t] = d.cdfJ[mid];
 }
 
-template <int ITEMS, int DMAX>
-__global__ void __launch_bounds__(kBlock) k_lg_propN(LgDev dd, int s) {
-    const LgDev d = chain_view(dd, blockIdx.y);
-    constexpr int B = ITEMS < 4 ? ITEMS : 4;       // slots in flight per thread
-    constexpr int TILE = kBlock * ITEMS;
-    __shared__ float xch[2][4];
-    __shared__ __attribute__((aligned(16))) float heapW[kHeapSizeW];
-    __shared__ float heapJ[kHeapSizeJ];
-    __shared__ float win[kBlock];
-    __shared__ __attribute__((aligned(16))) float lvs[TILE];
-    const int N = d.N;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
-    const int tile0 = blockIdx.x * TILE;
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
-    // ---- round 0
-    const float lastJ = d.cdfJ[N - 1];
-    const float last = d.cdf[N - 1];
-    const float w_max = d.scal[1];
-    static_assert(kHeapSizeW == 8 * kBlock && kHeapSizeJ == kBlock, "heap staging assumes 2048 / 256 nodes");
-    const float4 hw0 = reinterpret_cast<const float4*>(d.hpW)[2 * threadIdx.x];
-    const float4 hw1 = reinterpret_cast<const float4*>(d.hpW)[2 * threadIdx.x + 1];
-    const float hj = d.hpJ[threadIdx.x];
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const float u3 = __uint_as_float(kt[4]);
-    reinterpret_cast<float4*>(heapW)[2 * threadIdx.x] = hw0;
-    reinterpret_cast<float4*>(heapW)[2 * threadIdx.x + 1] = hw1;
-    heapJ[threadIdx.x] = hj;
-    __syncthreads();
-    // ---- round 1: J = choice(key_3, N, (), p=J_prob) (resamplings.py:84); roll by j - J (:85)
-    const int J = bisect_uniform(d.cdfJ, N, d.levels, d.lh_j, heapJ, win, lastJ * (1.0f - u3));
-    int shift = (j_ref - J) % N;
-    if (shift < 0) shift += N;
-#pragma unroll 1
-    for (int i0 = 0; i0 < ITEMS; i0 += B) {
-        int m[B], src[B];
-        bool live[B];
-#pragma unroll
-        for (int k = 0; k < B; ++k) {
-            m[k] = tile0 + (i0 + k) * kBlock + (int)threadIdx.x;
-            live[k] = m[k] < N;
-            int sc = m[k] - shift;
-            if (sc < 0) sc += N;
-            src[k] = live[k] ? sc : 0;
-        }
-        // ---- round 2: the sources' weights, rotated but contiguous
-        float ws[B], u[B][DMAX];
-#pragma unroll
-        for (int k = 0; k < B; ++k) ws[k] = d.w[src[k]];
-        float qK[B], xi[B][DMAX];
-        bool killed[B];
-        int lo[B], hi[B];
-#pragma unroll
-        for (int k = 0; k < B; ++k) {
-            const float u1 = uniform_at(a0, a1, (uint64_t)N, (uint64_t)src[k]);
-            const float u2 = uniform_at(b0, b1, (uint64_t)N, (uint64_t)src[k]);
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r)
-                xi[k][r] = r < d.du ? normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)(live[k] ? m[k] : 0) * d.du + r) : 0.0f;
-            qK[k] = last * (1.0f - u2);                                      // resamplings.py:73-74
-            bisect_lds_levels(N, d.lh_w, heapW, qK[k], lo[k], hi[k]);
-            killed[k] = live[k] && (u1 * w_max >= ws[k]);                     // :71
-        }
-        // ---- rounds 3..: the killed slots' searches, in lockstep
-#pragma unroll 1
-        for (int rem = d.levels - d.lh_w; rem > 0; rem -= 3) bisect_round3_xn<B>(d.cdf, lo, hi, qK, killed);
-        // ---- the ancestors' rows (a survivor's is its own source: contiguous; no load under a divergent branch)
-        int a[B];
-#pragma unroll
-        for (int k = 0; k < B; ++k) {
-            const bool pinned = m[k] == j_ref;
-            a[k] = pinned ? i_ref : (killed[k] ? hi[k] : src[k]);            // :86
-        }
-#pragma unroll
-        for (int k = 0; k < B; ++k) {
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) u[k][r] = r < d.du ? up[(size_t)r * N + a[k]] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < B; ++k) {
-            const bool pinned = m[k] == j_ref;
-            float l = -__builtin_inff();
-            if (live[k]) {
-                if (d.As) d.As[(size_t)s * N + m[k]] = a[k];
-                // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-                for (int r = 0; r < DMAX; ++r) {
-                    if (r < d.du) {
-                        const float dr = drift_row<DMAX>(t, r, u[k], v_prev);
-                        float x = (u[k][r] + dr * t.dt) + t.sd * xi[k][r];
-                        if (pinned) x = ustar[r];
-                        un[(size_t)r * N + m[k]] = x;
-                        if (d.uss) d.uss[((size_t)(s + 1) * N + m[k]) * d.du + r] = x;
-                    }
-                }
-                l = lg_loglik<DMAX>(t, u[k], v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
-                d.lw[m[k]] = l;
-            }
-            lvs[(i0 + k) * kBlock + threadIdx.x] = l;
-        }
-    }
-    __syncthreads();
-    float lv[ITEMS];
-    if (ITEMS % 4 == 0) {
-#pragma unroll
-        for (int i = 0; i < ITEMS; i += 4) {
-            const float4 q4 = *reinterpret_cast<const float4*>(lvs + threadIdx.x * ITEMS + i);
-            lv[i] = q4.x; lv[i + 1] = q4.y; lv[i + 2] = q4.z; lv[i + 3] = q4.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) lv[i] = lvs[threadIdx.x * ITEMS + i];
-    }
-    float mx, sx;
-    block_lse_partial<ITEMS>(lv, xch[0], xch[1], mx, sx);
-    if (threadIdx.x == 0) {
-        d.bmax[blockIdx.x] = mx;
-        d.bsumexp[blockIdx.x] = sx;
-    }
-}
-
-// The same with the killed sources' searches COMPACTED: only ~1 - mean(w) / max(w) of the slots are killed (a few per cent
-// when the weights are as flat as a short Euler step leaves them), yet in k_lg_propN every wave walks the 11 LDS levels and
-// the four probe rounds for every one of its slots, because some lane of it usually has a killed one -- a third of that
-// kernel's instructions.  Here the kill tests run first (phase 1) and push the killed slots of the tile into an LDS queue
-// (one LDS atomic per wave and batch); phase 2 hands the queue out one entry per thread -- redraw uniform, LDS levels,
-// probe rounds, all lanes busy --; phase 3 gathers, propagates and weights.  The ancestors found in phase 2 wait in the
-// LDS array that afterwards carries the new log-weights to the chunk-ordered reduction (same owner thread per element).
+// k_lg_propQ: the killed sources' searches COMPACTED.  Only ~1 - mean(w) / max(w) of the slots are killed (a few per cent
+// when the weights are as flat as a short Euler step leaves them), yet a wave that searched in place would walk the 11 LDS
+// levels and the four probe rounds for every one of its slots, because some lane of it usually has a killed one.  Here the
+// kill tests run first (phase 1) and push the killed slots of the tile into an LDS queue (one LDS atomic per wave and
+// batch); phase 2 hands the queue out two entries per thread, their searches in lockstep (bisect_round3_xn) -- redraw
+// uniform, LDS levels, probe rounds, all lanes busy --; phase 3 gathers, propagates and weights.  The ancestors found in
+// phase 2 wait in the LDS array that afterwards carries the new log-weights to the chunk-ordered reduction (same owner
+// thread per element).
 template <int ITEMS, int DMAX>
 __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
     const LgDev d = chain_view(dd, blockIdx.y);
@@ -1649,8 +1385,6 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
     __shared__ float part[2][4 * HALVES];
     __shared__ int Jsh;
     __shared__ float lastsh;
-    FBSMI_STAMP(6)
-    FBSMI_SPAN_IN(1, s, 4)
     const int N = d.N, tid = threadIdx.x & (kBlock - 1), half = threadIdx.x / kBlock;
     int bx = blockIdx.x;
     if (dd.pin) {   // (pinned launches use HALVES == 1)
@@ -1682,7 +1416,6 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
 #pragma unroll
     for (int r = 0; r < DMAX; ++r)
         xi[r] = r < d.du ? normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)(live ? m : 0) * d.du + r) : 0.0f;
-    FBSMI_STAMP(7)
     float last, rootW;
     int J;
     if (HALVES == 1) {
@@ -1708,7 +1441,6 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
     int src = m - shift;
     if (src < 0) src += N;
     if (!live) src = 0;
-    FBSMI_STAMP(9)
     // ---- round 2
     const float ws = d.w[src];
     float u[DMAX];
@@ -1721,7 +1453,6 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
     int tile[1], h[1], hi[1] = {0};
     tree_search_lds(L, d.nb - d.plus1, qK[0], P[0], E[0], tile[0], h[0]);
     const bool killed[1] = {live && u1 * w_max >= ws};                      // :71
-    FBSMI_STAMP(10)
     // ---- rounds 3, 4 (killed slots only)
     // The ancestor is one of the last four leaves or the slot behind them: for narrow states its row is fetched together
     // with those leaves (one dependent round trip less).
@@ -1753,7 +1484,6 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
     }
     const bool pinned = m == j_ref;
     const int a = pinned ? i_ref : (killed[0] ? hi[0] : src);               // :86
-    FBSMI_STAMP(11)
     // ---- round 5
     if (killed[0] && !pinned) {
 #pragma unroll
@@ -1782,7 +1512,6 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
     const float l = live ? lg_loglik<DMAX>(t, u, v, v_prev) : -__builtin_inff();   // likelihood_logpdf on the gathered particle (csmc.py:145)
     if (live) d.lw[m] = l;
     lv[0] = l;
-    FBSMI_STAMP(12)
     float mx, sx;
     {   // the tile's (max, sumexp): block_lse_partial per half
         const int lane = threadIdx.x & 63, wv = (threadIdx.x >> 6) & 3, h4 = half * 4;
@@ -1800,8 +1529,6 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
         d.bmax[tileb] = mx;
         d.bsumexp[tileb] = sx;
     }
-    FBSMI_STAMP(13)
-    FBSMI_SPAN_OUT(1, s, 4)
 }
 
 // The two-launch step with TWO slots per thread (see k_lg_prop2 below for the pairing): the trees, J and the
@@ -2266,7 +1993,6 @@ __device__ __forceinline__ void lgw_pre_body(const LgDev& d, int s, bool store, 
     const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3];
     const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
     const bool live = t < N;
-    FBSMI_STAMP(25)
     // log-weights: step 0 has them from k_lgw_init, later steps sum the rows the drift kernel left
     LgwRowLoads rows;
     float l = 0.0f;
@@ -2290,20 +2016,17 @@ __device__ __forceinline__ void lgw_pre_body(const LgDev& d, int s, bool store, 
         u1 = uniform_at(a0, a1, (uint64_t)N, (uint64_t)t);
         u2 = uniform_at(b0, b1, (uint64_t)N, (uint64_t)t);
     }
-    FBSMI_STAMP(31)
     __builtin_amdgcn_sched_barrier(0);
     if (ROWS && live && (s || d.ef)) {
         l = lgw_row_add(d, rows);
         if (store) d.lw[t] = l;
     }
-    FBSMI_STAMP(26)
     // normalise (csmc.py:146).  One tile: the two-level logsumexp combine multiplies the tile's sum by
     // exp(0) = 1 and adds zeros, i.e. lse = log(sum) + max' exactly.
     float lv[1] = {live ? l : -__builtin_inff()};
     float Mraw, sx;
     block_lse_partial<1>(lv, L.xch[0], L.xch[1], Mraw, sx);
     const float lse = fbsmi_logf(sx) + finite_or_zero_f(Mraw);
-    FBSMI_STAMP(27)
     const float w_max = fbsmi_expf(Mraw - lse);
     float w = 0.0f, xj = 0.0f;
     if (live) {
@@ -2340,7 +2063,6 @@ __device__ __forceinline__ void lgw_pre_body(const LgDev& d, int s, bool store, 
         L.cJ[t] = c[0];
     }
     __syncthreads();
-    FBSMI_STAMP(28)
     // conditional killing (resamplings.py:66-86) on the LDS-resident CDFs: J and the per-source redraws are
     // independent searches, their LDS walks overlap
     const int J = searchsorted_left(L.cJ, N, d.levels, L.cJ[N - 1] * (1.0f - u3));
@@ -2359,7 +2081,6 @@ __device__ __forceinline__ void lgw_pre_body(const LgDev& d, int s, bool store, 
     }
     L.ancS[t] = a;
     __syncthreads();
-    FBSMI_STAMP(29)
 }
 
 // The same for the particle filters (bootstrap_filter smc.py:58-74, pmcmc_filter_step smc.py:138-152): row
@@ -2494,7 +2215,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm(LgDev dd, int s, int tr0, i
     const float* v_prev = d.vs + (size_t)(swap_v ? s + 1 : s) * d.dv;
     const float* v = d.vs + (size_t)(swap_v ? s : s + 1) * d.dv;
     const float* ustar = d.us_star + (size_t)(s + 1) * du;
-    FBSMI_STAMP(20)
     // ---- round 0.  Wave w stages rows / slots w, w+4, ... of the two tiles.  The ancestors are asked for
     //      first, the G tile next; the four noise draws of this thread run while both are in flight; the
     //      ancestor rows (the only dependent loads) go out as soon as the ancestors are here.
@@ -2602,7 +2322,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm(LgDev dd, int s, int tr0, i
             if (mj < N && c < du) d.uss[((size_t)s * N + mj) * du + c] = zq[q];
         }
     }
-    FBSMI_STAMP(21)
     const int Q = Kp >> 2;
     if (vec4) {
         // a lane's four columns 4 lane .. 4 lane + 3 lie inside Kp (a multiple of 16) together: ONE branch for the 64 stores (they
@@ -2627,7 +2346,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm(LgDev dd, int s, int tr0, i
         }
     }
     __syncthreads();
-    FBSMI_STAMP(22)
     // ---- drift rows: acc = g_r, then acc = fma(G[r][c], z[c], acc) for c = 0 .. D-1, on the matrix cores
     {
         const float4* ga = reinterpret_cast<const float4*>(Gs + wide_pos(16 * ar + (lane & 15), lane >> 4, S));
@@ -2658,7 +2376,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm(LgDev dd, int s, int tr0, i
             }
         }
     }
-    FBSMI_STAMP(23)
     // ---- rows < du: transition_sampler (gp_gibbs.py:120-122) + pin (csmc.py:143);
     //      rows >= du: the terms of likelihood_logpdf (gp_gibbs.py:131-135, csmc.py:145)
     if (mo < N && vec4) {
@@ -2708,39 +2425,9 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm(LgDev dd, int s, int tr0, i
             }
         }
     }
-    FBSMI_STAMP(30)
-#ifdef FBSMI_STAMPS
-    const bool stamp_tail = true;   // diagnostic build: time the tail on the last step too (its draws are never used)
-#else
-    const bool stamp_tail = false;
-#endif
-    if (KIND == 1 && !pin && !extra_noise && (s + 1 < d.T || stamp_tail)) {   // this workgroup's share of the next step's noise (pinned
-        // launches: the idle blocks on the other XCDs drew it).  Into the other half: blocks of this launch may still be reading
-        // this step's.  (Diagnostic build, last step: the draws of a step that does not exist, with step s's keys, timed only.)
-        if (s + 1 < d.T) wide_draw_ahead(d, s + 1, bx, gx);
-        else {
-            LgDev dx = d;
-            dx.keytab = d.keytab - 8;
-            wide_draw_ahead(dx, s + 1, bx, gx);
-        }
-    }
-    FBSMI_STAMP(24)
-}
-
-// The noise of one step of a large wide ensemble, normal(key_transition, (N, du)) (gp_gibbs.py:122), as its own streaming
-// launch: elements a and a + n/2 of the draw are the two words of one Threefry call (jax's random_bits), so a thread that
-// owns a pair draws two normals per block-cipher call -- half the instructions of normal_at per element inside the drift
-// kernel, where four of the seven row tiles of every workgroup spent 2.5 us each on their draws with the matrix cores idle.
-__global__ void __launch_bounds__(kBlock) k_lgw_noise(LgDev dd, int s) {
-    const LgDev d = chain_view(dd, blockIdx.y);
-    const uint32_t t0 = d.keytab[8 * s + 6], t1 = d.keytab[8 * s + 7];
-    const uint32_t n = (uint32_t)d.N * (uint32_t)d.du, half = (n + 1u) >> 1;
-    for (uint32_t a = blockIdx.x * kBlock + threadIdx.x; a < half; a += gridDim.x * kBlock) {
-        const uint32_t b = a + half;
-        uint32_t o0, o1;
-        threefry2x32(t0, t1, a, b < n ? b : 0u, o0, o1);
-        d.xiw[a] = normal_from_bits(o0);
-        if (b < n) d.xiw[b] = normal_from_bits(o1);
+    if (KIND == 1 && !pin && !extra_noise && s + 1 < d.T) {   // this workgroup's share of the next step's noise (pinned launches:
+        // the idle blocks on the other XCDs drew it).  Into the other half: blocks of this launch may still be reading this step's.
+        wide_draw_ahead(d, s + 1, bx, gx);
     }
 }
 
@@ -2757,12 +2444,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_noise(LgDev dd, int s) {
 template <bool VEC4>   // D and du multiples of four: rows are whole float4s (the usual case; the other is kept for odd sizes)
 __global__ void __launch_bounds__(kBlock) k_lgw_gemm_fat(LgDev dd, int s, int nrt, int Kp, int S) {
     const LgDev d = chain_view(dd, blockIdx.y);
-#ifdef FBSMI_STAMPS
-    // diagnostic build: every workgroup of the last step's launch records its entry / exit time (view 9; the second noise slot of
-    // chain 0, which this path does not use) -- how the launch's workgroups are spread over its duration
-    unsigned long long* span = reinterpret_cast<unsigned long long*>(dd.xiw + (size_t)dd.N * dd.du) + 2 * (blockIdx.x + gridDim.x * blockIdx.y);
-    if (threadIdx.x == 0 && s == d.T - 1) span[0] = __builtin_amdgcn_s_memrealtime();
-#endif
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     float* Gs = dyn;
     float* Zs = dyn + 4 * kWideTile * S;
@@ -2780,7 +2461,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm_fat(LgDev dd, int s, int nr
     const float* v_prev = d.vs + (size_t)s * d.dv;
     const float* v = d.vs + (size_t)(s + 1) * d.dv;
     const float* ustar = d.us_star + (size_t)(s + 1) * du;
-    FBSMI_STAMP(20)
     constexpr int kRows = kWideTile / kWaves;
     constexpr bool vec4 = VEC4;
     const int Q = Kp >> 2;
@@ -2853,7 +2533,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm_fat(LgDev dd, int s, int nr
     store_tile(Gs, gq);
     store_tile(Zs, zq);
     __syncthreads();
-    FBSMI_STAMP(21)
     const int ar = wave >> 1, ac = wave & 1;
     const int jloc = 16 * ac + (lane & 15);
     const int mo = kWideTile * ts + jloc;
@@ -2932,8 +2611,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm_fat(LgDev dd, int s, int nr
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        if (tr == 0) { FBSMI_STAMP(22) }
-        if (tr == 5) { FBSMI_STAMP(26) }
         if (mo < N && vec4) {
             // the lane's four rows are consecutive and du, D are multiples of four: all four are coordinates, or all four
             // are observation rows, or none exists -- and each kind leaves as ONE 16-byte store (they were four dword
@@ -2980,19 +2657,14 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm_fat(LgDev dd, int s, int nr
                 }
             }
         }
-        if (tr == 0) { FBSMI_STAMP(23) }
-        if (tr == 5) { FBSMI_STAMP(27) }
         if (tr + 1 < nrt) {
             __syncthreads();      // every wave is done reading the G tile
             store_tile(Gs, gq);
             __syncthreads();
         }
-        if (tr == 0) { FBSMI_STAMP(24) }
-        if (tr == 4) { FBSMI_STAMP(25) }
 #pragma unroll
         for (int vv = 0; vv < 4; ++vv) gb[vv] = gbn[vv];
     }
-    FBSMI_STAMP(30)
     // The log-weights of this workgroup's slots.  Every row tile of a slot was multiplied here, so the slot's row sum (the
     // reference's sum over the observation coordinates, in row order) is taken here too: once the tiles are done with the LDS
     // the lanes park their terms in the G tile's memory as [32 slots][dv + 4] (rows 27 quads apart at d = 100: conflict-free for
@@ -3027,9 +2699,6 @@ __global__ void __launch_bounds__(kBlock) k_lgw_gemm_fat(LgDev dd, int s, int nr
             }
         }
     }
-#ifdef FBSMI_STAMPS
-    if (threadIdx.x == 0 && s == d.T - 1) span[1] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 // (Round 3 built the variant this file's history kept describing -- TWO independent accumulator chains per wave: 64-row G
@@ -3703,25 +3372,27 @@ static bool xcd_round_robin_holds() {
     return ok != 0;
 }
 
-// Launch streams come from a process-wide pool of four, created once and never destroyed: handle (group) g of a batch uses
-// stream g % 4.  One stream per handle made the number of streams -- and with it the hardware queue a stream lands on -- depend
-// on how many handles a process had created before: with the queues oversubscribed two chain groups could end up sharing one
-// and a 16 us step took 29 (round 3: the d = 100 toy at 100 particles measured 3.0 ms per sweep alone and 5.9 ms when a
-// smaller ensemble's handles had been created first).
+// Launch streams come from a process-wide pool of four per device, created on first use and never destroyed: handle (group) g
+// of a batch uses stream g % 4 of its device.  One stream per handle made the number of streams -- and with it the hardware
+// queue a stream lands on -- depend on how many handles a process had created before: with the queues oversubscribed two chain
+// groups could end up sharing one and a 16 us step took 29 (round 3: the d = 100 toy at 100 particles measured 3.0 ms per
+// sweep alone and 5.9 ms when a smaller ensemble's handles had been created first).  Handles may be created from several
+// threads at once: the pool is guarded.
 constexpr int kStreamPool = 4;
 static hipStream_t pool_stream(int g) {
-    static hipStream_t pool[kStreamPool] = {nullptr, nullptr, nullptr, nullptr};
-    static int dev_of[kStreamPool] = {-1, -1, -1, -1};
+    static std::mutex mu;
+    static std::map<int, std::array<hipStream_t, kStreamPool>> pools;   // device -> its streams (value-initialised: null)
     int dev = 0;
     (void)hipGetDevice(&dev);
     const int i = ((g % kStreamPool) + kStreamPool) % kStreamPool;
-    if (!pool[i] || dev_of[i] != dev) {   // (one device per process is the rule: one rank per GPU; a second device gets fresh streams)
+    std::lock_guard<std::mutex> lock(mu);
+    hipStream_t& slot = pools[dev][i];
+    if (!slot) {
         hipStream_t st = nullptr;
         if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        pool[i] = st;
-        dev_of[i] = dev;
+        slot = st;
     }
-    return pool[i];
+    return slot;
 }
 
 struct fbsmi_lg_sweep {
@@ -3735,12 +3406,14 @@ struct fbsmi_lg_sweep {
     hipGraphExec_t graph_single = nullptr;  // one sweep, no chain bookkeeping
     hipGraphExec_t graph_chain = nullptr;   // one sweep + key split + advance
     bool profile = false;
+    // forcing switches (read_switches): they reach kernels at sizes the default selection does not give them, or turn the
+    // XCD placement off
     int two_slot_prop = -1;  // FBSMI_TWO_SLOT_PROP=0|1: never / always (where applicable) k_lg_prop2; unset: by batch size
-    bool step_launches = false;  // FBSMI_STEP_LAUNCHES=1: one launch per step also where one launch per sweep is possible
-    bool generic_prop = false;  // FBSMI_GENERIC_PROP=1: k_lg_prop also for one slot per thread (timing experiments)
     bool tree_step = true;  // FBSMI_TREE_STEP=0: keep the cdf launch also where the two-launch step applies
+    bool tree_plus1 = true;  // FBSMI_TREE_PLUS1=0: no two-launch step for N = 2^k + 1
     int tree_halves = -1;   // FBSMI_TREE_HALVES=1|2|4: tiles per workgroup of k_lg_prop1t (unset: as many as there are tiles per CU, up to 4)
-    int debug_mask = 7;  // FBSMI_DEBUG_STEP_MASK: bit0 norm, bit1 cdf, bit2 prop (timing experiments only)
+    bool pin = true;        // FBSMI_PIN=0: no pinned launches of the narrow two-launch step (LgDev.pin)
+    bool wide_pin = true;   // FBSMI_WIDE_PIN=0: no pinned launches of the one-tile wide step
     bool em = false;     // fbsmi_lg_sweep_set_em_forward: Euler-Maruyama forward paths (k_lg_em_noise, k_lg_em_path)
     EmDev emd{};
     std::vector<hipEvent_t> prof_ev[kNumProfKernels];  // pairs (start, stop)
@@ -3749,6 +3422,20 @@ struct fbsmi_lg_sweep {
 };
 
 namespace {
+
+// The forcing switches of a handle, read once at its creation
+void read_switches(fbsmi_lg_sweep* s) {
+    auto env = [](const char* name, int unset) {
+        const char* e = getenv(name);
+        return e ? atoi(e) : unset;
+    };
+    if (const char* e = getenv("FBSMI_TWO_SLOT_PROP")) s->two_slot_prop = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("FBSMI_TREE_HALVES")) s->tree_halves = atoi(e) == 1 ? 1 : (atoi(e) == 4 ? 4 : 2);
+    s->tree_step = env("FBSMI_TREE_STEP", 1) != 0;
+    s->tree_plus1 = env("FBSMI_TREE_PLUS1", 1) != 0;
+    s->pin = env("FBSMI_PIN", 1) != 0;
+    s->wide_pin = env("FBSMI_WIDE_PIN", 1) != 0;
+}
 
 template <typename T>
 int dev_alloc(fbsmi_lg_sweep* s, T** p, size_t count) {
@@ -3862,23 +3549,20 @@ int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
             if (d.N > kBlock) k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);   // several tiles: lw + partials for k_lg_norm
         }
     } else LG_DISPATCH(s, (k_lg_init<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d)));
-    const bool one_tile = d.N <= kBlock && !s->generic_prop;   // the steps need no grid-wide stage of their own
-    const bool persistent = one_tile && !d.wide && !s->profile && !s->step_launches;
+    const bool one_tile = d.N <= kBlock;   // the steps need no grid-wide stage of their own
+    const bool persistent = one_tile && !d.wide && !s->profile;
     if (persistent) LG_DISPATCH(s, (void)ITEMS; (k_lg_sweep1<DMAX><<<gone, kBlock, 0, st>>>(d)));
     for (int k = 0; one_tile && !persistent && k < d.T; ++k) {
         ProfScope p(s, 2, st);
         if (d.wide) {
-            static const int pin = [] { const char* e = getenv("FBSMI_WIDE_PIN"); return (e ? atoi(e) : 1) && xcd_round_robin_holds(); }();
             // (one chain per launch only: with two chains per launch and two chain groups in flight the pinned step measured
             // 29 us against 16 unpinned, round 3)
-            static const int pin_multi = [] { const char* e = getenv("FBSMI_WIDE_PIN_MULTI"); return e ? atoi(e) : 0; }();
-            if (pin && (d.C == 1 || (pin_multi && d.C <= 4)) && gwide.x <= 32)
+            if (s->wide_pin && xcd_round_robin_holds() && d.C == 1 && gwide.x <= 32)
                 k_lgw_gemm<1><<<dim3(gwide.x * 8, d.C), kBlock, w_lds, st>>>(d, k, 0, w_nrt, w_Kp, w_S, 3, 8 + ((2 * d.c0) & 7));
             else {
                 // (+ extra blocks that draw the next step's noise beside the step: one per 1024 elements, at most 16)
                 const int64_t tot = (int64_t)d.N * d.du;
-                static const int extra_on = [] { const char* e = getenv("FBSMI_WIDE_EXTRA"); return e ? atoi(e) : 1; }();
-                const int extra = !extra_on ? 0 : (int)((tot + 1023) / 1024 < 16 ? (tot + 1023) / 1024 : 16);
+                const int extra = (int)((tot + 1023) / 1024 < 16 ? (tot + 1023) / 1024 : 16);
                 k_lgw_gemm<1><<<dim3(gwide.x + extra, d.C), kBlock, w_lds, st>>>(d, k, 0, w_nrt, w_Kp, w_S, 3, 0);
             }
         }
@@ -3890,48 +3574,42 @@ int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
     }
     // enough workgroups that instruction issue, not latency, bounds the step (measured crossover: between four and six
     // 256-slot workgroups per CU): two slots per thread, three Threefry calls instead of six
-    const bool two_slot = !d.wide && s->items == 1 && !s->generic_prop && d.N % (2 * kBlock) == 0 &&
+    const bool two_slot = !d.wide && s->items == 1 && d.N % (2 * kBlock) == 0 &&
                           (s->two_slot_prop == 1 || (s->two_slot_prop < 0 && (int64_t)nb * d.C >= 5 * 256));
     // N a power of two: the searches walk the summation tree, no cdf launch (k_lg_prop1t)
-    const bool tree = s->tree_step && d.trW && !s->generic_prop;
+    const bool tree = s->tree_step && d.trW;
     // Large wide ensembles (the fat drift kernel): the step's noise is drawn by extra blocks of the three small launches in front
     // of the drift kernel -- norm, cdf and the ancestor search need a few dozen workgroups each and leave the chip empty --
-    // instead of a launch of its own (k_lgw_noise: ~10 us per step at 10 000 particles).  FBSMI_WIDE_NOISE_FOLD=0: the own launch.
+    // instead of a launch of its own (~10 us per step at 10 000 particles).
     // The fat kernel (one workgroup per slot tile walks all row tiles: the gather once per slot tile, noise by the small
     // launches, row sums in its tail, no k_lgw_lse) from ~700 tiled workgroups per launch: d = 100, 4 chains in two groups:
-    // 2000 particles 8.6 against 9.3 ms per sweep, 4000: 9.2 against 11.4; 1000: 8.4 against 7.8 (FBSMI_FAT_MIN moves it).
-    static const int fat_min = [] { const char* e = getenv("FBSMI_FAT_MIN"); return e ? atoi(e) : 700; }();
-    const bool fat = d.wide && (int64_t)gwide.x * d.C > fat_min;
-    static const int noise_fold = [] { const char* e = getenv("FBSMI_WIDE_NOISE_FOLD"); return e ? atoi(e) : 1; }();
-    const bool fold = fat && noise_fold && s->items == 1 && (s->debug_mask & 7) == 7;
+    // 2000 particles 8.6 against 9.3 ms per sweep, 4000: 9.2 against 11.4; 1000: 8.4 against 7.8.
+    constexpr int64_t kFatMin = 700;
+    const bool fat = d.wide && (int64_t)gwide.x * d.C > kFatMin;
     LgDev dz = d;
     dim3 gz = gtile;
-    if (fold) {
+    if (fat) {
         const int64_t third = (((int64_t)d.N * d.du + 1) / 2 + 2) / 3;
         const int64_t want = (third + kBlock - 1) / kBlock;
         dz.nz = (int)(want < 1024 ? want : 1024);
         gz = dim3(gtile.x + dz.nz, gtile.y);
     }
     for (int k = 0; !one_tile && k < d.T; ++k) {
-        if (s->debug_mask & 1) {
+        {
             ProfScope p(s, 0, st);
             if (tree) k_lg_norm<1, 0, true><<<dim3(gtile.x * (d.pin ? 8 : 1), d.C), kBlock, 0, st>>>(d, k);
             else LG_DISPATCH(s, (void)DMAX; (k_lg_norm<ITEMS, 0><<<gz, kBlock, 0, st>>>(dz, k)));
         }
-        if ((s->debug_mask & 2) && !tree) {
+        if (!tree) {
             ProfScope p(s, 1, st);
             LG_DISPATCH(s, (void)DMAX; (k_lg_cdf<ITEMS, 0><<<gz, kBlock, 0, st>>>(dz, k)));
         }
-        if (s->debug_mask & 4) {
+        {
             ProfScope p(s, 2, st);
             if (d.wide) {
                 k_lgw_anc<<<gz, kBlock, 0, st>>>(dz, k);
                 bool fat_rowsum = false;
                 if (fat) {
-                    const int64_t pairs = ((int64_t)d.N * d.du + 1) / 2;
-                    if (!fold)
-                        k_lgw_noise<<<dim3((unsigned)((pairs + kBlock - 1) / kBlock < 4096 ? (pairs + kBlock - 1) / kBlock : 4096), d.C),
-                                      kBlock, 0, st>>>(d, k);
                     const int nst = (d.N + kWideTile - 1) / kWideTile;
                     fat_rowsum = (d.D & 3) == 0 && (d.du & 3) == 0;   // the float4 kernel leaves the log-weights in d.lw
                     if (fat_rowsum)
@@ -3957,16 +3635,12 @@ int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
                 LG_DISPATCH(s, (void)ITEMS; (k_lg_prop1t<DMAX, 1><<<dim3(gtile.x * (d.pin ? 8 : 1), d.C), kBlock, 0, st>>>(d, k)));
             } else if (two_slot) {
                 LG_DISPATCH(s, (void)ITEMS; (k_lg_prop2<DMAX><<<dim3(nb / 2, d.C), kBlock, 0, st>>>(d, k)));
-            } else if (s->items == 1 && !s->generic_prop) {
+            } else if (s->items == 1) {
                 LG_DISPATCH(s, (void)ITEMS; (k_lg_prop1<DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
-            } else if (s->items > 1 && !s->generic_prop) {
+            } else {
                 // several slots per thread: compact heaps by their own small launch, then the batched kernel
                 k_lg_heaps<<<dim3(kHeapSizeW / kBlock, d.C), kBlock, 0, st>>>(d);
-                static const int queue = [] { const char* e = getenv("FBSMI_BIGN_QUEUE"); return e ? atoi(e) : 1; }();
-                if (queue) LG_DISPATCH(s, (k_lg_propQ<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
-                else LG_DISPATCH(s, (k_lg_propN<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
-            } else {
-                LG_DISPATCH(s, (k_lg_prop<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
+                LG_DISPATCH(s, (k_lg_propQ<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
             }
         }
     }
@@ -4084,12 +3758,7 @@ int fbsmi_lg_sweep_create(const fbsmi_lg_model* m, int32_t nparticles, int expli
     d.levels = bisect_levels(d.N);
     d.wide = wide ? 1 : 0;
     d.lpw = nullptr;
-    if (const char* dm = getenv("FBSMI_DEBUG_STEP_MASK")) s->debug_mask = atoi(dm);
-    if (const char* gp = getenv("FBSMI_GENERIC_PROP")) s->generic_prop = atoi(gp) != 0;
-    if (const char* sl = getenv("FBSMI_STEP_LAUNCHES")) s->step_launches = atoi(sl) != 0;
-    if (const char* sp = getenv("FBSMI_TWO_SLOT_PROP")) s->two_slot_prop = atoi(sp) != 0 ? 1 : 0;
-    if (const char* tp = getenv("FBSMI_TREE_STEP")) s->tree_step = atoi(tp) != 0;
-    if (const char* th = getenv("FBSMI_TREE_HALVES")) s->tree_halves = atoi(th) == 1 ? 1 : (atoi(th) == 4 ? 4 : 2);
+    read_switches(s);
     s->items = fbsmi_tile_items(d.N);  // one workgroup = one tile of the two-level logsumexp (include/fbsmi_math.h)
     const int maxd = m->du > m->dv ? m->du : m->dv;
     s->dmax = maxd <= 1 ? 1 : (maxd <= 2 ? 2 : (maxd <= 4 ? 4 : 16));   // du = dv = 1 (BASELINE configs 1, 2) has its own instantiation
@@ -4136,8 +3805,7 @@ int fbsmi_lg_sweep_create(const fbsmi_lg_model* m, int32_t nparticles, int expli
         rc |= slab_request(s, &d.lpw, C * (size_t)((d.dv + 3) & ~3) * N);
         rc |= slab_request(s, &d.anc, C * N);
         rc |= slab_request(s, &d.xiw, 2 * C * N * d.du);
-        static const int upre = [] { const char* e = getenv("FBSMI_WIDE_UPRE"); return e ? atoi(e) : 1; }();
-        if (upre && N <= kBlock) rc |= slab_request(s, &d.uw, 4 * C * (size_t)N);
+        if (N <= kBlock) rc |= slab_request(s, &d.uw, 4 * C * (size_t)N);
     }
     d.hpW = d.hpJ = nullptr;
     d.hp_map = nullptr;
@@ -4157,8 +3825,7 @@ int fbsmi_lg_sweep_create(const fbsmi_lg_model* m, int32_t nparticles, int expli
     const bool pow2 = (d.N & (d.N - 1)) == 0 && d.nb >= 2 && d.nb <= kBlock;
     // N = 2^k + 1 (explicit_final on a power-of-two ensemble): the same step over the first 2^k slots' tree plus an extra
     // one-slot tile (tree_build)
-    const bool pow2p1 = d.N > 2 && ((d.N - 1) & (d.N - 2)) == 0 && d.nb - 1 >= 2 && d.nb - 1 <= kBlock &&
-                        !(getenv("FBSMI_TREE_PLUS1") && atoi(getenv("FBSMI_TREE_PLUS1")) == 0);
+    const bool pow2p1 = d.N > 2 && ((d.N - 1) & (d.N - 2)) == 0 && d.nb - 1 >= 2 && d.nb - 1 <= kBlock && s->tree_plus1;
     d.plus1 = 0;
     if (s->items == 1 && !wide && (pow2 || pow2p1)) {
         d.plus1 = pow2 ? 0 : 1;
@@ -4167,11 +3834,8 @@ int fbsmi_lg_sweep_create(const fbsmi_lg_model* m, int32_t nparticles, int expli
         rc |= slab_request(s, &d.wfirst, C * (size_t)d.nb);
         // few workgroups per launch (BASELINE config 1: 4 tiles; up to 64 workgroups): keep the step on one XCD.  Only with the default kernel
         // choices (one tile per workgroup, one slot per thread), which is what such sizes get.  FBSMI_PIN=0 turns it off.
-        const char* pe = getenv("FBSMI_PIN");
-        const char* pm = getenv("FBSMI_PIN_MAX");   // (diagnostic: workgroups per launch up to which the step is pinned)
-        const int64_t pin_max = pm ? atoi(pm) : 64;   // two workgroups per CU of the XCD: measured better up to there, worse beyond
-        d.pin = (!d.plus1 && s->tree_step && !s->generic_prop && s->tree_halves < 0 && s->two_slot_prop < 0 && (int64_t)d.nb * C <= pin_max &&
-                 (int64_t)d.nb * C < 2 * 256 && !(pe && atoi(pe) == 0)) ? 1 : 0;
+        constexpr int64_t kPinMax = 64;   // workgroups per launch; two per CU of the XCD: measured better up to there, worse beyond
+        d.pin = (s->pin && !d.plus1 && s->tree_step && s->tree_halves < 0 && s->two_slot_prop < 0 && (int64_t)d.nb * C <= kPinMax) ? 1 : 0;
         if (d.pin && !xcd_round_robin_holds()) d.pin = 0;   // the dispatch order the pinning rests on is not what this machine does
     }
     rc |= slab_request(s, &d.bsumw, C * d.nb);
@@ -4184,7 +3848,6 @@ int fbsmi_lg_sweep_create(const fbsmi_lg_model* m, int32_t nparticles, int expli
     rc |= slab_request(s, &d.acc, C * (T + 1));
     rc |= slab_request(s, &d.x0s_slot, 1);
     rc |= slab_request(s, &d.counter, 1);
-    rc |= slab_request(s, &d.dbg, 64);
     if (store_path) {
         rc |= slab_request(s, &d.As, C * T * N);
         rc |= slab_request(s, &d.uss, C * (T + 1) * N * d.du);
@@ -4405,9 +4068,6 @@ int fbsmi_lg_sweep_view(fbsmi_lg_sweep* s, int which, void* dst, int64_t* count,
         case 4: src = d.lwss; n = (int64_t)d.C * (d.T + 1) * d.N; break;
         case 5: src = d.us_star; n = (int64_t)d.C * (d.T + 1) * d.du; break;
         case 6: src = d.vs; n = (int64_t)d.C * (d.T + 1) * d.dv; break;
-        case 7: src = d.dbg; n = 128; break;  // 64 x uint64 as 32-bit words (diagnostic build)
-        case 8: src = d.cdfJ; n = (int64_t)d.C * d.N; break;   // (diagnostic build: per-workgroup entry / exit stamps of the last step)
-        case 9: src = d.xiw ? d.xiw + (size_t)d.N * d.du : nullptr; n = 16384; break;   // (diagnostic build: the drift kernel's workgroups)
         default: return fail(FBSMI_ERR_ARG, "lg_sweep_view: unknown view");
     }
     if (!src) n = 0;
@@ -4434,7 +4094,7 @@ int enqueue_filter(fbsmi_lg_filter* f, hipStream_t st) {
     const LgDev& d = s->d;
     const dim3 gone(1, d.C), gtile(d.nb, d.C);
     k_filt_keys<<<gone, kBlock, 0, st>>>(d);
-    if (!d.wide && d.N <= kBlock && !s->step_launches) {
+    if (!d.wide && d.N <= kBlock) {
         LG_DISPATCH(s, (void)ITEMS; (k_filt_sweep1<DMAX><<<gone, kBlock, 0, st>>>(d, f->u0s)));
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
@@ -4479,8 +4139,7 @@ int enqueue_filter(fbsmi_lg_filter* f, hipStream_t st) {
             return FBSMI_OK;
         }
         // one-tile ensembles: a step's launches are a few dozen workgroups -- pinned to one XCD (bit 8 of `emit`, grids 8x wide)
-        static const int pin_on = [] { const char* e = getenv("FBSMI_WIDE_PIN"); return (e ? atoi(e) : 1) && xcd_round_robin_holds(); }();
-        const bool pinw = pin_on && d.C == 1 && nst * nrt <= 32;
+        const bool pinw = s->wide_pin && xcd_round_robin_holds() && d.C == 1 && nst * nrt <= 32;
         const int pe = pinw ? 0x100 : 0, pg = pinw ? 8 : 1;
         if (d.flow == 0) {
             for (int k = 0; k < d.T; ++k) {

@@ -221,9 +221,8 @@ int fbsmi_lg_sweep_set_em_forward(fbsmi_lg_sweep* s, const fbsmi_em_forward* f);
 /* Parity views of the last sweep: copies view `which` into dst (device, nullable) and reports its
  * element count.  which: 0 final particles (n,du) row-major, 1 final normalised log-weights (n),
  * 2 As (T,n) int32, 3 uss (T+1,n,du), 4 log_wss (T+1,n) [2-4 only with store_path],
- * 5 us_star (T+1,du) and 6 vs (T+1,dv) of the sweep; each with a leading [nchains] axis;
- * 7 = 128 32-bit words of in-kernel clock stamps (only written by the -DFBSMI_STAMPS diagnostic build).
- * n = nparticles (+1 if explicit_final). */
+ * 5 us_star (T+1,du) and 6 vs (T+1,dv) of the sweep; each with a leading [nchains] axis; any other
+ * `which` is FBSMI_ERR_ARG.  n = nparticles (+1 if explicit_final). */
 int fbsmi_lg_sweep_view(fbsmi_lg_sweep* s, int which, void* dst, int64_t* count, void* stream);
 /* Fused particle filters for the analytic model, stratified (resampling = 0) or systematic (1)
  * resampling (fbs/samplers/resampling.py:43-59):

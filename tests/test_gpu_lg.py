@@ -528,14 +528,13 @@ def test_two_slot_prop_kernel_matches_oracle(tree, oracle, dev, monkeypatch):
                 _eq(_np(got[i][c] if C > 1 else got[i]), want[i], f"N={N} chain {c} {what}")
 
 
-@pytest.mark.parametrize("variant", ["queue", "generic"])
+@pytest.mark.parametrize("variant", ["queue"])
 @pytest.mark.parametrize("toy,N,T,C,eb", [(toy_2d, 200000, 5, 2, True), (toy_4d, 300001, 4, 1, False), (toy_2d, 1100000, 3, 1, True),
                                          (toy_31, 1048576 + 4096, 2, 1, True), (toy_2d, 1100003, 2, 2, True)])
-def test_several_slots_per_thread_kernels(variant, toy, N, T, C, eb, oracle, dev, monkeypatch):
+def test_several_slots_per_thread_kernels(variant, toy, N, T, C, eb, oracle, dev):
     """N > 131072: tiles of 1024 / 4096 slots (ITEMS = 4 / 16).  k_lg_heaps + k_lg_propQ (lane-major slots, kill tests first,
-    the killed sources' searches compacted through an LDS queue, compact heaps) and the one-slot-after-the-other kernel it
-    replaced (FBSMI_GENERIC_PROP=1): ragged last tiles, the stored path, several chains, du = 3.  Bit-exact."""
-    monkeypatch.setenv("FBSMI_GENERIC_PROP", "1" if variant == "generic" else "0")
+    the killed sources' searches compacted through an LDS queue, compact heaps): ragged last tiles, the stored path, several
+    chains, du = 3.  Bit-exact."""
     toy_ = toy()
     ts = np.linspace(0, 1.0, T + 1)
     br = _bridge(toy_, ts, dev)
@@ -557,6 +556,46 @@ def test_several_slots_per_thread_kernels(variant, toy, N, T, C, eb, oracle, dev
         _eq(_np(v["lw_T"][c] if C > 1 else v["lw_T"]), want[5], f"log-weights chain {c}")
     del sweep
     br._sweeps.clear()
+
+
+def test_sweep_handles_created_from_several_threads(oracle, dev):
+    """Four threads create narrow sweep handles at once (ctypes releases the GIL during the call, so the creations -- and the
+    shared launch-stream pool they draw from -- overlap); every handle's sweep is then bit-exact."""
+    import threading
+    toy_ = toy_4d()
+    T = 6
+    ts = np.linspace(0, 1.0, T + 1)
+    sizes = (100, 777, 4096, 200000)   # one tile, several tiles, the two-launch step, four slots per thread
+    brs = [_bridge(toy_, ts, dev) for _ in sizes]
+    handles, errors = [None] * len(sizes), []
+    start = threading.Barrier(len(sizes))
+
+    def create(i):
+        try:
+            start.wait()
+            handles[i] = brs[i].sweep_handle(sizes[i], True, False)
+        except Exception as e:   # surfaced below, on the main thread
+            errors.append(e)
+
+    threads = [threading.Thread(target=create, args=(i,)) for i in range(len(sizes))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    for i, N in enumerate(sizes):
+        om = oracle_model_from(oracle, brs[i])
+        rng = np.random.default_rng(N)
+        x0 = rng.normal(size=brs[i].du).astype(np.float32)
+        bs = rng.integers(0, N, T + 1).astype(np.int32)
+        key = oracle.split(oracle.PRNGKey(7 + i), 2)[1]
+        want = oracle.gibbs_kernel_lg(om, key, x0, toy_["y0"], bs, N, True, False, debug=True)
+        got = handles[i].sweep(key, x0, toy_["y0"], bs)
+        v = handles[i].views()
+        _eq(_np(v["us_T"]), want[4], f"N={N} final particles")
+        _eq(_np(v["lw_T"]), want[5], f"N={N} final log-weights")
+        for j, what in enumerate(("x0_next", "us_star_next", "bs_star_next", "acc")):
+            _eq(_np(got[j]), want[j], f"N={N} {what}")
 
 
 def test_toy_sb_gibbs_driver(tmp_path, dev):

@@ -14,7 +14,7 @@ f=glob.glob('gpurun_out/q_valu/**/*counter_collection.csv',recursive=True)[0]
 acc=collections.defaultdict(lambda: collections.defaultdict(float)); n=collections.Counter()
 for r in csv.DictReader(open(f)):
     k=r['Kernel_Name'][:50]
-    if 'k_lg_norm' in k or 'k_lg_prop' in k or 'k_lg_cdf' in k:
+    if 'k_lg_norm' in k or 'k_lg_cdf' in k or any(p in k for p in ('k_lg_prop1', 'k_lg_prop2', 'k_lg_propQ')):
         acc[k][r['Counter_Name']]+=float(r['Counter_Value'])
 for k,v in acc.items():
     w=v['SQ_WAVES']

@@ -23,6 +23,11 @@ def one(pattern):
     return sorted(hits)[-1]
 
 
+def is_prop(kernel):
+    """The Euler-step kernels: k_lg_prop1, _prop1t, _prop2, _prop2t, _propQ."""
+    return any(p in kernel for p in ("k_lg_prop1", "k_lg_prop2", "k_lg_propQ"))
+
+
 def pmc_avgs(path, counter):
     acc = defaultdict(lambda: [0.0, 0])
     for row in csv.DictReader(open(path)):
@@ -90,7 +95,7 @@ def main():
                 wv = cols["SQ_WAVES"][k][0]
                 per = [cols[n].get(k, (0, 0))[0] / wv if wv else 0.0 for n in names[:-1]]
                 w.writerow([k, wv] + per + [cols["SQ_WAVES"][k][1]])
-                if "k_lg_prop" in k or "<1, 0>" in k or "<1, 0, " in k:   # the step kernels (MODE 0)
+                if is_prop(k) or "<1, 0>" in k or "<1, 0, " in k:   # the step kernels (MODE 0)
                     valu_json[k] = {"waves_per_launch": wv, "valu_per_wave": per[0], "salu_per_wave": per[1],
                                     "launches": cols["SQ_WAVES"][k][1]}
     except SystemExit:
@@ -115,9 +120,9 @@ def main():
     except (SystemExit, ValueError):
         pass
     cfg = bench["config"]
-    prop = [k for k in fetch if "k_lg_prop" in k]
+    prop = [k for k in fetch if is_prop(k)]
     if not prop:
-        raise SystemExit("no k_lg_prop kernel in the PMC pass")
+        raise SystemExit("no Euler-step kernel (k_lg_prop1 / 2 / Q) in the PMC pass")
     k = max(prop, key=lambda n: fetch[n][1])
     fkb, wkb = fetch[k][0], write.get(k, (0.0, 0))[0]
     f4 = calib["4_bytes_per_lane"]["true_over_reported"] if calib and "4_bytes_per_lane" in calib else None
@@ -139,7 +144,7 @@ def main():
                 "WRITE_SIZE.  The counters sit on the memory side of the XCD L2s (Infinity-Cache hits included).",
     }
     if valu_json:
-        pk = [kk for kk in valu_json if "k_lg_prop" in kk]
+        pk = [kk for kk in valu_json if is_prop(kk)]
         if pk:
             top = max(pk, key=lambda kk: valu_json[kk]["launches"])
             traffic["k_lg_prop_valu_insts_per_launch"] = valu_json[top]["valu_per_wave"] * valu_json[top]["waves_per_launch"]
