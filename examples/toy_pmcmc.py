@@ -3,7 +3,8 @@
 Counterpart of the reference driver experiments/toy/gp_pmcmc.py (same flags, key schedule and .npz schema:
 samples (nchains, nsamples, d), gp_mean, gp_cov).  Every MCMC iteration of a chain is one
 pmcmc_filter_step; with the analytic score it is one hipGraph replay (for d > 16: drift on the f32 matrix
-cores).  The reference vmaps the chains; here they are iterated."""
+cores).  The reference vmaps the chains; here they are iterated, unless --fused is given: then the whole loop runs on
+the device for all chains at once (fbs_amd.samplers.pmcmc_chain), with the same key schedule."""
 import argparse
 import os
 
@@ -13,13 +14,14 @@ import torch
 from _gp_toy import add_common_args, gp_setting
 from fbs_amd import ops
 from fbs_amd.samplers import bootstrap_filter, stratified
-from fbs_amd.samplers.smc import pmcmc_kernel
+from fbs_amd.samplers.smc import pmcmc_chain, pmcmc_kernel
 
 
 def main(argv=None):
     parser = add_common_args(argparse.ArgumentParser())
     parser.add_argument('--delta', type=float, default=None, help='The pCN step size (None: independent proposals).')
     parser.add_argument('--nchains', type=int, default=4, help='The number of MCMC chains.')
+    parser.add_argument('--fused', action='store_true', help='Run the MCMC loop on the device, all chains per launch.')
     args = parser.parse_args(argv)
     dev = torch.device('cuda:0')
     g = gp_setting(args, dev)
@@ -37,7 +39,14 @@ def main(argv=None):
     state = [pmcmc_init(k) for k in ops.split(subkey, nchains)]
     samples = torch.empty((nchains, nsamples, g['d']), device=dev)
     accs = np.zeros(nsamples)
-    for i in range(nsamples):                                                       # gp_pmcmc.py:170-179
+    if args.fused:                                                                  # gp_pmcmc.py:170-179 on the device
+        out = pmcmc_chain(key, torch.stack([s[0] for s in state]), torch.stack([s[1].reshape(()) for s in state]),
+                          torch.stack([s[2] for s in state]), y0, ts, br.fwd_ys_sampler, g['sde'], br.ref_sampler,
+                          br.transition_sampler, br.likelihood_logpdf, stratified, args.nparticles, nsamples,
+                          delta=args.delta)
+        samples = out[4].permute(1, 0, 2)
+        accs = out[5].acceptance_prob[:, 0].cpu().numpy().astype(np.float64)
+    for i in range(0 if args.fused else nsamples):                                  # gp_pmcmc.py:170-179
         key, subkey = ops.split(key)
         for c, kc in enumerate(ops.split(subkey, nchains)):
             x0, log_ell, ys, mcmc_state = pmcmc_kernel(kc, *state[c], y0, ts, br.fwd_ys_sampler, g['sde'], br.ref_sampler,

@@ -141,6 +141,12 @@ class EMForwardStruct(C.Structure):
     _fields_ = [("nsub", C.c_int32), ("M", C.c_void_p), ("c", C.c_void_p), ("ddt", C.c_void_p), ("s", C.c_void_p)]
 
 
+class LGPmcmcTablesStruct(C.Structure):
+    _fields_ = [("m_u", C.c_void_p), ("m_v", C.c_void_p), ("gain", C.c_void_p), ("chol", C.c_void_p),
+                ("mean_coef", C.c_void_p), ("c0", C.c_float), ("beta", C.c_float), ("one_minus_beta", C.c_float),
+                ("c1", C.c_float), ("use_pcn", C.c_int32), ("which_u", C.c_int32)]
+
+
 class EMMaskStruct(C.Structure):
     _fields_ = [("du", C.c_int32), ("dv", C.c_int32), ("u_off", C.c_void_p), ("v_off", C.c_void_p),
                 ("role", C.c_void_p)]
@@ -191,6 +197,11 @@ SIGNATURES = {
     "fbsmi_lg_filter_create": (C.c_int, [C.POINTER(LGModelStruct), _i32, C.c_int, C.c_int, C.c_int, _i32, C.POINTER(_vp)]),
     "fbsmi_lg_filter_destroy": (None, [_vp]),
     "fbsmi_lg_filter_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "fbsmi_lg_pmcmc_create": (C.c_int, [C.POINTER(LGModelStruct), C.POINTER(LGPmcmcTablesStruct), _i32, C.c_int, _i32,
+                                        C.POINTER(_vp)]),
+    "fbsmi_lg_pmcmc_destroy": (None, [_vp]),
+    "fbsmi_lg_pmcmc_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "fbsmi_lg_pmcmc_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fbsmi_lg_sweep_profile": (C.c_int, [_vp, C.c_int]),
     "fbsmi_lg_sweep_kernel_us": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "fbsmi_em_concat": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),

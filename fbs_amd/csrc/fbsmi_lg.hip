@@ -3327,6 +3327,196 @@ __global__ void k_lg_advance_key(LgDev d) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// particle-marginal Metropolis-Hastings (fbs/samplers/smc.py:171-258) round the flow-1 filter:
+//   k_pm_propose -> k_pm_u0 -> [enqueue_filter] -> k_pm_accept, the chain on blockIdx.y
+// ------------------------------------------------------------------------------------------
+struct PmDev {
+    int C, N, du, dv, T;
+    int use_pcn, which_u;
+    float c0, beta, omb, c1;              // float32(sqrt(delta/2)), float32(beta), float32(1-beta), float32(sqrt(1-beta))
+    const double *m_u, *m_v, *gain;       // (du), (dv), (du, dv)
+    const float *chol, *coef;             // (du, du) lower factor; (T+1) mean coefficients (pCN)
+    const float *F, *sqQ;                 // the model's forward transition
+    // the filter's buffers this engine feeds and reads
+    uint32_t* fkeys;                      // [C][2]        key_filter, where k_filt_keys reads it
+    float* vs;                            // [C][T+1][dv]  reversed proposal path
+    float* u0s;                           // [C][N][du]    initial particles (staging buffer of the filter)
+    const float* usT;                     // [C][N][du]    final particles
+    const float* ell;                     // [C]           prop_log_ell
+    // the engine's own
+    uint32_t* key;                        // [2]     carried key of the chain driver
+    uint32_t* ikeys;                      // [C][2]  explicit iteration keys (fbsmi_lg_pmcmc_step)
+    uint32_t* pk;                         // [C][4]  key_u0, key_mh of the iteration
+    float* y0;                            // [dv]
+    float* xi;                            // [C][2][T][dv] noise of the forward path(s)
+    float* mcond;                         // [C][du] m_ of ref_sampler
+    float *uT, *log_ell, *ys;             // state: [C][du], [C], [C][T+1][dv]
+    float* prop_ys;                       // [C][T+1][dv]
+    int32_t* counter;                     // iterations done in this chain call
+    void** out;                           // [5] device slots: samples, acceptance_prob, is_accepted, prop_log_ell, log_ell
+};
+
+constexpr int kPmBlock = 512;
+constexpr int kPmChunk = 8;      // steps of the path recurrence whose operands are fetched together
+constexpr int kPmTile = 4096;    // normals of k_pm_u0 staged in LDS per workgroup
+
+// keys (smc.py:231,163; gp_pmcmc.py:171-172), forward path(s) with their noise drawn here (linear.py:211-221, the
+// recurrence of k_lg_path), pCN combination (smc.py:161-168), time reversal into the filter's vs (smc.py:239), and the
+// conditional mean of ref_sampler (gp_pmcmc.py:131) in float64 as include/fbsmi.h specifies it.
+__global__ void __launch_bounds__(kPmBlock) k_pm_propose(PmDev p, int chain) {
+    const int c = blockIdx.y;
+    __shared__ uint32_t sk[4];
+    __shared__ float syT[128];
+    if (threadIdx.x == 0) {
+        uint32_t k0, k1;
+        if (chain) {
+            uint32_t b0, b1;
+            split_at(p.key[0], p.key[1], 2, 1, b0, b1);      // key, subkey = split(key)  (k_pm_u0 advances key)
+            split_at(b0, b1, p.C, c, k0, k1);                // split(subkey, C)[c], C = 1 included
+        } else {
+            k0 = p.ikeys[2 * c];
+            k1 = p.ikeys[2 * c + 1];
+        }
+        uint32_t q0, q1;
+        split_at(k0, k1, 4, 0, q0, q1);                                  // key_prop
+        split_at(k0, k1, 4, 1, p.pk[4 * c], p.pk[4 * c + 1]);            // key_u0
+        split_at(k0, k1, 4, 2, p.fkeys[2 * c], p.fkeys[2 * c + 1]);      // key_filter
+        split_at(k0, k1, 4, 3, p.pk[4 * c + 2], p.pk[4 * c + 3]);        // key_mh
+        if (p.use_pcn) {
+            split_at(q0, q1, 2, 0, sk[0], sk[1]);
+            split_at(q0, q1, 2, 1, sk[2], sk[3]);
+        } else {
+            sk[0] = q0; sk[1] = q1; sk[2] = 0; sk[3] = 0;
+        }
+    }
+    __syncthreads();
+    const int T = p.T, dv = p.dv;
+    const uint64_t n = (uint64_t)T * dv;
+    float* xi0 = p.xi + (size_t)c * 2 * n;
+    float* xi1 = xi0 + n;
+    for (uint64_t i = threadIdx.x; i < n; i += kPmBlock) {               // normal(key, (T, dv)), linear.py:220
+        xi0[i] = normal_at(sk[0], sk[1], n, i);
+        if (p.use_pcn) xi1[i] = normal_at(sk[2], sk[3], n, i);
+    }
+    __syncthreads();
+    const int j = threadIdx.x;
+    if (j < dv) {
+        const size_t T1 = (size_t)T + 1;
+        const float* ys = p.ys + (size_t)c * T1 * dv;
+        float* prop = p.prop_ys + (size_t)c * T1 * dv;
+        float* vs = p.vs + (size_t)c * T1 * dv;
+        const float y0 = p.y0[j];
+        float r0 = y0, r1 = y0;
+        auto emit = [&](int k, float x_old, float coef) {
+            float out = r0;
+            if (p.use_pcn) {                                             // smc.py:167-168, separately rounded
+                const float mean = coef * y0;
+                const float q = x_old + p.c0 * (r0 - mean);
+                out = (p.beta * q + p.omb * mean) + p.c1 * (r1 - mean);
+            }
+            prop[(size_t)k * dv + j] = out;
+            vs[(size_t)(T - k) * dv + j] = out;
+            return out;
+        };
+        float last = emit(0, p.use_pcn ? ys[j] : 0.0f, p.use_pcn ? p.coef[0] : 0.0f);
+        for (int k0 = 0; k0 < T; k0 += kPmChunk) {
+            float f[kPmChunk], sq[kPmChunk], z0[kPmChunk], z1[kPmChunk], xo[kPmChunk], cf[kPmChunk];
+#pragma unroll
+            for (int i = 0; i < kPmChunk; ++i) {
+                const int k = k0 + i < T ? k0 + i : T - 1;
+                f[i] = p.F[k];
+                sq[i] = p.sqQ[k];
+                z0[i] = xi0[(size_t)k * dv + j];
+                z1[i] = p.use_pcn ? xi1[(size_t)k * dv + j] : 0.0f;
+                xo[i] = p.use_pcn ? ys[(size_t)(k + 1) * dv + j] : 0.0f;
+                cf[i] = p.use_pcn ? p.coef[k + 1] : 0.0f;
+            }
+#pragma unroll
+            for (int i = 0; i < kPmChunk; ++i) {
+                if (k0 + i < T) {
+                    r0 = f[i] * r0 + sq[i] * z0[i];
+                    r1 = f[i] * r1 + sq[i] * z1[i];
+                    last = emit(k0 + i + 1, xo[i], cf[i]);
+                }
+            }
+        }
+        syT[j] = last;                                                   // yT = vs[0]
+    }
+    __syncthreads();
+    if (j < p.du) {
+        double s = 0.0;
+        for (int cc = 0; cc < dv; ++cc) s = s + p.gain[(size_t)j * dv + cc] * ((double)syT[cc] - p.m_v[cc]);
+        p.mcond[(size_t)c * p.du + j] = (float)(p.m_u[j] + s);
+    }
+}
+
+// ref_sampler (gp_pmcmc.py:130-133): u0 = m_ + normal(key_u0, (n, du)) @ chol, `rows` particles per workgroup, written
+// into the filter's staging buffer.  In a chain call block (0, 0) also advances the carried key and the counter: this is
+// the one launch of the iteration that reads neither.
+__global__ void __launch_bounds__(kBlock) k_pm_u0(PmDev p, int rows, int chain) {
+    const int c = blockIdx.y;
+    __shared__ float zs[kPmTile];
+    const int du = p.du;
+    const int row0 = blockIdx.x * rows;
+    const int nr = p.N - row0 < rows ? p.N - row0 : rows;
+    const uint32_t k0 = p.pk[4 * c], k1 = p.pk[4 * c + 1];
+    const uint64_t n = (uint64_t)p.N * du;
+    for (int e = threadIdx.x; e < nr * du; e += kBlock) zs[e] = normal_at(k0, k1, n, (uint64_t)row0 * du + e);
+    __syncthreads();
+    const float* m = p.mcond + (size_t)c * du;
+    float* u0s = p.u0s + ((size_t)c * p.N + row0) * du;
+    for (int e = threadIdx.x; e < nr * du; e += kBlock) {
+        const int i = e / du, j = e - i * du;
+        const float* z = zs + i * du;
+        float acc = z[0] * p.chol[j];
+        for (int cc = 1; cc < du; ++cc) acc = acc + z[cc] * p.chol[(size_t)cc * du + j];
+        u0s[e] = m[j] + acc;
+    }
+    if (chain && blockIdx.x == 0 && c == 0 && threadIdx.x == 0) {
+        uint32_t a0, a1;
+        split_at(p.key[0], p.key[1], 2, 0, a0, a1);
+        p.key[0] = a0;
+        p.key[1] = a1;
+        *p.counter = *p.counter + 1;
+    }
+}
+
+// Metropolis-Hastings decision (smc.py:244-258): the chain's state is replaced by the proposal on acceptance, and the
+// iteration's sample and MCMCState fields (fbs/samplers/common.py) are recorded at row `counter - 1` (chain) / 0 (step).
+__global__ void __launch_bounds__(kBlock) k_pm_accept(PmDev p, int chain) {
+    const int c = blockIdx.y;
+    const int it = chain ? *p.counter - 1 : 0;
+    const float prop_ell = p.ell[c], old_ell = p.log_ell[c];
+    const float diff = prop_ell - old_ell;
+    const float log_acc = (diff < 0.0f || diff != diff) ? diff : 0.0f;   // minimum(0, .), NaN kept      :246
+    const float z = uniform_at(p.pk[4 * c + 2], p.pk[4 * c + 3], 1, 0);                              // :248
+    const bool acc = fbsmi_logf(z) < log_acc;                                                        // :249
+    __syncthreads();   // every thread has read the state's log_ell before thread 0 replaces it
+    float* samples = (float*)p.out[0];
+    float* uT = p.uT + (size_t)c * p.du;
+    const float* new_uT = p.usT + ((size_t)c * p.N + p.which_u) * p.du;
+    for (int r = threadIdx.x; r < p.du; r += kBlock) {
+        const float x = acc ? new_uT[r] : uT[r];
+        uT[r] = x;
+        if (samples) samples[((size_t)it * p.C + c) * p.du + r] = x;
+    }
+    if (acc) {
+        const size_t nys = ((size_t)p.T + 1) * p.dv;
+        float* ys = p.ys + (size_t)c * nys;
+        const float* prop = p.prop_ys + (size_t)c * nys;
+        for (size_t e = threadIdx.x; e < nys; e += kBlock) ys[e] = prop[e];
+    }
+    if (threadIdx.x == 0) {
+        if (acc) p.log_ell[c] = prop_ell;
+        const size_t o = (size_t)it * p.C + c;
+        if (p.out[1]) ((float*)p.out[1])[o] = fbsmi_expf(log_acc);
+        if (p.out[2]) ((uint8_t*)p.out[2])[o] = acc ? 1 : 0;
+        if (p.out[3]) ((float*)p.out[3])[o] = prop_ell;
+        if (p.out[4]) ((float*)p.out[4])[o] = old_ell;
+    }
+}
+
 }  // namespace fbsmi
 
 using namespace fbsmi;
@@ -4285,6 +4475,190 @@ int fbsmi_lg_sweep_kernel_us(fbsmi_lg_sweep* s, int which, double* avg_us, int64
     if (avg_us) *avg_us = s->prof_n[which] ? s->prof_us[which] / (double)s->prof_n[which] : 0.0;
     if (launches) *launches = s->prof_n[which];
     return FBSMI_OK;
+}
+
+// ---- fused particle-marginal Metropolis-Hastings ---------------------------------------------
+struct fbsmi_lg_pmcmc {
+    fbsmi_lg_filter* filt = nullptr;   // flow 1, nchains = C: buffers, stream, events
+    PmDev p{};
+    void* slab = nullptr;
+    int rows = 1;                      // particles per workgroup of k_pm_u0
+    hipGraphExec_t graph_step = nullptr, graph_chain = nullptr;
+};
+
+namespace {
+
+// the launch sequence of one pMCMC iteration: three launches round the filter's own
+int enqueue_pmcmc(fbsmi_lg_pmcmc* h, hipStream_t st, int chain) {
+    const PmDev& p = h->p;
+    k_pm_propose<<<dim3(1, p.C), kPmBlock, 0, st>>>(p, chain);
+    k_pm_u0<<<dim3((p.N + h->rows - 1) / h->rows, p.C), kBlock, 0, st>>>(p, h->rows, chain);
+    int rc = enqueue_filter(h->filt, st);
+    if (rc) return rc;
+    k_pm_accept<<<dim3(1, p.C), kBlock, 0, st>>>(p, chain);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("pmcmc launch: ") + hipGetErrorString(e));
+    return FBSMI_OK;
+}
+
+int run_pmcmc(fbsmi_lg_pmcmc* h, int chain, int use_graph) {
+    hipStream_t st = h->filt->core->stream;
+    if (!use_graph) return enqueue_pmcmc(h, st, chain);
+    hipGraphExec_t& slot = chain ? h->graph_chain : h->graph_step;
+    if (!slot) {
+        hipGraph_t g = nullptr;
+        FBSMI_HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+        int rc = enqueue_pmcmc(h, st, chain);
+        hipError_t e = hipStreamEndCapture(st, &g);
+        if (rc) {
+            if (g) hipGraphDestroy(g);
+            return rc;
+        }
+        if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+        FBSMI_HIP_TRY(hipGraphInstantiate(&slot, g, nullptr, nullptr, 0));
+        FBSMI_HIP_TRY(hipGraphDestroy(g));
+    }
+    FBSMI_HIP_TRY(hipGraphLaunch(slot, st));
+    return FBSMI_OK;
+}
+
+// inputs of a call -> the handle's buffers, on its own stream; `outs` are the five record pointers of k_pm_accept
+int pmcmc_begin(fbsmi_lg_pmcmc* h, const float* uT, const float* log_ell, const float* ys, const float* y0,
+                void* const outs[5], hipStream_t ust) {
+    fbsmi_lg_sweep* s = h->filt->core;
+    const PmDev& p = h->p;
+    const size_t C = p.C, T1 = (size_t)p.T + 1;
+    FBSMI_HIP_TRY(hipEventRecord(s->ev_in, ust));
+    FBSMI_HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_in, 0));
+    FBSMI_HIP_TRY(hipMemcpyAsync(p.uT, uT, C * p.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    FBSMI_HIP_TRY(hipMemcpyAsync(p.log_ell, log_ell, C * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    FBSMI_HIP_TRY(hipMemcpyAsync(p.ys, ys, C * T1 * p.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    FBSMI_HIP_TRY(hipMemcpyAsync(p.y0, y0, p.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    FBSMI_HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(int32_t), s->stream));
+    FBSMI_HIP_TRY(hipMemcpyAsync(p.out, outs, 5 * sizeof(void*), hipMemcpyHostToDevice, s->stream));
+    // the slot copy reads the caller's stack: make sure it has landed before we return
+    FBSMI_HIP_TRY(hipStreamSynchronize(s->stream));
+    return FBSMI_OK;
+}
+
+int pmcmc_end(fbsmi_lg_pmcmc* h, float* uT, float* log_ell, float* ys, hipStream_t ust) {
+    fbsmi_lg_sweep* s = h->filt->core;
+    const PmDev& p = h->p;
+    const size_t C = p.C, T1 = (size_t)p.T + 1;
+    FBSMI_HIP_TRY(hipMemcpyAsync(uT, p.uT, C * p.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    FBSMI_HIP_TRY(hipMemcpyAsync(log_ell, p.log_ell, C * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    FBSMI_HIP_TRY(hipMemcpyAsync(ys, p.ys, C * T1 * p.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    FBSMI_HIP_TRY(hipEventRecord(s->ev_out, s->stream));
+    FBSMI_HIP_TRY(hipStreamWaitEvent(ust, s->ev_out, 0));
+    return FBSMI_OK;
+}
+
+}  // namespace
+
+int fbsmi_lg_pmcmc_create(const fbsmi_lg_model* m, const fbsmi_lg_pmcmc_tables* t, int32_t nparticles, int resampling,
+                          int32_t nchains, fbsmi_lg_pmcmc** out) {
+    if (!m || !t || !out) return fail(FBSMI_ERR_ARG, "lg_pmcmc_create: null argument");
+    if (!t->m_u || !t->m_v || !t->gain || !t->chol || (t->use_pcn && !t->mean_coef))
+        return fail(FBSMI_ERR_ARG, "lg_pmcmc_create: null table (mean_coef is needed with use_pcn)");
+    if (t->which_u < 0 || t->which_u >= nparticles) return fail(FBSMI_ERR_ARG, "lg_pmcmc_create: which_u out of range");
+    if (!m->F || !m->sqQ || m->T < 1) return fail(FBSMI_ERR_ARG, "lg_pmcmc_create: null model table");
+    {
+        // The proposal is the EXACT forward transition x' = F x + sqrt(Q) xi.  A model whose forward process is
+        // Euler-Maruyama (fbsmi_lg_sweep_set_em_forward) carries all-zero placeholders here.
+        std::vector<float> F((size_t)m->T), Q((size_t)m->T);
+        FBSMI_HIP_TRY(hipMemcpy(F.data(), m->F, sizeof(float) * F.size(), hipMemcpyDeviceToHost));
+        FBSMI_HIP_TRY(hipMemcpy(Q.data(), m->sqQ, sizeof(float) * Q.size(), hipMemcpyDeviceToHost));
+        bool any = false;
+        for (size_t k = 0; k < F.size(); ++k) any = any || F[k] != 0.0f || Q[k] != 0.0f;
+        if (!any) return fail(FBSMI_ERR_UNSUPPORTED, "lg_pmcmc: the model has no exact forward transition (F, sqQ)");
+    }
+    fbsmi_lg_filter* filt = nullptr;
+    int rc = fbsmi_lg_filter_create(m, nparticles, 1, resampling, 0, nchains, &filt);
+    if (rc) return rc;
+    fbsmi_lg_pmcmc* h = new (std::nothrow) fbsmi_lg_pmcmc();
+    if (!h) {
+        fbsmi_lg_filter_destroy(filt);
+        return fail(FBSMI_ERR_ARG, "out of host memory");
+    }
+    h->filt = filt;
+    const LgDev& d = filt->core->d;
+    PmDev& p = h->p;
+    p.C = d.C; p.N = d.N; p.du = d.du; p.dv = d.dv; p.T = d.T;
+    p.use_pcn = t->use_pcn ? 1 : 0;
+    p.which_u = t->which_u;
+    p.c0 = t->c0; p.beta = t->beta; p.omb = t->one_minus_beta; p.c1 = t->c1;
+    p.m_u = t->m_u; p.m_v = t->m_v; p.gain = t->gain; p.chol = t->chol; p.coef = t->mean_coef;
+    p.F = d.F; p.sqQ = d.sqQ;
+    p.fkeys = d.keys; p.vs = d.vs; p.u0s = filt->u0s; p.usT = d.usT; p.ell = d.ell;
+    h->rows = kPmTile / p.du < kBlock ? kPmTile / p.du : kBlock;   // du <= 128: at least 32 rows
+    // one allocation, 256-byte aligned pieces
+    const size_t C = p.C, T1 = (size_t)p.T + 1;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    const size_t o_key = take(2 * sizeof(uint32_t)), o_ikeys = take(C * 2 * sizeof(uint32_t)),
+                 o_pk = take(C * 4 * sizeof(uint32_t)), o_y0 = take(p.dv * sizeof(float)),
+                 o_xi = take(C * 2 * (size_t)p.T * p.dv * sizeof(float)), o_mcond = take(C * p.du * sizeof(float)),
+                 o_uT = take(C * p.du * sizeof(float)), o_ell = take(C * sizeof(float)),
+                 o_ys = take(C * T1 * p.dv * sizeof(float)), o_prop = take(C * T1 * p.dv * sizeof(float)),
+                 o_counter = take(sizeof(int32_t)), o_out = take(5 * sizeof(void*));
+    if (hipMalloc(&h->slab, off) != hipSuccess || hipMemset(h->slab, 0, off) != hipSuccess) {
+        fbsmi_lg_pmcmc_destroy(h);
+        return fail(FBSMI_ERR_HIP, "lg_pmcmc_create: device allocation failed");
+    }
+    char* b = (char*)h->slab;
+    p.key = (uint32_t*)(b + o_key); p.ikeys = (uint32_t*)(b + o_ikeys); p.pk = (uint32_t*)(b + o_pk);
+    p.y0 = (float*)(b + o_y0); p.xi = (float*)(b + o_xi); p.mcond = (float*)(b + o_mcond);
+    p.uT = (float*)(b + o_uT); p.log_ell = (float*)(b + o_ell); p.ys = (float*)(b + o_ys);
+    p.prop_ys = (float*)(b + o_prop); p.counter = (int32_t*)(b + o_counter); p.out = (void**)(b + o_out);
+    *out = h;
+    return FBSMI_OK;
+}
+
+void fbsmi_lg_pmcmc_destroy(fbsmi_lg_pmcmc* h) {
+    if (!h) return;
+    if (h->filt && h->filt->core && h->filt->core->stream) hipStreamSynchronize(h->filt->core->stream);
+    if (h->graph_step) hipGraphExecDestroy(h->graph_step);
+    if (h->graph_chain) hipGraphExecDestroy(h->graph_chain);
+    fbsmi_lg_filter_destroy(h->filt);
+    if (h->slab) hipFree(h->slab);
+    delete h;
+}
+
+int fbsmi_lg_pmcmc_step(fbsmi_lg_pmcmc* h, const uint32_t* keys, float* uT, float* log_ell, float* ys, const float* y0,
+                        float* acc_prob, uint8_t* accepted, float* prop_log_ell, int use_graph, void* stream) {
+    if (!h || !keys || !uT || !log_ell || !ys || !y0) return fail(FBSMI_ERR_ARG, "lg_pmcmc_step: null argument");
+    hipStream_t ust = (hipStream_t)stream;
+    hipStream_t st = h->filt->core->stream;
+    void* const outs[5] = {nullptr, acc_prob, accepted, prop_log_ell, nullptr};
+    int rc = pmcmc_begin(h, uT, log_ell, ys, y0, outs, ust);
+    if (rc) return rc;
+    FBSMI_HIP_TRY(hipMemcpyAsync(h->p.ikeys, keys, (size_t)h->p.C * 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    rc = run_pmcmc(h, 0, use_graph);
+    if (rc) return rc;
+    return pmcmc_end(h, uT, log_ell, ys, ust);
+}
+
+int fbsmi_lg_pmcmc_chain(fbsmi_lg_pmcmc* h, uint32_t* key, float* uT, float* log_ell, float* ys, const float* y0,
+                         int32_t nsamples, float* samples, float* acc_prob, uint8_t* accepted, float* prop_log_ell,
+                         float* log_ells, int use_graph, void* stream) {
+    if (!h || !key || !uT || !log_ell || !ys || !y0 || nsamples < 0)
+        return fail(FBSMI_ERR_ARG, "lg_pmcmc_chain: bad arguments");
+    hipStream_t ust = (hipStream_t)stream;
+    hipStream_t st = h->filt->core->stream;
+    void* const outs[5] = {samples, acc_prob, accepted, prop_log_ell, log_ells};
+    int rc = pmcmc_begin(h, uT, log_ell, ys, y0, outs, ust);
+    if (rc) return rc;
+    FBSMI_HIP_TRY(hipMemcpyAsync(h->p.key, key, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    for (int i = 0; i < nsamples; ++i) {
+        rc = run_pmcmc(h, 1, use_graph);
+        if (rc) return rc;
+    }
+    FBSMI_HIP_TRY(hipMemcpyAsync(key, h->p.key, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    return pmcmc_end(h, uT, log_ell, ys, ust);
 }
 
 }  // extern "C"

@@ -58,6 +58,26 @@ def lg_tables(m0, cov0, sde: LinearSDE, ts, du: int, dt: Optional[float] = None)
                 sqQ=sqQ)
 
 
+def lg_pmcmc_tables(m_ref, cov_ref, du: int, delta: Optional[float] = None) -> dict:
+    """Host tables of the fused pMCMC engine (include/fbsmi.h, fbsmi_lg_pmcmc_tables), float64, no device needed:
+    the terms of ref_sampler (gp_pmcmc.py:130-133) that do not depend on yT, from the terminal moments
+    (m_ref, cov_ref) = forward_m_cov(T), and the four pCN constants (smc.py:164-168) rounded once to float32."""
+    m_ref = np.asarray(m_ref, np.float64).reshape(-1)
+    cov_ref = np.asarray(cov_ref, np.float64)
+    d = int(du)
+    gain = cov_ref[:d, d:] @ np.linalg.inv(cov_ref[d:, d:])
+    cov_ = cov_ref[:d, :d] - gain @ cov_ref[d:, :d]
+    tab = dict(m_u=m_ref[:d].copy(), m_v=m_ref[d:].copy(), gain=np.ascontiguousarray(gain),
+               chol=np.ascontiguousarray(np.linalg.cholesky(cov_).astype(np.float32)), use_pcn=delta is not None)
+    if delta is None:
+        tab.update(c0=np.float32(0), beta=np.float32(0), one_minus_beta=np.float32(0), c1=np.float32(0))
+    else:
+        beta = 2 / (2 + delta)
+        tab.update(c0=np.float32(np.sqrt(delta / 2)), beta=np.float32(beta), one_minus_beta=np.float32(1 - beta),
+                   c1=np.float32(np.sqrt(1 - beta)))
+    return tab
+
+
 class _Closure:
     """A callable that remembers the model it came from (how gibbs_kernel recognises the fused path)."""
 
@@ -221,11 +241,50 @@ class LinearGaussianBridge:
             self._sweeps[keyt] = h
         return h
 
-    def filter_handle(self, nparticles: int, flow: str, resampling: str = "stratified", store_path: bool = False):
-        keyt = ("filter", int(nparticles), flow, resampling, bool(store_path))
+    def filter_handle(self, nparticles: int, flow: str, resampling: str = "stratified", store_path: bool = False,
+                      nchains: int = 1):
+        keyt = ("filter", int(nparticles), flow, resampling, bool(store_path), int(nchains))
         h = self._sweeps.get(keyt)
         if h is None:
-            h = LGFilter(self, int(nparticles), flow, resampling, bool(store_path))
+            h = LGFilter(self, int(nparticles), flow, resampling, bool(store_path), int(nchains))
+            self._sweeps[keyt] = h
+        return h
+
+    def fused_pmcmc_supported(self, nparticles: int) -> bool:
+        """What fbsmi_lg_pmcmc_create accepts: the fused filter's sizes, and an exact forward transition (a model with an
+        Euler-Maruyama forward process has none)."""
+        return getattr(self, "em_struct", None) is None and self.sde is not None and self.fused_filter_supported(nparticles)
+
+    def pmcmc_tables_host(self, delta: Optional[float] = None) -> dict:
+        """lg_pmcmc_tables of this bridge plus the pCN mean coefficients float32(sde.mean(ts, ts[0], 1)) (smc.py:236)."""
+        tab = lg_pmcmc_tables(*self.terminal_moments(), self.du, delta)
+        tab["mean_coef"] = None if delta is None else np.ascontiguousarray(
+            np.asarray(self.sde.mean(self.ts_np, self.ts_np[0], 1.0), np.float32).reshape(-1))
+        return tab
+
+    def pmcmc_tables(self, delta: Optional[float] = None, which_u: int = 0):
+        """The device copy of pmcmc_tables_host as an fbsmi_lg_pmcmc_tables struct (cached; the struct keeps its arrays
+        alive through ``_keep``)."""
+        keyt = ("pmcmc_tables", None if delta is None else float(delta), int(which_u))
+        st = self._sweeps.get(keyt)
+        if st is None:
+            tab = self.pmcmc_tables_host(delta)
+            dev = {k: torch.from_numpy(np.ascontiguousarray(tab[k])).to(self.device)
+                   for k in ("m_u", "m_v", "gain", "chol", "mean_coef") if tab[k] is not None}
+            st = _lib.LGPmcmcTablesStruct(dev["m_u"].data_ptr(), dev["m_v"].data_ptr(), dev["gain"].data_ptr(),
+                                          dev["chol"].data_ptr(), dev["mean_coef"].data_ptr() if "mean_coef" in dev else None,
+                                          float(tab["c0"]), float(tab["beta"]), float(tab["one_minus_beta"]),
+                                          float(tab["c1"]), int(tab["use_pcn"]), int(which_u))
+            st._keep = dev
+            self._sweeps[keyt] = st
+        return st
+
+    def pmcmc_handle(self, nparticles: int, resampling: str = "stratified", nchains: int = 1,
+                     delta: Optional[float] = None, which_u: int = 0):
+        keyt = ("pmcmc", int(nparticles), resampling, int(nchains), None if delta is None else float(delta), int(which_u))
+        h = self._sweeps.get(keyt)
+        if h is None:
+            h = LGPmcmc(self, int(nparticles), resampling, int(nchains), delta, int(which_u))
             self._sweeps[keyt] = h
         return h
 
@@ -400,17 +459,20 @@ class LGSweep:
 
 class LGFilter:
     """Fused bootstrap_filter (flow='bootstrap', smc.py:9-88) / pmcmc_filter_step (flow='pmcmc',
-    smc.py:115-158) for the analytic model: one hipGraph replay per call."""
+    smc.py:115-158) for the analytic model: one hipGraph replay per call, for `nchains` independent filters at once.
+
+    With nchains == 1 the chain axis is squeezed from inputs and outputs; with nchains > 1 keys (C,2), vs (C,T+1,dv) and
+    u0s (C,n,du) carry it and so does every output."""
 
     _FLOW = {"bootstrap": 0, "pmcmc": 1}
     _RES = {"stratified": 0, "systematic": 1}
 
-    def __init__(self, model: LinearGaussianBridge, nparticles, flow, resampling, store_path):
-        self.model, self.n, self.flow, self.store = model, nparticles, flow, store_path
+    def __init__(self, model: LinearGaussianBridge, nparticles, flow, resampling, store_path, nchains=1):
+        self.model, self.n, self.flow, self.store, self.C = model, nparticles, flow, store_path, int(nchains)
         h = C.c_void_p()
         with torch.cuda.device(model.device):
             _lib.call("fbsmi_lg_filter_create", C.byref(model.struct), nparticles, self._FLOW[flow],
-                      self._RES[resampling], int(store_path), 1, C.byref(h))
+                      self._RES[resampling], int(store_path), self.C, C.byref(h))
         self.h = h
 
     def __del__(self):
@@ -422,15 +484,97 @@ class LGFilter:
             pass
 
     def run(self, key, vs, u0s, use_graph=True):
-        """-> (particles (n, du), log-likelihood scalar tensor[, filtering path (T+1, n, du)])."""
-        m = self.model
-        k = np.asarray(key.detach().cpu() if isinstance(key, torch.Tensor) else key).astype(np.uint32).reshape(1, 2)
+        """-> (particles ([C,] n, du), log-likelihood ([C]) tensor[, filtering path ([C,] T+1, n, du)])."""
+        m, Cn = self.model, self.C
+        k = np.asarray(key.detach().cpu() if isinstance(key, torch.Tensor) else key).astype(np.uint32).reshape(Cn, 2)
         kt = torch.from_numpy(k.view(np.int32).copy()).to(m.device)
-        vst = m._t(vs).reshape(m.T + 1, m.dv)
-        u0t = m._t(u0s).reshape(self.n, m.du)
-        uT = torch.empty((self.n, m.du), dtype=torch.float32, device=m.device)
-        ell = torch.empty(1, dtype=torch.float32, device=m.device)
-        path = torch.empty((m.T + 1, self.n, m.du), dtype=torch.float32, device=m.device) if self.store else None
+        vst = m._t(vs).reshape(Cn, m.T + 1, m.dv)
+        u0t = m._t(u0s).reshape(Cn, self.n, m.du)
+        uT = torch.empty((Cn, self.n, m.du), dtype=torch.float32, device=m.device)
+        ell = torch.empty(Cn, dtype=torch.float32, device=m.device)
+        path = torch.empty((Cn, m.T + 1, self.n, m.du), dtype=torch.float32, device=m.device) if self.store else None
         _lib.call("fbsmi_lg_filter_run", self.h, kt.data_ptr(), vst.data_ptr(), u0t.data_ptr(), uT.data_ptr(),
                   ell.data_ptr(), path.data_ptr() if path is not None else None, int(bool(use_graph)), ops._stream())
-        return (uT, ell.reshape(())) if path is None else (uT, ell.reshape(()), path)
+        sq = (lambda t: t[0]) if Cn == 1 else (lambda t: t)
+        return (sq(uT), sq(ell)) if path is None else (sq(uT), sq(ell), sq(path))
+
+
+class LGPmcmc:
+    """Owns one fbsmi_lg_pmcmc handle: pmcmc_kernel (smc.py:171-258) for `nchains` chains, one hipGraph replay per MCMC
+    iteration, nothing on the host between iterations.
+
+    With nchains == 1 the chain axis is squeezed from inputs and outputs (the reference's plain pmcmc_kernel); with
+    nchains > 1 every per-chain array carries a leading axis of that size, like the reference's
+    jax.vmap(pmcmc_kernel, in_axes=[0, 0, 0, 0, None]) (gp_pmcmc.py:161)."""
+
+    def __init__(self, model: LinearGaussianBridge, nparticles, resampling, nchains=1, delta=None, which_u=0):
+        if not model.fused_pmcmc_supported(nparticles):
+            raise NotImplementedError("the fused pMCMC engine needs an exact forward transition and a model size the fused "
+                                      "filter takes")
+        self.model, self.n, self.C, self.delta = model, nparticles, int(nchains), delta
+        self.tables = model.pmcmc_tables(delta, which_u)
+        h = C.c_void_p()
+        with torch.cuda.device(model.device):
+            _lib.call("fbsmi_lg_pmcmc_create", C.byref(model.struct), C.byref(self.tables), nparticles,
+                      LGFilter._RES[resampling], self.C, C.byref(h))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                _lib.lib().fbsmi_lg_pmcmc_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _dev(self, x, shape):
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x, np.float32))
+        return x.to(self.model.device, torch.float32).reshape(shape).contiguous().clone()
+
+    def _key_t(self, key, n):
+        k = np.asarray(key.detach().cpu() if isinstance(key, torch.Tensor) else key).astype(np.uint32).reshape(n, 2)
+        return torch.from_numpy(k.view(np.int32).copy()).to(self.model.device)
+
+    def _sq(self, t, axis=0):
+        return t.squeeze(axis) if self.C == 1 else t
+
+    def _state_in(self, uT, log_ell, ys, y0):
+        m, Cn = self.model, self.C
+        return (self._dev(uT, (Cn, m.du)), self._dev(log_ell, (Cn,)), self._dev(ys, (Cn, m.T + 1, m.dv)),
+                self._dev(y0, (m.dv,)))
+
+    def step(self, keys, uT, log_ell, ys, y0, use_graph=True):
+        """keys (C,2) [or (2,)], uT (C,du), log_ell (C), ys (C,T+1,dv), y0 (dv,) -> (uT, log_ell, ys, MCMCState)."""
+        from .samplers.common import MCMCState
+        m, Cn = self.model, self.C
+        kt = self._key_t(keys, Cn)
+        uTt, ellt, yst, y0t = self._state_in(uT, log_ell, ys, y0)
+        old = ellt.clone()
+        prob = torch.empty(Cn, dtype=torch.float32, device=m.device)
+        acc = torch.empty(Cn, dtype=torch.uint8, device=m.device)
+        prop = torch.empty(Cn, dtype=torch.float32, device=m.device)
+        _lib.call("fbsmi_lg_pmcmc_step", self.h, kt.data_ptr(), uTt.data_ptr(), ellt.data_ptr(), yst.data_ptr(),
+                  y0t.data_ptr(), prob.data_ptr(), acc.data_ptr(), prop.data_ptr(), int(bool(use_graph)), ops._stream())
+        state = MCMCState(acceptance_prob=self._sq(prob), is_accepted=self._sq(acc.bool()), prop_log_ell=self._sq(prop),
+                          log_ell=self._sq(old))
+        return self._sq(uTt), self._sq(ellt), self._sq(yst), state
+
+    def chain(self, key, uT, log_ell, ys, y0, nsamples, use_graph=True):
+        """nsamples iterations; per iteration ``key, subkey = split(key)`` and chain c runs with split(subkey, C)[c]
+        (gp_pmcmc.py:171-172).  Returns (key, uT, log_ell, ys, samples, MCMCState) with samples (nsamples, [C,] du) and the
+        state's fields (nsamples, [C])."""
+        from .samplers.common import MCMCState
+        m, Cn, ns = self.model, self.C, int(nsamples)
+        kt = self._key_t(key, 1)
+        uTt, ellt, yst, y0t = self._state_in(uT, log_ell, ys, y0)
+        samples = torch.empty((ns, Cn, m.du), dtype=torch.float32, device=m.device)
+        prob, prop, ells = (torch.empty((ns, Cn), dtype=torch.float32, device=m.device) for _ in range(3))
+        acc = torch.empty((ns, Cn), dtype=torch.uint8, device=m.device)
+        _lib.call("fbsmi_lg_pmcmc_chain", self.h, kt.data_ptr(), uTt.data_ptr(), ellt.data_ptr(), yst.data_ptr(),
+                  y0t.data_ptr(), ns, samples.data_ptr(), prob.data_ptr(), acc.data_ptr(), prop.data_ptr(), ells.data_ptr(),
+                  int(bool(use_graph)), ops._stream())
+        key_out = kt.cpu().numpy().view(np.uint32).reshape(2).copy()
+        state = MCMCState(acceptance_prob=self._sq(prob, 1), is_accepted=self._sq(acc.bool(), 1),
+                          prop_log_ell=self._sq(prop, 1), log_ell=self._sq(ells, 1))
+        return key_out, self._sq(uTt), self._sq(ellt), self._sq(yst), self._sq(samples, 1), state

@@ -168,6 +168,65 @@ def pmcmc_kernel(key, uT, log_ell, ys, y0, ts, fwd_ys_sampler, sde, ref_sampler,
     return uT, log_ell_t, ys, state
 
 
+def _fused_pmcmc(fwd_ys_sampler, sde, ref_sampler, transition_sampler, likelihood_logpdf, resampling, ts, nparticles, delta):
+    """(model, resampling name) when the fused pMCMC engine applies: all four closures belong to one
+    LinearGaussianBridge on its own grid, its forward transition is exact, and the resampler is one the fused filter has."""
+    fused = _fused_filter(transition_sampler, likelihood_logpdf, resampling, {}, nparticles)
+    if fused is None:
+        return None
+    model = fused[0]
+    for closure, role in ((fwd_ys_sampler, "fwd_ys_sampler"), (ref_sampler, "ref_sampler"),
+                          (transition_sampler, "transition_sampler")):
+        if getattr(closure, "_fbsmi_lg", None) is not model or getattr(closure, "_role", "") != role:
+            return None
+    if not model.fused_pmcmc_supported(nparticles) or not model.same_grid(ts):
+        return None
+    if delta is not None and sde is not model.sde:       # the pCN mean path is tabulated from the bridge's own SDE
+        return None
+    return fused
+
+
+def pmcmc_chain(key, uTs, log_ells, yss, y0, ts, fwd_ys_sampler, sde, ref_sampler, transition_sampler, likelihood_logpdf,
+                resampling, nparticles, nsamples, delta: float = None):
+    """The pMCMC loop of experiments/toy/gp_pmcmc.py:170-179 for C = uTs.shape[0] chains: per iteration
+    ``key, subkey = split(key)`` and chain c runs pmcmc_kernel with split(subkey, C)[c].
+
+    uTs (C, du), log_ells (C,), yss (C, T+1, dv), y0 (dv,).  Returns (key, uTs, log_ells, yss, samples, states) with
+    samples (nsamples, C, du) and states an MCMCState of (nsamples, C) tensors.  With the closures of one
+    LinearGaussianBridge and stratified / systematic resampling the whole loop runs on the device (LGPmcmc.chain);
+    otherwise pmcmc_kernel is called per chain and iteration with the same keys."""
+    nchains, nsamples = int(uTs.shape[0]), int(nsamples)
+    fused = _fused_pmcmc(fwd_ys_sampler, sde, ref_sampler, transition_sampler, likelihood_logpdf, resampling, ts,
+                         nparticles, delta)
+    if fused is not None:
+        model, rname = fused
+        h = model.pmcmc_handle(nparticles, rname, nchains, delta)
+        out = h.chain(key, uTs, log_ells, yss, y0, nsamples)
+        if nchains > 1:
+            return out
+        key, uT, ell, ys, samples, st = out                # (the handle squeezes a single chain's axis)
+        return (key, uT[None], ell[None], ys[None], samples[:, None], MCMCState(*(f[:, None] for f in st)))
+    dev = uTs.device
+    state = [(uTs[c], log_ells[c], yss[c]) for c in range(nchains)]
+    samples = torch.empty((nsamples, nchains) + tuple(uTs.shape[1:]), dtype=torch.float32, device=dev)
+    fields = [[] for _ in MCMCState._fields]
+    for i in range(nsamples):
+        key, subkey = ops.split(key)
+        row = [[] for _ in MCMCState._fields]
+        for c, kc in enumerate(ops.split(subkey, nchains)):
+            uT, log_ell, ys, st = pmcmc_kernel(kc, *state[c], y0, ts, fwd_ys_sampler, sde, ref_sampler, transition_sampler,
+                                               likelihood_logpdf, resampling, nparticles, delta=delta)
+            state[c] = (uT, log_ell, ys)
+            samples[i, c] = uT
+            for r, f in zip(row, st):
+                r.append(f.reshape(()))
+        for fl, r in zip(fields, row):
+            fl.append(torch.stack(r))
+    states = MCMCState(*(torch.stack(fl) if fl else torch.empty((0, nchains), device=dev) for fl in fields))
+    return (key, torch.stack([s[0] for s in state]), torch.stack([torch.as_tensor(s[1], device=dev).reshape(()) for s in state]),
+            torch.stack([s[2] for s in state]), samples, states)
+
+
 def twisted_smc(key, y, ts, init_sampler, transition_logpdf, twisting_logpdf, twisting_prop_sampler,
                 twisting_prop_logpdf, resampling, nparticles, **kwargs):
     """Twisted SMC baseline (smc.py:261-309; Algorithm 1 of arXiv 2306.17775)."""

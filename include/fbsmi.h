@@ -238,6 +238,57 @@ void fbsmi_lg_filter_destroy(fbsmi_lg_filter* f);
 int fbsmi_lg_filter_run(fbsmi_lg_filter* f, const uint32_t* keys, const float* vs, const float* u0s, float* uT,
                         float* loglik, float* path, int use_graph, void* stream);
 
+/* Fused particle-marginal Metropolis-Hastings for the analytic model: pmcmc_kernel (fbs/samplers/smc.py:171-258, with
+ * delta = None or the pCN proposal of smc.py:161-168) for `nchains` chains in every launch, inside the loop of
+ * experiments/toy/gp_pmcmc.py:163-179.  One iteration is three launches round the flow-1 filter above (keys + proposal
+ * path + reversal; initial particles; accept), captured with it in one hipGraph; nothing returns to the host between
+ * iterations.  The tables are device arrays built ONCE on the host in float64 from (m_ref, cov_ref) = forward_m_cov(T)
+ * (gp_gibbs.py:84-86): m_u = m_ref[:du], m_v = m_ref[du:], gain = cov_ref[:du, du:] inv(cov_ref[du:, du:]),
+ * chol = float32(cholesky(cov_ref[:du, :du] - gain cov_ref[du:, :du])) (lower), mean_coef[k] = float32(sde.mean(ts[k],
+ * ts[0], 1)).  They must outlive the handle.
+ * Numeric specification (no contraction anywhere; every operation separately rounded):
+ *   forward path   r[0] = y0, r[k+1] = F[k] * r[k] + sqQ[k] * xi[k], xi = normal(key, (T, dv))  (fbsmi_linear_path);
+ *   pCN            mean[k] = mean_coef[k] * y0;  p = ys[k] + c0 * (r0[k] - mean[k]);
+ *                  prop_ys[k] = (beta * p + one_minus_beta * mean[k]) + c1 * (r1[k] - mean[k]),  float32, where r0, r1
+ *                  are the paths of split(key_prop, 2) and c0 = float32(sqrt(delta / 2)), beta = float32(2 / (2 + delta)),
+ *                  one_minus_beta = float32(1 - 2 / (2 + delta)), c1 = float32(sqrt(1 - 2 / (2 + delta)));
+ *   ref_sampler    (gp_pmcmc.py:130-133) with yT = prop_ys[T]:
+ *                  m_[j] = float32( m_u[j] + s_j ), s_j = 0, then s_j = s_j + gain[j][c] * (double(yT[c]) - m_v[c]) for
+ *                  c = 0 .. dv-1, float64;  z = normal(key_u0, (n, du));
+ *                  acc = z[i][0] * chol[0][j], then acc = acc + z[i][c] * chol[c][j] for c = 1 .. du-1, float32;
+ *                  u0[i][j] = m_[j] + acc;
+ *   accept         log_acc = minimum(0, prop_log_ell - log_ell); accepted = fbsmi_logf(uniform(key_mh, ())) < log_acc;
+ *                  acceptance_prob = fbsmi_expf(log_acc).
+ * Keys: key_prop, key_u0, key_filter, key_mh = split(key, 4) (smc.py:231). */
+typedef struct fbsmi_lg_pmcmc_tables {
+    const double* m_u;       /* (du) */
+    const double* m_v;       /* (dv) */
+    const double* gain;      /* (du, dv) */
+    const float* chol;       /* (du, du) lower factor */
+    const float* mean_coef;  /* (T+1), pCN only (nullable) */
+    float c0, beta, one_minus_beta, c1; /* pCN constants */
+    int32_t use_pcn;         /* 0: independent proposals (delta = None) */
+    int32_t which_u;         /* the particle of the filter's output that is proposed (smc.py:244) */
+} fbsmi_lg_pmcmc_tables;
+typedef struct fbsmi_lg_pmcmc fbsmi_lg_pmcmc; /* opaque: a flow-1 filter, the chain state and the captured graphs */
+/* resampling 0 stratified | 1 systematic.  FBSMI_ERR_UNSUPPORTED for what fbsmi_lg_filter_create does not take and for a
+ * model without an exact forward transition (Euler-Maruyama forward process: F and sqQ are all-zero placeholders). */
+int fbsmi_lg_pmcmc_create(const fbsmi_lg_model* model, const fbsmi_lg_pmcmc_tables* tables, int32_t nparticles,
+                          int resampling, int32_t nchains, fbsmi_lg_pmcmc** out);
+void fbsmi_lg_pmcmc_destroy(fbsmi_lg_pmcmc* h);
+/* One iteration with explicit per-chain keys (C,2).  The state uT (C,du), log_ell (C), ys (C,T+1,dv) is updated in
+ * place; y0 (dv) is shared by the chains.  Nullable outputs: acc_prob (C), accepted (C) bytes, prop_log_ell (C). */
+int fbsmi_lg_pmcmc_step(fbsmi_lg_pmcmc* h, const uint32_t* keys, float* uT, float* log_ell, float* ys, const float* y0,
+                        float* acc_prob, uint8_t* accepted, float* prop_log_ell, int use_graph, void* stream);
+/* nsamples iterations with the driver's key schedule (gp_pmcmc.py:171-172): per iteration key, subkey = split(key) and
+ * chain c takes split(subkey, C)[c], for every C >= 1; key (2) is advanced in place, on the device.  samples
+ * (nsamples, C, du) receives the state uT after every iteration, acc_prob / accepted (bytes) / prop_log_ell / log_ells
+ * (nsamples, C) the fields of MCMCState (fbs/samplers/common.py; log_ell is the state's value BEFORE the decision,
+ * smc.py:254); each nullable. */
+int fbsmi_lg_pmcmc_chain(fbsmi_lg_pmcmc* h, uint32_t* key, float* uT, float* log_ell, float* ys, const float* y0,
+                         int32_t nsamples, float* samples, float* acc_prob, uint8_t* accepted, float* prop_log_ell,
+                         float* log_ells, int use_graph, void* stream);
+
 /* ---- fused SMC step for score-network models (image experiments) --------------------------------
  * The three closures of experiments/imgs/inpainting.py:102-147 (and supr.py; sb_imgs/supr.py:80-127)
  * wrap ONE network evaluation on the joint image concat(u, v) per SMC step (csmc.py:142,145 evaluate it
