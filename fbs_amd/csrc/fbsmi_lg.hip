@@ -3586,11 +3586,9 @@ static hipStream_t pool_stream(int g) {
 }
 
 struct fbsmi_lg_sweep {
-    LgDev d{};
+    LgDev d{};   // (zeroed: a buffer this model does not need stays null)
     int items = 1, dmax = 2;
     std::vector<void*> allocs;
-    std::vector<std::pair<void**, size_t>> slab_reqs;   // (pointer slot, offset) until slab_commit
-    size_t slab_bytes = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     hipGraphExec_t graph_single = nullptr;  // one sweep, no chain bookkeeping
@@ -3640,61 +3638,52 @@ int dev_alloc(fbsmi_lg_sweep* s, T** p, size_t count) {
 // The buffers of a handle are carved from ONE allocation: the step kernels touch ~20 of them per
 // launch, and as separate hipMallocs each sits in pages of its own -- a first-touch translation miss
 // per buffer per kernel, on the critical path of kernels that run for a few microseconds.
-template <typename T>
-int slab_request(fbsmi_lg_sweep* s, T** p, size_t count) {
-    const size_t bytes = (sizeof(T) * (count ? count : 1) + 255) & ~(size_t)255;
-    s->slab_reqs.push_back({(void**)p, s->slab_bytes});
-    s->slab_bytes += bytes;
-    *p = nullptr;
-    return 0;
-}
+// request() the pieces (each rounded up to 256 bytes, laid out in request order), then commit() once: one zeroed
+// allocation, every requested pointer set into it.
+struct Slab {
+    std::vector<std::pair<void**, size_t>> reqs;   // (pointer slot, offset)
+    size_t bytes = 0;
 
-int slab_commit(fbsmi_lg_sweep* s) {
-    void* q = nullptr;
-    FBSMI_HIP_TRY(hipMalloc(&q, s->slab_bytes ? s->slab_bytes : 256));
-    s->allocs.push_back(q);
-    FBSMI_HIP_TRY(hipMemset(q, 0, s->slab_bytes ? s->slab_bytes : 256));
-    for (auto& r : s->slab_reqs) *r.first = (char*)q + r.second;
-    s->slab_reqs.clear();
-    return 0;
-}
+    template <typename T>
+    void request(T** p, size_t count) {
+        reqs.push_back({(void**)p, bytes});
+        bytes += (sizeof(T) * (count ? count : 1) + 255) & ~(size_t)255;
+    }
 
-#define LG_DISPATCH(s, ...)                                                                   \
-    do {                                                                                      \
-        if ((s)->items == 1) {                                                                \
-            constexpr int ITEMS = 1;                                                          \
-            if ((s)->dmax == 1) { constexpr int DMAX = 1; __VA_ARGS__; }                      \
-            else if ((s)->dmax == 2) { constexpr int DMAX = 2; __VA_ARGS__; }                 \
-            else if ((s)->dmax == 4) { constexpr int DMAX = 4; __VA_ARGS__; }                 \
-            else { constexpr int DMAX = 16; __VA_ARGS__; }                                    \
-        } else if ((s)->items == 4) {                                                         \
-            constexpr int ITEMS = 4;                                                          \
-            if ((s)->dmax == 1) { constexpr int DMAX = 1; __VA_ARGS__; }                      \
-            else if ((s)->dmax == 2) { constexpr int DMAX = 2; __VA_ARGS__; }                 \
-            else if ((s)->dmax == 4) { constexpr int DMAX = 4; __VA_ARGS__; }                 \
-            else { constexpr int DMAX = 16; __VA_ARGS__; }                                    \
-        } else {                                                                              \
-            constexpr int ITEMS = 16;                                                         \
-            if ((s)->dmax == 1) { constexpr int DMAX = 1; __VA_ARGS__; }                      \
-            else if ((s)->dmax == 2) { constexpr int DMAX = 2; __VA_ARGS__; }                 \
-            else if ((s)->dmax == 4) { constexpr int DMAX = 4; __VA_ARGS__; }                 \
-            else { constexpr int DMAX = 16; __VA_ARGS__; }                                    \
-        }                                                                                     \
+    // *base is the allocation (the caller's to free, also when the status is an error)
+    hipError_t commit(void** base) {
+        hipError_t e = hipMalloc(base, bytes ? bytes : 256);
+        if (e == hipSuccess) e = hipMemset(*base, 0, bytes ? bytes : 256);
+        if (e != hipSuccess) return e;
+        for (auto& r : reqs) *r.first = (char*)*base + r.second;
+        reqs.clear();
+        return hipSuccess;
+    }
+};
+
+// Launch with a handle's compile-time parameters bound: LG_DMAX names DMAX (s->dmax: 1, 2, 4 or 16), LG_ITEMS names ITEMS
+// (s->items: 1, 4 or 16).  A kernel that takes both nests them: LG_ITEMS(s, LG_DMAX(s, k<ITEMS, DMAX><<<...>>>(...))).
+#define LG_DMAX(s, ...)                                                       \
+    do {                                                                      \
+        if ((s)->dmax == 1) { constexpr int DMAX = 1; __VA_ARGS__; }          \
+        else if ((s)->dmax == 2) { constexpr int DMAX = 2; __VA_ARGS__; }     \
+        else if ((s)->dmax == 4) { constexpr int DMAX = 4; __VA_ARGS__; }     \
+        else { constexpr int DMAX = 16; __VA_ARGS__; }                        \
+    } while (0)
+#define LG_ITEMS(s, ...)                                                      \
+    do {                                                                      \
+        if ((s)->items == 1) { constexpr int ITEMS = 1; __VA_ARGS__; }        \
+        else if ((s)->items == 4) { constexpr int ITEMS = 4; __VA_ARGS__; }   \
+        else { constexpr int ITEMS = 16; __VA_ARGS__; }                       \
     } while (0)
 
 struct ProfScope {
     fbsmi_lg_sweep* s;
     int which;
     hipStream_t st;
-    ProfScope(fbsmi_lg_sweep* s_, int which_, hipStream_t st_) : s(s_), which(which_), st(st_) {
-        if (s->profile) {
-            hipEvent_t e;
-            hipEventCreate(&e);
-            hipEventRecord(e, st);
-            s->prof_ev[which].push_back(e);
-        }
-    }
-    ~ProfScope() {
+    ProfScope(fbsmi_lg_sweep* s_, int which_, hipStream_t st_) : s(s_), which(which_), st(st_) { mark(); }
+    ~ProfScope() { mark(); }
+    void mark() {
         if (s->profile) {
             hipEvent_t e;
             hipEventCreate(&e);
@@ -3704,70 +3693,94 @@ struct ProfScope {
     }
 };
 
-// the launch sequence of one sweep on stream st
-int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
+// after a launch list: what the launches left in hipGetLastError
+int launch_status(const char* what) {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FBSMI_OK : fail(FBSMI_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+}
+
+// blocks of a grid-stride launch over n elements: ceil(n / per_block), at least 1, at most cap
+int grid_1d(int64_t n, int per_block, int cap) {
+    const int64_t g = (n + per_block - 1) / per_block;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// Launch geometry of the wide models' drift product (k_lgw_gemm*: MFMA drift, one workgroup per (32 slots, 32 drift rows))
+struct WideGeom {
+    int nrt, Kp, S;   // row tiles of D; D padded to 16; LDS plane row (wide_plane_row)
+    size_t lds;
+    int nst;          // slot tiles
+    int u_tiles;      // row tiles holding rows < du
+    int v_tile0;      // first row tile holding rows >= du
+    explicit WideGeom(const LgDev& d)
+        : nrt((d.D + kWideTile - 1) / kWideTile), Kp((d.D + 15) / 16 * 16), S(wide_plane_row(Kp)), lds(wide_lds_bytes(S)),
+          nst((d.N + kWideTile - 1) / kWideTile), u_tiles((d.du + kWideTile - 1) / kWideTile), v_tile0(d.du / kWideTile) {}
+    int v_tiles() const { return nrt - v_tile0; }
+};
+
+// ---- the launch sequence of one sweep on stream st, by regime ---------------------------------
+
+void sweep_prologue(fbsmi_lg_sweep* s, hipStream_t st, int chain, const WideGeom& w) {
     const LgDev& d = s->d;
-    const int nb = d.nb;
-    const dim3 gone(1, d.C), gtile(nb, d.C);
-    k_lg_keys<<<gone, kBlock, 0, st>>>(d, chain);
-    const unsigned em_block = (unsigned)((d.D + 63) / 64 * 64);
+    const dim3 gtile(d.nb, d.C);
+    k_lg_keys<<<dim3(1, d.C), kBlock, 0, st>>>(d, chain);
     if (s->em) {
-        const int64_t n = (int64_t)d.T * s->emd.t.nsub * d.D;
-        int g = (int)((n + 255) / 256);
-        g = g < 1 ? 1 : (g > 1024 ? 1024 : g);
-        k_lg_em_noise<<<dim3(g, d.C), 256, 0, st>>>(d, s->emd);
+        k_lg_em_noise<<<dim3(grid_1d((int64_t)d.T * s->emd.t.nsub * d.D, 256, 1024), d.C), 256, 0, st>>>(d, s->emd);
+        k_lg_em_path<<<dim3(1, d.C), (unsigned)((d.D + 63) / 64 * 64), 0, st>>>(d, s->emd, 0);
     } else {
-        const int64_t n = (int64_t)d.T * d.D;
-        int g = (int)((n + 255) / 256);
-        g = g < 1 ? 1 : (g > 1024 ? 1024 : g);
-        k_lg_noise<<<dim3(g, d.C), 256, 0, st>>>(d);
+        k_lg_noise<<<dim3(grid_1d((int64_t)d.T * d.D, 256, 1024), d.C), 256, 0, st>>>(d);
+        k_lg_path<<<dim3((d.D + 63) / 64, d.C), 64, 0, st>>>(d, 0);
     }
-    const int gpath = (d.D + 63) / 64;
-    if (s->em) k_lg_em_path<<<dim3(1, d.C), em_block, 0, st>>>(d, s->emd, 0);
-    else k_lg_path<<<dim3(gpath, d.C), 64, 0, st>>>(d, 0);
-    // wide models: MFMA drift, one workgroup per (32 slots, 32 drift rows)
-    const int w_nrt = (d.D + kWideTile - 1) / kWideTile, w_Kp = (d.D + 15) / 16 * 16;
-    const int w_S = wide_plane_row(w_Kp);
-    const size_t w_lds = wide_lds_bytes(w_S);
-    const dim3 gwide(((d.N + kWideTile - 1) / kWideTile) * w_nrt, d.C);
     if (d.wide) {
         k_lgw_init<<<gtile, kBlock, 0, st>>>(d);
         if (d.ef) {   // initial log-weights: rows >= du of the drift product on the initial particles, no resampling
-            const int v_tile0 = d.du / kWideTile;
-            k_lgw_gemm<3><<<dim3(((d.N + kWideTile - 1) / kWideTile) * (w_nrt - v_tile0), d.C), kBlock, w_lds, st>>>(
-                d, 0, v_tile0, w_nrt - v_tile0, w_Kp, w_S, 2, 1);
+            k_lgw_gemm<3><<<dim3(w.nst * w.v_tiles(), d.C), kBlock, w.lds, st>>>(d, 0, w.v_tile0, w.v_tiles(), w.Kp, w.S, 2, 1);
             if (d.N > kBlock) k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);   // several tiles: lw + partials for k_lg_norm
         }
-    } else LG_DISPATCH(s, (k_lg_init<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d)));
-    const bool one_tile = d.N <= kBlock;   // the steps need no grid-wide stage of their own
-    const bool persistent = one_tile && !d.wide && !s->profile;
-    if (persistent) LG_DISPATCH(s, (void)ITEMS; (k_lg_sweep1<DMAX><<<gone, kBlock, 0, st>>>(d)));
-    for (int k = 0; one_tile && !persistent && k < d.T; ++k) {
+    } else LG_ITEMS(s, LG_DMAX(s, k_lg_init<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d)));
+}
+
+// narrow, one tile: the whole forward pass is one launch (the steps need no grid-wide stage of their own)
+void sweep_one_tile_persistent(fbsmi_lg_sweep* s, hipStream_t st) {
+    const LgDev& d = s->d;
+    LG_DMAX(s, k_lg_sweep1<DMAX><<<dim3(1, d.C), kBlock, 0, st>>>(d));
+}
+
+// one tile, wide (the drift product) or narrow while profiling (so that the steps can be timed): one launch per step
+void sweep_one_tile_stepwise(fbsmi_lg_sweep* s, hipStream_t st, const WideGeom& w) {
+    const LgDev& d = s->d;
+    const int gwide = w.nst * w.nrt;
+    // (one chain per launch only: with two chains per launch and two chain groups in flight the pinned step measured
+    // 29 us against 16 unpinned, round 3)
+    const bool pinned = d.wide && s->wide_pin && xcd_round_robin_holds() && d.C == 1 && gwide <= 32;
+    // (unpinned: + extra blocks that draw the next step's noise beside the step: one per 1024 elements, at most 16)
+    const int extra = grid_1d((int64_t)d.N * d.du, 1024, 16);
+    for (int k = 0; k < d.T; ++k) {
         ProfScope p(s, 2, st);
-        if (d.wide) {
-            // (one chain per launch only: with two chains per launch and two chain groups in flight the pinned step measured
-            // 29 us against 16 unpinned, round 3)
-            if (s->wide_pin && xcd_round_robin_holds() && d.C == 1 && gwide.x <= 32)
-                k_lgw_gemm<1><<<dim3(gwide.x * 8, d.C), kBlock, w_lds, st>>>(d, k, 0, w_nrt, w_Kp, w_S, 3, 8 + ((2 * d.c0) & 7));
-            else {
-                // (+ extra blocks that draw the next step's noise beside the step: one per 1024 elements, at most 16)
-                const int64_t tot = (int64_t)d.N * d.du;
-                const int extra = (int)((tot + 1023) / 1024 < 16 ? (tot + 1023) / 1024 : 16);
-                k_lgw_gemm<1><<<dim3(gwide.x + extra, d.C), kBlock, w_lds, st>>>(d, k, 0, w_nrt, w_Kp, w_S, 3, 0);
-            }
-        }
-        else LG_DISPATCH(s, (void)ITEMS; (k_lg_step1<DMAX><<<gone, kBlock, 0, st>>>(d, k)));
+        if (pinned) k_lgw_gemm<1><<<dim3(gwide * 8, d.C), kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3, 8 + ((2 * d.c0) & 7));
+        else if (d.wide) k_lgw_gemm<1><<<dim3(gwide + extra, d.C), kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3, 0);
+        else LG_DMAX(s, k_lg_step1<DMAX><<<dim3(1, d.C), kBlock, 0, st>>>(d, k));
     }
-    if (one_tile) {   // log-weights / tile partial for the final-mode kernels
-        if (d.wide) k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);
-        else k_lg_lwpart<<<gtile, kBlock, 0, st>>>(d);
+}
+
+// Several tiles: the launches of a step in front of its propagation.  tree (N a power of two): normalise and publish the
+// summation tree, which the searches walk -- no cdf launch (k_lg_prop1t).  Otherwise normalise, then the cdf, on grid g with
+// descriptor dk (the handle's own, or with the fat step's noise blocks).
+void step_norm_cdf(fbsmi_lg_sweep* s, hipStream_t st, int k, bool tree, dim3 g, const LgDev& dk) {
+    {
+        ProfScope p(s, 0, st);
+        if (tree) k_lg_norm<1, 0, true><<<dim3(g.x * (dk.pin ? 8 : 1), g.y), kBlock, 0, st>>>(dk, k);
+        else LG_ITEMS(s, k_lg_norm<ITEMS, 0><<<g, kBlock, 0, st>>>(dk, k));
     }
-    // enough workgroups that instruction issue, not latency, bounds the step (measured crossover: between four and six
-    // 256-slot workgroups per CU): two slots per thread, three Threefry calls instead of six
-    const bool two_slot = !d.wide && s->items == 1 && d.N % (2 * kBlock) == 0 &&
-                          (s->two_slot_prop == 1 || (s->two_slot_prop < 0 && (int64_t)nb * d.C >= 5 * 256));
-    // N a power of two: the searches walk the summation tree, no cdf launch (k_lg_prop1t)
-    const bool tree = s->tree_step && d.trW;
+    if (tree) return;
+    ProfScope p(s, 1, st);
+    LG_ITEMS(s, k_lg_cdf<ITEMS, 0><<<g, kBlock, 0, st>>>(dk, k));
+}
+
+// wide, several tiles: norm, cdf, ancestors, drift (tiled or fat), row sums
+void sweep_steps_wide(fbsmi_lg_sweep* s, hipStream_t st, const WideGeom& w) {
+    const LgDev& d = s->d;
+    const dim3 gtile(d.nb, d.C), gwide(w.nst * w.nrt, d.C);
     // Large wide ensembles (the fat drift kernel): the step's noise is drawn by extra blocks of the three small launches in front
     // of the drift kernel -- norm, cdf and the ancestor search need a few dozen workgroups each and leave the chip empty --
     // instead of a launch of its own (~10 us per step at 10 000 particles).
@@ -3775,119 +3788,141 @@ int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
     // launches, row sums in its tail, no k_lgw_lse) from ~700 tiled workgroups per launch: d = 100, 4 chains in two groups:
     // 2000 particles 8.6 against 9.3 ms per sweep, 4000: 9.2 against 11.4; 1000: 8.4 against 7.8.
     constexpr int64_t kFatMin = 700;
-    const bool fat = d.wide && (int64_t)gwide.x * d.C > kFatMin;
+    const bool fat = (int64_t)gwide.x * d.C > kFatMin;
+    const bool fat_rowsum = fat && (d.D & 3) == 0 && (d.du & 3) == 0;   // the float4 kernel leaves the log-weights in d.lw
     LgDev dz = d;
     dim3 gz = gtile;
     if (fat) {
         const int64_t third = (((int64_t)d.N * d.du + 1) / 2 + 2) / 3;
-        const int64_t want = (third + kBlock - 1) / kBlock;
-        dz.nz = (int)(want < 1024 ? want : 1024);
+        dz.nz = grid_1d(third, kBlock, 1024);
         gz = dim3(gtile.x + dz.nz, gtile.y);
     }
-    for (int k = 0; !one_tile && k < d.T; ++k) {
-        {
-            ProfScope p(s, 0, st);
-            if (tree) k_lg_norm<1, 0, true><<<dim3(gtile.x * (d.pin ? 8 : 1), d.C), kBlock, 0, st>>>(d, k);
-            else LG_DISPATCH(s, (void)DMAX; (k_lg_norm<ITEMS, 0><<<gz, kBlock, 0, st>>>(dz, k)));
-        }
-        if (!tree) {
-            ProfScope p(s, 1, st);
-            LG_DISPATCH(s, (void)DMAX; (k_lg_cdf<ITEMS, 0><<<gz, kBlock, 0, st>>>(dz, k)));
-        }
-        {
-            ProfScope p(s, 2, st);
-            if (d.wide) {
-                k_lgw_anc<<<gz, kBlock, 0, st>>>(dz, k);
-                bool fat_rowsum = false;
-                if (fat) {
-                    const int nst = (d.N + kWideTile - 1) / kWideTile;
-                    fat_rowsum = (d.D & 3) == 0 && (d.du & 3) == 0;   // the float4 kernel leaves the log-weights in d.lw
-                    if (fat_rowsum)
-                        k_lgw_gemm_fat<true><<<dim3(nst, d.C), kBlock, w_lds, st>>>(d, k, w_nrt, w_Kp, w_S);
-                    else
-                        k_lgw_gemm_fat<false><<<dim3(nst, d.C), kBlock, w_lds, st>>>(d, k, w_nrt, w_Kp, w_S);
-                }
-                else
-                    k_lgw_gemm<0><<<gwide, kBlock, w_lds, st>>>(d, k, 0, w_nrt, w_Kp, w_S, 3, 0);
-                if (fat_rowsum) k_lg_lwpart<<<gtile, kBlock, 0, st>>>(d);   // tile partials of the log-weights the drift kernel left
-                else k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);
-            } else if (tree && two_slot && !d.plus1) {
-                LG_DISPATCH(s, (void)ITEMS; (k_lg_prop2t<DMAX><<<dim3(nb / 2, d.C), kBlock, 0, st>>>(d, k)));
-            } else if (tree && !d.plus1 && nb % 4 == 0 && (s->tree_halves == 4 || (s->tree_halves < 0 && (int64_t)nb * d.C >= 4 * 256))) {
-                // four tiles per 1024-thread workgroup once there are four tiles per CU (measured 8.57 against 8.80 ms per
-                // 4-chain sweep with two; a single chain is fastest with one tile per workgroup)
-                LG_DISPATCH(s, (void)ITEMS; (k_lg_prop1t<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k)));
-            } else if (tree && !d.plus1 && nb % 2 == 0 && (s->tree_halves == 2 || (s->tree_halves < 0 && (int64_t)nb * d.C >= 2 * 256))) {
-                // two adjacent tiles per 512-thread workgroup: half the waves skip the tree building (measured +2 % at 4 chains,
-                // -1 % for a single chain, which keeps one tile per workgroup)
-                LG_DISPATCH(s, (void)ITEMS; (k_lg_prop1t<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k)));
-            } else if (tree) {
-                LG_DISPATCH(s, (void)ITEMS; (k_lg_prop1t<DMAX, 1><<<dim3(gtile.x * (d.pin ? 8 : 1), d.C), kBlock, 0, st>>>(d, k)));
-            } else if (two_slot) {
-                LG_DISPATCH(s, (void)ITEMS; (k_lg_prop2<DMAX><<<dim3(nb / 2, d.C), kBlock, 0, st>>>(d, k)));
-            } else if (s->items == 1) {
-                LG_DISPATCH(s, (void)ITEMS; (k_lg_prop1<DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
-            } else {
-                // several slots per thread: compact heaps by their own small launch, then the batched kernel
-                k_lg_heaps<<<dim3(kHeapSizeW / kBlock, d.C), kBlock, 0, st>>>(d);
-                LG_DISPATCH(s, (k_lg_propQ<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
-            }
+    for (int k = 0; k < d.T; ++k) {
+        step_norm_cdf(s, st, k, false, gz, dz);
+        ProfScope p(s, 2, st);
+        k_lgw_anc<<<gz, kBlock, 0, st>>>(dz, k);
+        if (fat_rowsum) k_lgw_gemm_fat<true><<<dim3(w.nst, d.C), kBlock, w.lds, st>>>(d, k, w.nrt, w.Kp, w.S);
+        else if (fat) k_lgw_gemm_fat<false><<<dim3(w.nst, d.C), kBlock, w.lds, st>>>(d, k, w.nrt, w.Kp, w.S);
+        else k_lgw_gemm<0><<<gwide, kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3, 0);
+        if (fat_rowsum) k_lg_lwpart<<<gtile, kBlock, 0, st>>>(d);   // tile partials of the log-weights the drift kernel left
+        else k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);
+    }
+}
+
+// narrow, several tiles: two (tree), three or four (several slots per thread) launches per step
+void sweep_steps_narrow(fbsmi_lg_sweep* s, hipStream_t st) {
+    const LgDev& d = s->d;
+    const int nb = d.nb;
+    const dim3 gtile(nb, d.C);
+    // enough workgroups that instruction issue, not latency, bounds the step (measured crossover: between four and six
+    // 256-slot workgroups per CU): two slots per thread, three Threefry calls instead of six
+    const bool two_slot = s->items == 1 && d.N % (2 * kBlock) == 0 &&
+                          (s->two_slot_prop == 1 || (s->two_slot_prop < 0 && (int64_t)nb * d.C >= 5 * 256));
+    // N a power of two: the searches walk the summation tree, no cdf launch (k_lg_prop1t)
+    const bool tree = s->tree_step && d.trW;
+    for (int k = 0; k < d.T; ++k) {
+        step_norm_cdf(s, st, k, tree, gtile, d);
+        ProfScope p(s, 2, st);
+        if (tree && two_slot && !d.plus1) {
+            LG_DMAX(s, k_lg_prop2t<DMAX><<<dim3(nb / 2, d.C), kBlock, 0, st>>>(d, k));
+        } else if (tree && !d.plus1 && nb % 4 == 0 && (s->tree_halves == 4 || (s->tree_halves < 0 && (int64_t)nb * d.C >= 4 * 256))) {
+            // four tiles per 1024-thread workgroup once there are four tiles per CU (measured 8.57 against 8.80 ms per
+            // 4-chain sweep with two; a single chain is fastest with one tile per workgroup)
+            LG_DMAX(s, k_lg_prop1t<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k));
+        } else if (tree && !d.plus1 && nb % 2 == 0 && (s->tree_halves == 2 || (s->tree_halves < 0 && (int64_t)nb * d.C >= 2 * 256))) {
+            // two adjacent tiles per 512-thread workgroup: half the waves skip the tree building (measured +2 % at 4 chains,
+            // -1 % for a single chain, which keeps one tile per workgroup)
+            LG_DMAX(s, k_lg_prop1t<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k));
+        } else if (tree) {
+            LG_DMAX(s, k_lg_prop1t<DMAX, 1><<<dim3(nb * (d.pin ? 8 : 1), d.C), kBlock, 0, st>>>(d, k));
+        } else if (two_slot) {
+            LG_DMAX(s, k_lg_prop2<DMAX><<<dim3(nb / 2, d.C), kBlock, 0, st>>>(d, k));
+        } else if (s->items == 1) {
+            LG_DMAX(s, k_lg_prop1<DMAX><<<gtile, kBlock, 0, st>>>(d, k));
+        } else {
+            // several slots per thread: compact heaps by their own small launch, then the batched kernel
+            k_lg_heaps<<<dim3(kHeapSizeW / kBlock, d.C), kBlock, 0, st>>>(d);
+            LG_ITEMS(s, LG_DMAX(s, k_lg_propQ<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
         }
     }
+}
+
+// the backward pass (explicit: force-move tail and a second forward path; else backward scanning), parity view, chain step
+void sweep_epilogue(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
+    const LgDev& d = s->d;
+    const dim3 gone(1, d.C), gtile(d.nb, d.C);
     if (d.eb) {
-        LG_DISPATCH(s, (void)DMAX; (k_lg_norm<ITEMS, 1><<<gtile, kBlock, 0, st>>>(d, d.T)));
-        LG_DISPATCH(s, (void)DMAX; (k_lg_cdf<ITEMS, 1><<<gtile, kBlock, 0, st>>>(d, d.T)));
+        LG_ITEMS(s, k_lg_norm<ITEMS, 1><<<gtile, kBlock, 0, st>>>(d, d.T));
+        LG_ITEMS(s, k_lg_cdf<ITEMS, 1><<<gtile, kBlock, 0, st>>>(d, d.T));
         k_lg_force_move<<<gone, 64, 0, st>>>(d);
-        if (s->em) k_lg_em_path<<<dim3(1, d.C), em_block, 0, st>>>(d, s->emd, 1);
+        const int gpath = (d.D + 63) / 64;
+        if (s->em) k_lg_em_path<<<dim3(1, d.C), (unsigned)((d.D + 63) / 64 * 64), 0, st>>>(d, s->emd, 1);
         else k_lg_path<<<dim3(gpath > (d.T + 64) / 64 ? gpath : (d.T + 64) / 64, d.C), 64, 0, st>>>(d, 1);
     } else {
-        LG_DISPATCH(s, (void)DMAX; (k_lg_norm<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T)));
-        LG_DISPATCH(s, (void)DMAX; (k_lg_cdf<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T)));
+        LG_ITEMS(s, k_lg_norm<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T));
+        LG_ITEMS(s, k_lg_cdf<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T));
         k_lg_backscan<<<gone, 256, 0, st>>>(d);
     }
-    {
-        const int64_t n = (int64_t)d.N * d.du;
-        int g = (int)((n + 255) / 256);
-        g = g < 1 ? 1 : (g > 2048 ? 2048 : g);
-        k_lg_export<<<dim3(g, d.C), 256, 0, st>>>(d);
-    }
+    k_lg_export<<<dim3(grid_1d((int64_t)d.N * d.du, 256, 2048), d.C), 256, 0, st>>>(d);
     if (chain) {
         k_lg_advance<<<gone, 256, 0, st>>>(d);
         k_lg_advance_key<<<1, 64, 0, st>>>(d);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString(e));
-    return FBSMI_OK;
 }
 
-int get_graph(fbsmi_lg_sweep* s, int chain, hipGraphExec_t* out) {
-    hipGraphExec_t& slot = chain ? s->graph_chain : s->graph_single;
+int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
+    const LgDev& d = s->d;
+    const WideGeom w(d);
+    sweep_prologue(s, st, chain, w);
+    if (d.N <= kBlock) {
+        if (d.wide || s->profile) sweep_one_tile_stepwise(s, st, w);
+        else sweep_one_tile_persistent(s, st);
+        // log-weights / tile partial for the final-mode kernels
+        if (d.wide) k_lgw_lse<<<dim3(d.nb, d.C), kBlock, 0, st>>>(d);
+        else k_lg_lwpart<<<dim3(d.nb, d.C), kBlock, 0, st>>>(d);
+    } else if (d.wide) sweep_steps_wide(s, st, w);
+    else sweep_steps_narrow(s, st);
+    sweep_epilogue(s, st, chain);
+    return launch_status("sweep");
+}
+
+// Run `enqueue` on st: directly, or (use_graph) as a graph captured on first use into `slot` and replayed from then on.
+template <typename Enqueue>
+int launch_captured(hipGraphExec_t& slot, hipStream_t st, bool use_graph, Enqueue&& enqueue) {
+    if (!use_graph) return enqueue();
     if (!slot) {
         hipGraph_t g = nullptr;
-        FBSMI_HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed));
-        int rc = enqueue_sweep(s, s->stream, chain);
-        hipError_t e = hipStreamEndCapture(s->stream, &g);
-        if (rc) {
-            if (g) hipGraphDestroy(g);
-            return rc;
-        }
-        if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        FBSMI_HIP_TRY(hipGraphInstantiate(&slot, g, nullptr, nullptr, 0));
-        FBSMI_HIP_TRY(hipGraphDestroy(g));
+        FBSMI_HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+        int rc = enqueue();
+        hipError_t e = hipStreamEndCapture(st, &g);
+        if (!rc && e != hipSuccess) rc = fail(FBSMI_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+        if (!rc && (e = hipGraphInstantiate(&slot, g, nullptr, nullptr, 0)) != hipSuccess)
+            rc = fail(FBSMI_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+        if (g) (void)hipGraphDestroy(g);
+        if (rc) return rc;
     }
-    *out = slot;
+    FBSMI_HIP_TRY(hipGraphLaunch(slot, st));
     return FBSMI_OK;
 }
 
 int run_sweep(fbsmi_lg_sweep* s, int chain, int use_graph) {
-    if (use_graph && !s->profile) {
-        hipGraphExec_t g;
-        int rc = get_graph(s, chain, &g);
-        if (rc) return rc;
-        FBSMI_HIP_TRY(hipGraphLaunch(g, s->stream));
-        return FBSMI_OK;
-    }
-    return enqueue_sweep(s, s->stream, chain);
+    // (no graph while profiling: ProfScope's events belong between the launches)
+    return launch_captured(chain ? s->graph_chain : s->graph_single, s->stream, use_graph && !s->profile,
+                           [&] { return enqueue_sweep(s, s->stream, chain); });
+}
+
+// A call's work runs on the handle's own stream between join_in and join_out: it starts after what the caller's stream `ust`
+// holds so far, and what the caller queues afterwards starts after it.
+int join_in(fbsmi_lg_sweep* s, hipStream_t ust) {
+    FBSMI_HIP_TRY(hipEventRecord(s->ev_in, ust));
+    FBSMI_HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_in, 0));
+    return FBSMI_OK;
+}
+
+int join_out(fbsmi_lg_sweep* s, hipStream_t ust) {
+    FBSMI_HIP_TRY(hipEventRecord(s->ev_out, s->stream));
+    FBSMI_HIP_TRY(hipStreamWaitEvent(ust, s->ev_out, 0));
+    return FBSMI_OK;
 }
 
 int collect_profile(fbsmi_lg_sweep* s) {
@@ -3929,6 +3964,11 @@ int fbsmi_lg_sweep_create(const fbsmi_lg_model* m, int32_t nparticles, int expli
         return fail(FBSMI_ERR_ARG, "lg_sweep_create: explicit_backward=0 needs store_path (As, uss)");
     fbsmi_lg_sweep* s = new (std::nothrow) fbsmi_lg_sweep();
     if (!s) return fail(FBSMI_ERR_ARG, "out of host memory");
+    // the one failure exit from here on (fbsmi_lg_sweep_destroy takes a half-built handle)
+    auto bail = [s](int code, const std::string& msg) {
+        fbsmi_lg_sweep_destroy(s);
+        return fail(code, msg);
+    };
     LgDev& d = s->d;
     d.C = nchains;
     d.Ctot = nchains;
@@ -3947,104 +3987,91 @@ int fbsmi_lg_sweep_create(const fbsmi_lg_model* m, int32_t nparticles, int expli
     d.G = m->G; d.g = m->g; d.sd = m->sd; d.lognorm = m->lognorm; d.F = m->F; d.sqQ = m->sqQ;
     d.levels = bisect_levels(d.N);
     d.wide = wide ? 1 : 0;
-    d.lpw = nullptr;
     read_switches(s);
     s->items = fbsmi_tile_items(d.N);  // one workgroup = one tile of the two-level logsumexp (include/fbsmi_math.h)
     const int maxd = m->du > m->dv ? m->du : m->dv;
     s->dmax = maxd <= 1 ? 1 : (maxd <= 2 ? 2 : (maxd <= 4 ? 4 : 16));   // du = dv = 1 (BASELINE configs 1, 2) has its own instantiation
     const int tile = kBlock * s->items;
     d.nb = (d.N + tile - 1) / tile;
-    if (d.nb > kMaxNbSweep) {
-        delete s;
-        return fail(FBSMI_ERR_UNSUPPORTED, "lg_sweep: more than 4M particles per device not supported yet");
-    }
+    if (d.nb > kMaxNbSweep) return bail(FBSMI_ERR_UNSUPPORTED, "lg_sweep: more than 4M particles per device not supported yet");
     if (store_path) {
         const double bytes = (((double)d.T * d.N * 4.0) + ((double)(d.T + 1) * d.N * (d.du + 1) * 4.0)) * nchains;
-        if (bytes > 200e9) {
-            delete s;
-            return fail(FBSMI_ERR_UNSUPPORTED, "lg_sweep: path storage (T,N,du) does not fit device memory");
-        }
+        if (bytes > 200e9) return bail(FBSMI_ERR_UNSUPPORTED, "lg_sweep: path storage (T,N,du) does not fit device memory");
     }
     const size_t N = d.N, T = d.T, C = nchains;
-    int rc = 0;
-    rc |= slab_request(s, &d.key, 2);
-    rc |= slab_request(s, &d.keys, 2 * C);
-    rc |= slab_request(s, &d.x0, C * d.du);
-    rc |= slab_request(s, &d.y0, d.dv);
-    rc |= slab_request(s, &d.bs, C * (T + 1));
-    rc |= slab_request(s, &d.keytab, C * 8 * T);
-    rc |= slab_request(s, &d.misc, C * 16);
-    rc |= slab_request(s, &d.xi1, C * T * D);
-    rc |= slab_request(s, &d.xi2, C * T * D);
-    rc |= slab_request(s, &d.path, 1);
-    rc |= slab_request(s, &d.us_star, C * (T + 1) * d.du);
-    rc |= slab_request(s, &d.vs, C * (T + 1) * d.dv);
-    rc |= slab_request(s, &d.u0, C * N * d.du);
-    rc |= slab_request(s, &d.u1, C * N * d.du);
-    rc |= slab_request(s, &d.lw, C * N);
-    rc |= slab_request(s, &d.lwn, C * N);
-    rc |= slab_request(s, &d.w, C * N);
-    rc |= slab_request(s, &d.cdf, C * N);
-    rc |= slab_request(s, &d.cdfJ, C * N);
-    rc |= slab_request(s, &d.bmax, C * d.nb);
-    rc |= slab_request(s, &d.bsumexp, C * d.nb);
-    d.anc = nullptr;
-    d.xiw = nullptr;
-    d.uw = nullptr;
+    Slab slab;
+    slab.request(&d.key, 2);
+    slab.request(&d.keys, 2 * C);
+    slab.request(&d.x0, C * d.du);
+    slab.request(&d.y0, d.dv);
+    slab.request(&d.bs, C * (T + 1));
+    slab.request(&d.keytab, C * 8 * T);
+    slab.request(&d.misc, C * 16);
+    slab.request(&d.xi1, C * T * D);
+    slab.request(&d.xi2, C * T * D);
+    slab.request(&d.path, 1);
+    slab.request(&d.us_star, C * (T + 1) * d.du);
+    slab.request(&d.vs, C * (T + 1) * d.dv);
+    slab.request(&d.u0, C * N * d.du);
+    slab.request(&d.u1, C * N * d.du);
+    slab.request(&d.lw, C * N);
+    slab.request(&d.lwn, C * N);
+    slab.request(&d.w, C * N);
+    slab.request(&d.cdf, C * N);
+    slab.request(&d.cdfJ, C * N);
+    slab.request(&d.bmax, C * d.nb);
+    slab.request(&d.bsumexp, C * d.nb);
     if (wide) {
-        rc |= slab_request(s, &d.lpw, C * (size_t)((d.dv + 3) & ~3) * N);
-        rc |= slab_request(s, &d.anc, C * N);
-        rc |= slab_request(s, &d.xiw, 2 * C * N * d.du);
-        if (N <= kBlock) rc |= slab_request(s, &d.uw, 4 * C * (size_t)N);
+        slab.request(&d.lpw, C * (size_t)((d.dv + 3) & ~3) * N);
+        slab.request(&d.anc, C * N);
+        slab.request(&d.xiw, 2 * C * N * d.du);
+        if (N <= kBlock) slab.request(&d.uw, 4 * C * (size_t)N);
     }
-    d.hpW = d.hpJ = nullptr;
-    d.hp_map = nullptr;
     int32_t* hp_map_dev = nullptr;
-    d.lh_w = d.lh_j = 0;
     if (!wide) {   // compact bisection heaps: written by k_lg_cdf itself (one slot per thread, through hp_map) or by k_lg_heaps
         int fl = 0;
         while ((2ll << fl) <= (long long)d.N) ++fl;   // floor(log2 N)
         d.lh_w = fl < kHeapLevelsW ? fl : kHeapLevelsW;
         d.lh_j = fl < kHeapLevelsJ ? fl : kHeapLevelsJ;
-        if (s->items == 1) rc |= slab_request(s, &hp_map_dev, (size_t)N);
-        rc |= slab_request(s, &d.hpW, C * (size_t)kHeapSizeW);
-        rc |= slab_request(s, &d.hpJ, C * (size_t)kHeapSizeJ);
+        if (s->items == 1) slab.request(&hp_map_dev, (size_t)N);
+        slab.request(&d.hpW, C * (size_t)kHeapSizeW);
+        slab.request(&d.hpJ, C * (size_t)kHeapSizeJ);
     }
-    d.trW = d.trWtop = nullptr;
-    d.wfirst = nullptr;
     const bool pow2 = (d.N & (d.N - 1)) == 0 && d.nb >= 2 && d.nb <= kBlock;
     // N = 2^k + 1 (explicit_final on a power-of-two ensemble): the same step over the first 2^k slots' tree plus an extra
     // one-slot tile (tree_build)
     const bool pow2p1 = d.N > 2 && ((d.N - 1) & (d.N - 2)) == 0 && d.nb - 1 >= 2 && d.nb - 1 <= kBlock && s->tree_plus1;
-    d.plus1 = 0;
     if (s->items == 1 && !wide && (pow2 || pow2p1)) {
         d.plus1 = pow2 ? 0 : 1;
-        rc |= slab_request(s, &d.trW, C * (size_t)kTreeNodes * d.nb);
-        rc |= slab_request(s, &d.trWtop, C * (size_t)kMidN * d.nb);
-        rc |= slab_request(s, &d.wfirst, C * (size_t)d.nb);
+        slab.request(&d.trW, C * (size_t)kTreeNodes * d.nb);
+        slab.request(&d.trWtop, C * (size_t)kMidN * d.nb);
+        slab.request(&d.wfirst, C * (size_t)d.nb);
         // few workgroups per launch (BASELINE config 1: 4 tiles; up to 64 workgroups): keep the step on one XCD.  Only with the default kernel
         // choices (one tile per workgroup, one slot per thread), which is what such sizes get.  FBSMI_PIN=0 turns it off.
         constexpr int64_t kPinMax = 64;   // workgroups per launch; two per CU of the XCD: measured better up to there, worse beyond
         d.pin = (s->pin && !d.plus1 && s->tree_step && s->tree_halves < 0 && s->two_slot_prop < 0 && (int64_t)d.nb * C <= kPinMax) ? 1 : 0;
         if (d.pin && !xcd_round_robin_holds()) d.pin = 0;   // the dispatch order the pinning rests on is not what this machine does
     }
-    rc |= slab_request(s, &d.bsumw, C * d.nb);
-    rc |= slab_request(s, &d.bsumJ, C * d.nb);
-    rc |= slab_request(s, &d.scal, C * 16);
-    rc |= slab_request(s, &d.usT, C * N * d.du);
-    rc |= slab_request(s, &d.x0n, C * d.du);
-    rc |= slab_request(s, &d.usn, C * (T + 1) * d.du);
-    rc |= slab_request(s, &d.bsn, C * (T + 1));
-    rc |= slab_request(s, &d.acc, C * (T + 1));
-    rc |= slab_request(s, &d.x0s_slot, 1);
-    rc |= slab_request(s, &d.counter, 1);
+    slab.request(&d.bsumw, C * d.nb);
+    slab.request(&d.bsumJ, C * d.nb);
+    slab.request(&d.scal, C * 16);
+    slab.request(&d.usT, C * N * d.du);
+    slab.request(&d.x0n, C * d.du);
+    slab.request(&d.usn, C * (T + 1) * d.du);
+    slab.request(&d.bsn, C * (T + 1));
+    slab.request(&d.acc, C * (T + 1));
+    slab.request(&d.x0s_slot, 1);
+    slab.request(&d.counter, 1);
     if (store_path) {
-        rc |= slab_request(s, &d.As, C * T * N);
-        rc |= slab_request(s, &d.uss, C * (T + 1) * N * d.du);
-        rc |= slab_request(s, &d.lwss, C * (T + 1) * N);
+        slab.request(&d.As, C * T * N);
+        slab.request(&d.uss, C * (T + 1) * N * d.du);
+        slab.request(&d.lwss, C * (T + 1) * N);
     }
-    rc |= slab_commit(s);
-    if (!rc && hp_map_dev) {
+    void* base = nullptr;
+    hipError_t e = slab.commit(&base);
+    if (base) s->allocs.push_back(base);
+    if (e != hipSuccess) return bail(FBSMI_ERR_HIP, std::string("lg_sweep_create: device allocation: ") + hipGetErrorString(e));
+    if (hp_map_dev) {
         // Down to depth floor(log2 N) every node of the implicit bisection tree is at least two wide, so an
         // element is the midpoint of at most one node there: walk the tree once, on the host.
         std::vector<int32_t> map((size_t)d.N, 0);
@@ -4059,34 +4086,25 @@ int fbsmi_lg_sweep_create(const fbsmi_lg_model* m, int32_t nparticles, int expli
             stack.push_back({n.lo, mid, 2 * n.t, n.dep + 1});
             stack.push_back({mid, n.hi, 2 * n.t + 1, n.dep + 1});
         }
-        if (hipMemcpy(hp_map_dev, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice) != hipSuccess) rc = 1;
+        e = hipMemcpy(hp_map_dev, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return bail(FBSMI_ERR_HIP, std::string("lg_sweep_create: heap map upload: ") + hipGetErrorString(e));
         d.hp_map = hp_map_dev;
-    }
-    if (rc) {
-        fbsmi_lg_sweep_destroy(s);
-        return FBSMI_ERR_HIP;
     }
     (void)xcd_round_robin_holds();   // the once-per-process placement probe must not run inside a later stream capture
     if ((s->stream = pool_stream(0)) == nullptr ||
         hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_out, hipEventDisableTiming) != hipSuccess) {
-        fbsmi_lg_sweep_destroy(s);
-        return fail(FBSMI_ERR_HIP, "lg_sweep_create: stream/event creation failed");
-    }
+        hipEventCreateWithFlags(&s->ev_out, hipEventDisableTiming) != hipSuccess)
+        return bail(FBSMI_ERR_HIP, "lg_sweep_create: stream/event creation failed");
     if (wide) {
         // The attribute belongs to the function, not to the handle: always ask for the largest tile pair any model can
         // need (D = 256), or a later handle with a smaller model would lower the limit under an earlier one.
         const int lds = (int)wide_lds_bytes(wide_plane_row(256));
-        hipError_t e = hipFuncSetAttribute((const void*)k_lgw_gemm<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_lgw_gemm<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_lgw_gemm<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_lgw_gemm<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_lgw_gemm<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_lgw_gemm_fat<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_lgw_gemm_fat<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            fbsmi_lg_sweep_destroy(s);
-            return fail(FBSMI_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
+        const void* const gemms[] = {(const void*)k_lgw_gemm<0>, (const void*)k_lgw_gemm<1>, (const void*)k_lgw_gemm<2>,
+                                     (const void*)k_lgw_gemm<3>, (const void*)k_lgw_gemm<4>,
+                                     (const void*)k_lgw_gemm_fat<true>, (const void*)k_lgw_gemm_fat<false>};
+        for (const void* fn : gemms) {
+            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            if (e != hipSuccess) return bail(FBSMI_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
         }
     }
     *out = s;
@@ -4114,25 +4132,20 @@ int fbsmi_lg_gibbs_sweep(fbsmi_lg_sweep* s, const uint32_t* keys, const float* x
     hipStream_t ust = (hipStream_t)stream;
     const LgDev& d = s->d;
     const size_t C = d.C, T1 = d.T + 1;
-    FBSMI_HIP_TRY(hipEventRecord(s->ev_in, ust));
-    FBSMI_HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_in, 0));
+    if (int rc = join_in(s, ust)) return rc;
     FBSMI_HIP_TRY(hipMemcpyAsync(d.keys, keys, C * 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(d.x0, x0, C * d.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(d.y0, y0, d.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(d.bs, bs_star, C * T1 * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
-    int rc = run_sweep(s, 0, use_graph);
-    if (rc) return rc;
+    if (int rc = run_sweep(s, 0, use_graph)) return rc;
     if (x0_next) FBSMI_HIP_TRY(hipMemcpyAsync(x0_next, d.x0n, C * d.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     if (us_star_next)
         FBSMI_HIP_TRY(hipMemcpyAsync(us_star_next, d.usn, C * T1 * d.du * sizeof(float), hipMemcpyDeviceToDevice,
                                      s->stream));
     if (bs_next) FBSMI_HIP_TRY(hipMemcpyAsync(bs_next, d.bsn, C * T1 * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
     if (acc) FBSMI_HIP_TRY(hipMemcpyAsync(acc, d.acc, C * T1, hipMemcpyDeviceToDevice, s->stream));
-    rc = collect_profile(s);
-    if (rc) return rc;
-    FBSMI_HIP_TRY(hipEventRecord(s->ev_out, s->stream));
-    FBSMI_HIP_TRY(hipStreamWaitEvent(ust, s->ev_out, 0));
-    return FBSMI_OK;
+    if (int rc = collect_profile(s)) return rc;
+    return join_out(s, ust);
 }
 
 namespace {
@@ -4141,8 +4154,7 @@ int chain_begin(fbsmi_lg_sweep* s, const uint32_t* key, const float* x0, const f
                 hipStream_t ust) {
     const LgDev& d = s->d;
     const size_t C = d.C, T1 = d.T + 1;
-    FBSMI_HIP_TRY(hipEventRecord(s->ev_in, ust));
-    FBSMI_HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_in, 0));
+    if (int rc = join_in(s, ust)) return rc;
     FBSMI_HIP_TRY(hipMemcpyAsync(d.key, key, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(d.x0, x0, C * d.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(d.y0, y0, d.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
@@ -4160,11 +4172,8 @@ int chain_end(fbsmi_lg_sweep* s, uint32_t* key, float* x0, int32_t* bs_star, hip
     if (key) FBSMI_HIP_TRY(hipMemcpyAsync(key, d.key, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(x0, d.x0, C * d.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(bs_star, d.bs, C * T1 * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
-    int rc = collect_profile(s);
-    if (rc) return rc;
-    FBSMI_HIP_TRY(hipEventRecord(s->ev_out, s->stream));
-    FBSMI_HIP_TRY(hipStreamWaitEvent(ust, s->ev_out, 0));
-    return FBSMI_OK;
+    if (int rc = collect_profile(s)) return rc;
+    return join_out(s, ust);
 }
 }  // namespace
 
@@ -4172,12 +4181,9 @@ int fbsmi_lg_gibbs_chain(fbsmi_lg_sweep* s, uint32_t* key, float* x0, const floa
                          int32_t nsweeps, float* x0s, int use_graph, void* stream) {
     if (!s || !key || !x0 || !y0 || !bs_star || nsweeps < 0) return fail(FBSMI_ERR_ARG, "lg_gibbs_chain: bad arguments");
     hipStream_t ust = (hipStream_t)stream;
-    int rc = chain_begin(s, key, x0, y0, bs_star, x0s, ust);
-    if (rc) return rc;
-    for (int i = 0; i < nsweeps; ++i) {
-        rc = run_sweep(s, 1, use_graph);
-        if (rc) return rc;
-    }
+    if (int rc = chain_begin(s, key, x0, y0, bs_star, x0s, ust)) return rc;
+    for (int i = 0; i < nsweeps; ++i)
+        if (int rc = run_sweep(s, 1, use_graph)) return rc;
     return chain_end(s, key, x0, bs_star, ust);
 }
 
@@ -4226,20 +4232,16 @@ int fbsmi_lg_gibbs_chain_groups(fbsmi_lg_sweep* const* groups, int32_t ngroups, 
     for (int g = 0; g < ngroups; ++g) {
         fbsmi_lg_sweep* s = groups[g];
         const size_t c0 = s->d.c0;
-        int rc = chain_begin(s, key, x0 + c0 * s->d.du, y0, bs_star + c0 * (s->d.T + 1), x0s, ust);
-        if (rc) return rc;
+        if (int rc = chain_begin(s, key, x0 + c0 * s->d.du, y0, bs_star + c0 * (s->d.T + 1), x0s, ust)) return rc;
     }
     // sweeps outermost: every group's stream always has work queued, and the groups' launches interleave on the GPU
     for (int i = 0; i < nsweeps; ++i)
-        for (int g = 0; g < ngroups; ++g) {
-            int rc = run_sweep(groups[g], 1, use_graph);
-            if (rc) return rc;
-        }
+        for (int g = 0; g < ngroups; ++g)
+            if (int rc = run_sweep(groups[g], 1, use_graph)) return rc;
     for (int g = 0; g < ngroups; ++g) {
         fbsmi_lg_sweep* s = groups[g];
         const size_t c0 = s->d.c0;
-        int rc = chain_end(s, g == 0 ? key : nullptr, x0 + c0 * s->d.du, bs_star + c0 * (s->d.T + 1), ust);
-        if (rc) return rc;
+        if (int rc = chain_end(s, g == 0 ? key : nullptr, x0 + c0 * s->d.du, bs_star + c0 * (s->d.T + 1), ust)) return rc;
     }
     return FBSMI_OK;
 }
@@ -4279,109 +4281,115 @@ struct fbsmi_lg_filter {
 
 namespace {
 
+// ---- the launch sequence of one filter run on stream st (after k_filt_keys), by regime ---------
+
+// narrow, one tile: the whole filter is one launch
+void filter_narrow_one_launch(fbsmi_lg_filter* f, hipStream_t st) {
+    fbsmi_lg_sweep* s = f->core;
+    const LgDev& d = s->d;
+    LG_DMAX(s, k_filt_sweep1<DMAX><<<dim3(1, d.C), kBlock, 0, st>>>(d, f->u0s));
+}
+
+// wide, several logsumexp tiles: the prologue of a step is its own launches (row sums + partials, normalise, cumsum,
+// ancestors), the drift product takes the ancestors from d.anc
+void filter_wide_tiles(fbsmi_lg_filter* f, hipStream_t st, const WideGeom& w) {
+    const LgDev& d = f->core->d;
+    const dim3 gtile(d.nb, d.C);
+    const dim3 gall(w.nst * w.nrt, d.C), gu(w.nst * w.u_tiles, d.C), gv(w.nst * w.v_tiles(), d.C), gg(64, d.C);
+    auto resample = [&](int kres) {
+        k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);
+        k_filt_norm<1><<<gtile, kBlock, 0, st>>>(d);
+        k_lg_cdf<1, 2><<<gtile, kBlock, 0, st>>>(d, d.T);
+        k_lgwf_anc<<<gtile, kBlock, 0, st>>>(d, kres);
+    };
+    k_lgwf_init<<<dim3(8, d.C), kBlock, 0, st>>>(d, f->u0s);
+    if (d.flow == 0) {
+        k_lgw_gemm<3><<<gall, kBlock, w.lds, st>>>(d, 0, 0, w.nrt, w.Kp, w.S, 3, 0);
+        for (int k = 1; k < d.T; ++k) {
+            resample(k - 1);
+            k_lgw_gemm<4><<<gall, kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3, 0);
+        }
+        resample(d.T - 1);
+        k_lgwf_gather<<<gg, kBlock, 0, st>>>(d);
+    } else {
+        k_lgw_gemm<3><<<gv, kBlock, w.lds, st>>>(d, 0, w.v_tile0, w.v_tiles(), w.Kp, w.S, 2, 0);
+        for (int k = 0; k < d.T; ++k) {
+            resample(k);
+            k_lgw_gemm<4><<<gu, kBlock, w.lds, st>>>(d, k, 0, w.u_tiles, w.Kp, w.S, 1, 0);
+            if (k + 1 < d.T) k_lgw_gemm<3><<<gv, kBlock, w.lds, st>>>(d, k + 1, w.v_tile0, w.v_tiles(), w.Kp, w.S, 2, 0);
+        }
+    }
+}
+
+// wide, one tile (N <= 256): a launch = [filter prologue +] drift product.  A step's launches are a few dozen workgroups --
+// pinned to one XCD (bit 8 of `emit`, grids 8x wide)
+void filter_wide_one_tile(fbsmi_lg_filter* f, hipStream_t st, const WideGeom& w) {
+    fbsmi_lg_sweep* s = f->core;
+    const LgDev& d = s->d;
+    const bool pinw = s->wide_pin && xcd_round_robin_holds() && d.C == 1 && w.nst * w.nrt <= 32;
+    const int pe = pinw ? 0x100 : 0, pg = pinw ? 8 : 1;
+    const dim3 gall(w.nst * w.nrt * pg, d.C), gu(w.nst * w.u_tiles * pg, d.C), gv(w.nst * w.v_tiles() * pg, d.C);
+    k_lgwf_init<<<dim3(8, d.C), kBlock, 0, st>>>(d, f->u0s);
+    if (d.flow == 0) {
+        for (int k = 0; k < d.T; ++k) {
+            if (k == 0) k_lgw_gemm<3><<<gall, kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3 | pe, 0);
+            else k_lgw_gemm<2><<<gall, kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3 | pe, k - 1);
+        }
+        k_lgwf_final<<<dim3(1, d.C), kBlock, 0, st>>>(d);
+    } else {
+        // weight the current particles (rows >= du, no resampling), then resample + propagate (rows < du)
+        k_lgw_gemm<3><<<gv, kBlock, w.lds, st>>>(d, 0, w.v_tile0, w.v_tiles(), w.Kp, w.S, 2 | pe, 0);
+        for (int k = 0; k < d.T; ++k) {
+            k_lgw_gemm<2><<<gu, kBlock, w.lds, st>>>(d, k, 0, w.u_tiles, w.Kp, w.S, 1 | pe, k);
+            if (k + 1 < d.T) k_lgw_gemm<3><<<gv, kBlock, w.lds, st>>>(d, k + 1, w.v_tile0, w.v_tiles(), w.Kp, w.S, 2 | pe, 0);
+        }
+    }
+}
+
+// narrow, N a power of two with 2..256 tiles: the searches walk the summation tree, a step is two launches (no cdf)
+void filter_narrow_tree(fbsmi_lg_filter* f, hipStream_t st) {
+    fbsmi_lg_sweep* s = f->core;
+    const LgDev& d = s->d;
+    const dim3 gtile(d.nb, d.C);
+    const dim3 gpin(gtile.x * (d.pin ? 8 : 1), d.C);   // (pinned to one XCD when the launches are small: LgDev.pin)
+    LG_ITEMS(s, LG_DMAX(s, k_filt_init<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, f->u0s)));
+    for (int k = 0; k < d.T; ++k) {
+        if (d.flow == 0) LG_DMAX(s, k_filt_prop1t<DMAX><<<gpin, kBlock, 0, st>>>(d, k, k > 0, k > 0 ? k - 1 : 0, 1, 1));
+        k_filt_norm<1, true><<<gpin, kBlock, 0, st>>>(d);
+        if (d.flow == 1) LG_DMAX(s, k_filt_prop1t<DMAX><<<gpin, kBlock, 0, st>>>(d, k, 1, k, k + 1 < d.T ? 2 : 0, 1));
+    }
+    if (d.flow == 0) LG_DMAX(s, k_filt_prop1t<DMAX><<<gpin, kBlock, 0, st>>>(d, d.T, 1, d.T - 1, 0, 0));
+}
+
+// narrow, any other size: normalise, cdf, propagate
+void filter_narrow_general(fbsmi_lg_filter* f, hipStream_t st) {
+    fbsmi_lg_sweep* s = f->core;
+    const LgDev& d = s->d;
+    const dim3 gtile(d.nb, d.C);
+    LG_ITEMS(s, LG_DMAX(s, k_filt_init<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, f->u0s)));
+    for (int k = 0; k < d.T; ++k) {
+        if (d.flow == 0)
+            LG_ITEMS(s, LG_DMAX(s, k_filt_prop<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k, k > 0, k > 0 ? k - 1 : 0, 1, 1)));
+        LG_ITEMS(s, k_filt_norm<ITEMS><<<gtile, kBlock, 0, st>>>(d));
+        LG_ITEMS(s, k_lg_cdf<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T));
+        if (d.flow == 1)
+            LG_ITEMS(s, LG_DMAX(s, k_filt_prop<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k, 1, k, k + 1 < d.T ? 2 : 0, 1)));
+    }
+    if (d.flow == 0) LG_ITEMS(s, LG_DMAX(s, k_filt_prop<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, d.T, 1, d.T - 1, 0, 0)));
+}
+
 int enqueue_filter(fbsmi_lg_filter* f, hipStream_t st) {
     fbsmi_lg_sweep* s = f->core;
     const LgDev& d = s->d;
-    const dim3 gone(1, d.C), gtile(d.nb, d.C);
-    k_filt_keys<<<gone, kBlock, 0, st>>>(d);
-    if (!d.wide && d.N <= kBlock) {
-        LG_DISPATCH(s, (void)ITEMS; (k_filt_sweep1<DMAX><<<gone, kBlock, 0, st>>>(d, f->u0s)));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
-        return FBSMI_OK;
-    }
+    k_filt_keys<<<dim3(1, d.C), kBlock, 0, st>>>(d);
     if (d.wide) {
-        // N <= 256: a launch = [filter prologue +] drift product
-        const int nrt = (d.D + kWideTile - 1) / kWideTile, Kp = (d.D + 15) / 16 * 16, S = wide_plane_row(Kp);
-        const size_t lds = wide_lds_bytes(S);
-        const int nst = (d.N + kWideTile - 1) / kWideTile;
-        const int u_tiles = (d.du + kWideTile - 1) / kWideTile;   // row tiles holding rows < du
-        const int v_tile0 = d.du / kWideTile;                     // first row tile holding rows >= du
-        k_lgwf_init<<<dim3(8, d.C), kBlock, 0, st>>>(d, f->u0s);
-        if (d.N > kBlock) {
-            // several logsumexp tiles: the prologue is its own launches (row sums + partials, normalise, cumsum,
-            // ancestors), the drift product takes the ancestors from d.anc
-            const dim3 gall(nst * nrt, d.C), gu(nst * u_tiles, d.C), gv(nst * (nrt - v_tile0), d.C), gg(64, d.C);
-            auto resample = [&](int kres) {
-                k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);
-                k_filt_norm<1><<<gtile, kBlock, 0, st>>>(d);
-                k_lg_cdf<1, 2><<<gtile, kBlock, 0, st>>>(d, d.T);
-                k_lgwf_anc<<<gtile, kBlock, 0, st>>>(d, kres);
-            };
-            if (d.flow == 0) {
-                k_lgw_gemm<3><<<gall, kBlock, lds, st>>>(d, 0, 0, nrt, Kp, S, 3, 0);
-                for (int k = 1; k < d.T; ++k) {
-                    resample(k - 1);
-                    k_lgw_gemm<4><<<gall, kBlock, lds, st>>>(d, k, 0, nrt, Kp, S, 3, 0);
-                }
-                resample(d.T - 1);
-                k_lgwf_gather<<<gg, kBlock, 0, st>>>(d);
-            } else {
-                k_lgw_gemm<3><<<gv, kBlock, lds, st>>>(d, 0, v_tile0, nrt - v_tile0, Kp, S, 2, 0);
-                for (int k = 0; k < d.T; ++k) {
-                    resample(k);
-                    k_lgw_gemm<4><<<gu, kBlock, lds, st>>>(d, k, 0, u_tiles, Kp, S, 1, 0);
-                    if (k + 1 < d.T) k_lgw_gemm<3><<<gv, kBlock, lds, st>>>(d, k + 1, v_tile0, nrt - v_tile0, Kp, S, 2, 0);
-                }
-            }
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
-            return FBSMI_OK;
-        }
-        // one-tile ensembles: a step's launches are a few dozen workgroups -- pinned to one XCD (bit 8 of `emit`, grids 8x wide)
-        const bool pinw = s->wide_pin && xcd_round_robin_holds() && d.C == 1 && nst * nrt <= 32;
-        const int pe = pinw ? 0x100 : 0, pg = pinw ? 8 : 1;
-        if (d.flow == 0) {
-            for (int k = 0; k < d.T; ++k) {
-                if (k == 0) k_lgw_gemm<3><<<dim3(nst * nrt * pg, d.C), kBlock, lds, st>>>(d, k, 0, nrt, Kp, S, 3 | pe, 0);
-                else k_lgw_gemm<2><<<dim3(nst * nrt * pg, d.C), kBlock, lds, st>>>(d, k, 0, nrt, Kp, S, 3 | pe, k - 1);
-            }
-            k_lgwf_final<<<gone, kBlock, 0, st>>>(d);
-        } else {
-            // weight the current particles (rows >= du, no resampling), then resample + propagate (rows < du)
-            k_lgw_gemm<3><<<dim3(nst * (nrt - v_tile0) * pg, d.C), kBlock, lds, st>>>(d, 0, v_tile0, nrt - v_tile0, Kp, S, 2 | pe, 0);
-            for (int k = 0; k < d.T; ++k) {
-                k_lgw_gemm<2><<<dim3(nst * u_tiles * pg, d.C), kBlock, lds, st>>>(d, k, 0, u_tiles, Kp, S, 1 | pe, k);
-                if (k + 1 < d.T)
-                    k_lgw_gemm<3><<<dim3(nst * (nrt - v_tile0) * pg, d.C), kBlock, lds, st>>>(d, k + 1, v_tile0, nrt - v_tile0,
-                                                                                               Kp, S, 2 | pe, 0);
-            }
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
-        return FBSMI_OK;
-    }
-    LG_DISPATCH(s, (k_filt_init<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, f->u0s)));
-    // N a power of two with 2..256 tiles: the searches walk the summation tree, a step is two launches (no cdf)
-    const bool tree = s->tree_step && d.trW && s->items == 1 && !d.plus1;
-    if (tree) {
-        const dim3 gpin(gtile.x * (d.pin ? 8 : 1), d.C);   // (pinned to one XCD when the launches are small: LgDev.pin)
-        for (int k = 0; k < d.T; ++k) {
-            if (d.flow == 0)
-                LG_DISPATCH(s, (void)ITEMS; (k_filt_prop1t<DMAX><<<gpin, kBlock, 0, st>>>(d, k, k > 0, k > 0 ? k - 1 : 0, 1, 1)));
-            k_filt_norm<1, true><<<gpin, kBlock, 0, st>>>(d);
-            if (d.flow == 1)
-                LG_DISPATCH(s, (void)ITEMS; (k_filt_prop1t<DMAX><<<gpin, kBlock, 0, st>>>(d, k, 1, k, k + 1 < d.T ? 2 : 0, 1)));
-        }
-        if (d.flow == 0)
-            LG_DISPATCH(s, (void)ITEMS; (k_filt_prop1t<DMAX><<<gpin, kBlock, 0, st>>>(d, d.T, 1, d.T - 1, 0, 0)));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
-        return FBSMI_OK;
-    }
-    for (int k = 0; k < d.T; ++k) {
-        if (d.flow == 0)
-            LG_DISPATCH(s, (k_filt_prop<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k, k > 0, k > 0 ? k - 1 : 0, 1, 1)));
-        LG_DISPATCH(s, (void)DMAX; (k_filt_norm<ITEMS><<<gtile, kBlock, 0, st>>>(d)));
-        LG_DISPATCH(s, (void)DMAX; (k_lg_cdf<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T)));
-        if (d.flow == 1)
-            LG_DISPATCH(s, (k_filt_prop<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k, 1, k, k + 1 < d.T ? 2 : 0, 1)));
-    }
-    if (d.flow == 0)
-        LG_DISPATCH(s, (k_filt_prop<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, d.T, 1, d.T - 1, 0, 0)));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
-    return FBSMI_OK;
+        const WideGeom w(d);
+        if (d.N > kBlock) filter_wide_tiles(f, st, w);
+        else filter_wide_one_tile(f, st, w);
+    } else if (d.N <= kBlock) filter_narrow_one_launch(f, st);
+    else if (s->tree_step && d.trW && s->items == 1 && !d.plus1) filter_narrow_tree(f, st);
+    else filter_narrow_general(f, st);
+    return launch_status("filter");
 }
 
 }  // namespace
@@ -4430,34 +4438,16 @@ int fbsmi_lg_filter_run(fbsmi_lg_filter* f, const uint32_t* keys, const float* v
     if (path && !d.uss) return fail(FBSMI_ERR_ARG, "lg_filter_run: path requested but the filter was created without store_path");
     hipStream_t ust = (hipStream_t)stream;
     const size_t C = d.C, T1 = d.T + 1;
-    FBSMI_HIP_TRY(hipEventRecord(s->ev_in, ust));
-    FBSMI_HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_in, 0));
+    if (int rc = join_in(s, ust)) return rc;
     FBSMI_HIP_TRY(hipMemcpyAsync(d.keys, keys, C * 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(d.vs, vs, C * T1 * d.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(f->u0s, u0s, C * d.N * d.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-    if (use_graph) {
-        if (!f->graph) {
-            hipGraph_t g = nullptr;
-            FBSMI_HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed));
-            int rc = enqueue_filter(f, s->stream);
-            hipError_t e = hipStreamEndCapture(s->stream, &g);
-            if (rc) return rc;
-            if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-            FBSMI_HIP_TRY(hipGraphInstantiate(&f->graph, g, nullptr, nullptr, 0));
-            FBSMI_HIP_TRY(hipGraphDestroy(g));
-        }
-        FBSMI_HIP_TRY(hipGraphLaunch(f->graph, s->stream));
-    } else {
-        int rc = enqueue_filter(f, s->stream);
-        if (rc) return rc;
-    }
+    if (int rc = launch_captured(f->graph, s->stream, use_graph != 0, [&] { return enqueue_filter(f, s->stream); })) return rc;
     if (uT) FBSMI_HIP_TRY(hipMemcpyAsync(uT, d.usT, C * d.N * d.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     if (loglik) FBSMI_HIP_TRY(hipMemcpyAsync(loglik, d.ell, C * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     if (path)
         FBSMI_HIP_TRY(hipMemcpyAsync(path, d.uss, C * T1 * d.N * d.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-    FBSMI_HIP_TRY(hipEventRecord(s->ev_out, s->stream));
-    FBSMI_HIP_TRY(hipStreamWaitEvent(ust, s->ev_out, 0));
-    return FBSMI_OK;
+    return join_out(s, ust);
 }
 
 int fbsmi_lg_sweep_profile(fbsmi_lg_sweep* s, int enable) {
@@ -4493,33 +4483,15 @@ int enqueue_pmcmc(fbsmi_lg_pmcmc* h, hipStream_t st, int chain) {
     const PmDev& p = h->p;
     k_pm_propose<<<dim3(1, p.C), kPmBlock, 0, st>>>(p, chain);
     k_pm_u0<<<dim3((p.N + h->rows - 1) / h->rows, p.C), kBlock, 0, st>>>(p, h->rows, chain);
-    int rc = enqueue_filter(h->filt, st);
-    if (rc) return rc;
+    if (int rc = enqueue_filter(h->filt, st)) return rc;
     k_pm_accept<<<dim3(1, p.C), kBlock, 0, st>>>(p, chain);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("pmcmc launch: ") + hipGetErrorString(e));
-    return FBSMI_OK;
+    return launch_status("pmcmc");
 }
 
 int run_pmcmc(fbsmi_lg_pmcmc* h, int chain, int use_graph) {
     hipStream_t st = h->filt->core->stream;
-    if (!use_graph) return enqueue_pmcmc(h, st, chain);
-    hipGraphExec_t& slot = chain ? h->graph_chain : h->graph_step;
-    if (!slot) {
-        hipGraph_t g = nullptr;
-        FBSMI_HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-        int rc = enqueue_pmcmc(h, st, chain);
-        hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc) {
-            if (g) hipGraphDestroy(g);
-            return rc;
-        }
-        if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        FBSMI_HIP_TRY(hipGraphInstantiate(&slot, g, nullptr, nullptr, 0));
-        FBSMI_HIP_TRY(hipGraphDestroy(g));
-    }
-    FBSMI_HIP_TRY(hipGraphLaunch(slot, st));
-    return FBSMI_OK;
+    return launch_captured(chain ? h->graph_chain : h->graph_step, st, use_graph != 0,
+                           [&] { return enqueue_pmcmc(h, st, chain); });
 }
 
 // inputs of a call -> the handle's buffers, on its own stream; `outs` are the five record pointers of k_pm_accept
@@ -4528,8 +4500,7 @@ int pmcmc_begin(fbsmi_lg_pmcmc* h, const float* uT, const float* log_ell, const 
     fbsmi_lg_sweep* s = h->filt->core;
     const PmDev& p = h->p;
     const size_t C = p.C, T1 = (size_t)p.T + 1;
-    FBSMI_HIP_TRY(hipEventRecord(s->ev_in, ust));
-    FBSMI_HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_in, 0));
+    if (int rc = join_in(s, ust)) return rc;
     FBSMI_HIP_TRY(hipMemcpyAsync(p.uT, uT, C * p.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(p.log_ell, log_ell, C * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(p.ys, ys, C * T1 * p.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
@@ -4548,9 +4519,7 @@ int pmcmc_end(fbsmi_lg_pmcmc* h, float* uT, float* log_ell, float* ys, hipStream
     FBSMI_HIP_TRY(hipMemcpyAsync(uT, p.uT, C * p.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(log_ell, p.log_ell, C * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     FBSMI_HIP_TRY(hipMemcpyAsync(ys, p.ys, C * T1 * p.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-    FBSMI_HIP_TRY(hipEventRecord(s->ev_out, s->stream));
-    FBSMI_HIP_TRY(hipStreamWaitEvent(ust, s->ev_out, 0));
-    return FBSMI_OK;
+    return join_out(s, ust);
 }
 
 }  // namespace
@@ -4591,29 +4560,24 @@ int fbsmi_lg_pmcmc_create(const fbsmi_lg_model* m, const fbsmi_lg_pmcmc_tables* 
     p.F = d.F; p.sqQ = d.sqQ;
     p.fkeys = d.keys; p.vs = d.vs; p.u0s = filt->u0s; p.usT = d.usT; p.ell = d.ell;
     h->rows = kPmTile / p.du < kBlock ? kPmTile / p.du : kBlock;   // du <= 128: at least 32 rows
-    // one allocation, 256-byte aligned pieces
     const size_t C = p.C, T1 = (size_t)p.T + 1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_key = take(2 * sizeof(uint32_t)), o_ikeys = take(C * 2 * sizeof(uint32_t)),
-                 o_pk = take(C * 4 * sizeof(uint32_t)), o_y0 = take(p.dv * sizeof(float)),
-                 o_xi = take(C * 2 * (size_t)p.T * p.dv * sizeof(float)), o_mcond = take(C * p.du * sizeof(float)),
-                 o_uT = take(C * p.du * sizeof(float)), o_ell = take(C * sizeof(float)),
-                 o_ys = take(C * T1 * p.dv * sizeof(float)), o_prop = take(C * T1 * p.dv * sizeof(float)),
-                 o_counter = take(sizeof(int32_t)), o_out = take(5 * sizeof(void*));
-    if (hipMalloc(&h->slab, off) != hipSuccess || hipMemset(h->slab, 0, off) != hipSuccess) {
+    Slab slab;
+    slab.request(&p.key, 2);
+    slab.request(&p.ikeys, C * 2);
+    slab.request(&p.pk, C * 4);
+    slab.request(&p.y0, p.dv);
+    slab.request(&p.xi, C * 2 * (size_t)p.T * p.dv);
+    slab.request(&p.mcond, C * p.du);
+    slab.request(&p.uT, C * p.du);
+    slab.request(&p.log_ell, C);
+    slab.request(&p.ys, C * T1 * p.dv);
+    slab.request(&p.prop_ys, C * T1 * p.dv);
+    slab.request(&p.counter, 1);
+    slab.request(&p.out, 5);
+    if (slab.commit(&h->slab) != hipSuccess) {
         fbsmi_lg_pmcmc_destroy(h);
         return fail(FBSMI_ERR_HIP, "lg_pmcmc_create: device allocation failed");
     }
-    char* b = (char*)h->slab;
-    p.key = (uint32_t*)(b + o_key); p.ikeys = (uint32_t*)(b + o_ikeys); p.pk = (uint32_t*)(b + o_pk);
-    p.y0 = (float*)(b + o_y0); p.xi = (float*)(b + o_xi); p.mcond = (float*)(b + o_mcond);
-    p.uT = (float*)(b + o_uT); p.log_ell = (float*)(b + o_ell); p.ys = (float*)(b + o_ys);
-    p.prop_ys = (float*)(b + o_prop); p.counter = (int32_t*)(b + o_counter); p.out = (void**)(b + o_out);
     *out = h;
     return FBSMI_OK;
 }
@@ -4634,11 +4598,9 @@ int fbsmi_lg_pmcmc_step(fbsmi_lg_pmcmc* h, const uint32_t* keys, float* uT, floa
     hipStream_t ust = (hipStream_t)stream;
     hipStream_t st = h->filt->core->stream;
     void* const outs[5] = {nullptr, acc_prob, accepted, prop_log_ell, nullptr};
-    int rc = pmcmc_begin(h, uT, log_ell, ys, y0, outs, ust);
-    if (rc) return rc;
+    if (int rc = pmcmc_begin(h, uT, log_ell, ys, y0, outs, ust)) return rc;
     FBSMI_HIP_TRY(hipMemcpyAsync(h->p.ikeys, keys, (size_t)h->p.C * 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    rc = run_pmcmc(h, 0, use_graph);
-    if (rc) return rc;
+    if (int rc = run_pmcmc(h, 0, use_graph)) return rc;
     return pmcmc_end(h, uT, log_ell, ys, ust);
 }
 
@@ -4650,13 +4612,10 @@ int fbsmi_lg_pmcmc_chain(fbsmi_lg_pmcmc* h, uint32_t* key, float* uT, float* log
     hipStream_t ust = (hipStream_t)stream;
     hipStream_t st = h->filt->core->stream;
     void* const outs[5] = {samples, acc_prob, accepted, prop_log_ell, log_ells};
-    int rc = pmcmc_begin(h, uT, log_ell, ys, y0, outs, ust);
-    if (rc) return rc;
+    if (int rc = pmcmc_begin(h, uT, log_ell, ys, y0, outs, ust)) return rc;
     FBSMI_HIP_TRY(hipMemcpyAsync(h->p.key, key, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    for (int i = 0; i < nsamples; ++i) {
-        rc = run_pmcmc(h, 1, use_graph);
-        if (rc) return rc;
-    }
+    for (int i = 0; i < nsamples; ++i)
+        if (int rc = run_pmcmc(h, 1, use_graph)) return rc;
     FBSMI_HIP_TRY(hipMemcpyAsync(key, h->p.key, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     return pmcmc_end(h, uT, log_ell, ys, ust);
 }

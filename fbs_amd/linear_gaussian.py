@@ -231,24 +231,23 @@ class LinearGaussianBridge:
             return True
         return max(self.du, self.dv) <= 128 and nparticles <= 131072
 
+    def _cached(self, keyt, make):
+        """Get-or-create in the bridge's cache of engine handles and device tables."""
+        h = self._sweeps.get(keyt)
+        if h is None:
+            h = self._sweeps[keyt] = make()
+        return h
+
     def sweep_handle(self, nparticles: int, explicit_backward=True, explicit_final=False, store_path=None,
                      nchains: int = 1):
         store = (not explicit_backward) if store_path is None else bool(store_path)
         keyt = (int(nparticles), bool(explicit_backward), bool(explicit_final), store, int(nchains))
-        h = self._sweeps.get(keyt)
-        if h is None:
-            h = LGSweep(self, *keyt)
-            self._sweeps[keyt] = h
-        return h
+        return self._cached(keyt, lambda: LGSweep(self, *keyt))
 
     def filter_handle(self, nparticles: int, flow: str, resampling: str = "stratified", store_path: bool = False,
                       nchains: int = 1):
         keyt = ("filter", int(nparticles), flow, resampling, bool(store_path), int(nchains))
-        h = self._sweeps.get(keyt)
-        if h is None:
-            h = LGFilter(self, int(nparticles), flow, resampling, bool(store_path), int(nchains))
-            self._sweeps[keyt] = h
-        return h
+        return self._cached(keyt, lambda: LGFilter(self, int(nparticles), flow, resampling, bool(store_path), int(nchains)))
 
     def fused_pmcmc_supported(self, nparticles: int) -> bool:
         """What fbsmi_lg_pmcmc_create accepts: the fused filter's sizes, and an exact forward transition (a model with an
@@ -266,8 +265,8 @@ class LinearGaussianBridge:
         """The device copy of pmcmc_tables_host as an fbsmi_lg_pmcmc_tables struct (cached; the struct keeps its arrays
         alive through ``_keep``)."""
         keyt = ("pmcmc_tables", None if delta is None else float(delta), int(which_u))
-        st = self._sweeps.get(keyt)
-        if st is None:
+
+        def make():
             tab = self.pmcmc_tables_host(delta)
             dev = {k: torch.from_numpy(np.ascontiguousarray(tab[k])).to(self.device)
                    for k in ("m_u", "m_v", "gain", "chol", "mean_coef") if tab[k] is not None}
@@ -276,17 +275,14 @@ class LinearGaussianBridge:
                                           float(tab["c0"]), float(tab["beta"]), float(tab["one_minus_beta"]),
                                           float(tab["c1"]), int(tab["use_pcn"]), int(which_u))
             st._keep = dev
-            self._sweeps[keyt] = st
-        return st
+            return st
+
+        return self._cached(keyt, make)
 
     def pmcmc_handle(self, nparticles: int, resampling: str = "stratified", nchains: int = 1,
                      delta: Optional[float] = None, which_u: int = 0):
         keyt = ("pmcmc", int(nparticles), resampling, int(nchains), None if delta is None else float(delta), int(which_u))
-        h = self._sweeps.get(keyt)
-        if h is None:
-            h = LGPmcmc(self, int(nparticles), resampling, int(nchains), delta, int(which_u))
-            self._sweeps[keyt] = h
-        return h
+        return self._cached(keyt, lambda: LGPmcmc(self, int(nparticles), resampling, int(nchains), delta, int(which_u)))
 
     def gibbs_kernel(self, key, x0, y0, bs_star, nparticles, explicit_backward=True, explicit_final=False,
                      use_graph=True):
@@ -295,12 +291,43 @@ class LinearGaussianBridge:
         return h.sweep(key, x0, y0, bs_star, use_graph=use_graph)
 
 
-class LGSweep:
+class _LGHandle:
+    """What the three engine handles share: the handle's lifetime (``_DESTROY`` names its destroy entry of libfbsmi) and
+    the staging of a call's keys and tensors.  A subclass sets ``model``, ``C`` (chains) and ``h`` (the handle)."""
+
+    _DESTROY = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                getattr(_lib.lib(), self._DESTROY)(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _dev(self, x, dtype, shape, clone=False):
+        """x on the model's device, contiguous; clone=True: storage of its own (the call overwrites it)."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x))
+        x = x.to(self.model.device, dtype).contiguous().reshape(shape)
+        return x.clone() if clone else x
+
+    def _key_t(self, key, n):
+        k = np.asarray(key.detach().cpu() if isinstance(key, torch.Tensor) else key).astype(np.uint32).reshape(n, 2)
+        return torch.from_numpy(k.view(np.int32).copy()).to(self.model.device)
+
+    def _sq(self, t, axis=0):
+        return t.squeeze(axis) if self.C == 1 else t
+
+
+class LGSweep(_LGHandle):
     """Owns one fbsmi_lg_sweep handle (device buffers + captured hipGraph) for `nchains` chains.
 
     With nchains == 1 the chain axis is squeezed from inputs and outputs (the reference's plain
     gibbs_kernel); with nchains > 1 every per-chain array carries a leading axis of that size, like
     the reference's jax.vmap(gibbs_kernel, in_axes=[0, 0, None, 0, 0]) (gp_gibbs.py:173)."""
+
+    _DESTROY = "fbsmi_lg_sweep_destroy"
 
     def __init__(self, model: LinearGaussianBridge, nparticles, eb, ef, store, nchains=1, _group=None):
         self.model = model
@@ -352,26 +379,6 @@ class LGSweep:
         if _group is not None:
             _lib.call("fbsmi_lg_sweep_set_group", self.h, int(_group[0]), int(_group[1]))
 
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.lib().fbsmi_lg_sweep_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def _dev(self, x, dtype, shape):
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x))
-        return x.to(self.model.device, dtype).contiguous().reshape(shape)
-
-    def _key_t(self, key, n):
-        k = np.asarray(key.detach().cpu() if isinstance(key, torch.Tensor) else key).astype(np.uint32).reshape(n, 2)
-        return torch.from_numpy(k.view(np.int32).copy()).to(self.model.device)
-
-    def _sq(self, t):
-        return t[0] if self.C == 1 else t
-
     def sweep(self, key, x0, y0, bs_star, use_graph=True):
         """key (C,2) [or (2,)], x0 (C,du), y0 (dv,), bs_star (C,T+1) -> (x0, us_star, bs_star, acc)."""
         m, Cn = self.model, self.C
@@ -403,9 +410,9 @@ class LGSweep:
         Returns (key, x0, bs_star, x0s) with x0s of shape (nsweeps, [C,] du)."""
         m, Cn = self.model, self.C
         kt = self._key_t(key, 1)
-        x0t = self._dev(x0, torch.float32, (Cn, m.du)).clone()
+        x0t = self._dev(x0, torch.float32, (Cn, m.du), clone=True)
         y0t = self._dev(y0, torch.float32, (m.dv,))
-        bst = self._dev(bs_star, torch.int32, (Cn, m.T + 1)).clone()
+        bst = self._dev(bs_star, torch.int32, (Cn, m.T + 1), clone=True)
         x0s = torch.empty((nsweeps, Cn, m.du), dtype=torch.float32, device=m.device) if keep else None
         if self.children:
             _lib.call("fbsmi_lg_gibbs_chain_groups", self._harr, len(self.children), kt.data_ptr(), x0t.data_ptr(), y0t.data_ptr(),
@@ -457,7 +464,7 @@ class LGSweep:
         return avg.value, n.value
 
 
-class LGFilter:
+class LGFilter(_LGHandle):
     """Fused bootstrap_filter (flow='bootstrap', smc.py:9-88) / pmcmc_filter_step (flow='pmcmc',
     smc.py:115-158) for the analytic model: one hipGraph replay per call, for `nchains` independent filters at once.
 
@@ -466,6 +473,7 @@ class LGFilter:
 
     _FLOW = {"bootstrap": 0, "pmcmc": 1}
     _RES = {"stratified": 0, "systematic": 1}
+    _DESTROY = "fbsmi_lg_filter_destroy"
 
     def __init__(self, model: LinearGaussianBridge, nparticles, flow, resampling, store_path, nchains=1):
         self.model, self.n, self.flow, self.store, self.C = model, nparticles, flow, store_path, int(nchains)
@@ -475,19 +483,10 @@ class LGFilter:
                       self._RES[resampling], int(store_path), self.C, C.byref(h))
         self.h = h
 
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.lib().fbsmi_lg_filter_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
     def run(self, key, vs, u0s, use_graph=True):
         """-> (particles ([C,] n, du), log-likelihood ([C]) tensor[, filtering path ([C,] T+1, n, du)])."""
         m, Cn = self.model, self.C
-        k = np.asarray(key.detach().cpu() if isinstance(key, torch.Tensor) else key).astype(np.uint32).reshape(Cn, 2)
-        kt = torch.from_numpy(k.view(np.int32).copy()).to(m.device)
+        kt = self._key_t(key, Cn)
         vst = m._t(vs).reshape(Cn, m.T + 1, m.dv)
         u0t = m._t(u0s).reshape(Cn, self.n, m.du)
         uT = torch.empty((Cn, self.n, m.du), dtype=torch.float32, device=m.device)
@@ -495,17 +494,18 @@ class LGFilter:
         path = torch.empty((Cn, m.T + 1, self.n, m.du), dtype=torch.float32, device=m.device) if self.store else None
         _lib.call("fbsmi_lg_filter_run", self.h, kt.data_ptr(), vst.data_ptr(), u0t.data_ptr(), uT.data_ptr(),
                   ell.data_ptr(), path.data_ptr() if path is not None else None, int(bool(use_graph)), ops._stream())
-        sq = (lambda t: t[0]) if Cn == 1 else (lambda t: t)
-        return (sq(uT), sq(ell)) if path is None else (sq(uT), sq(ell), sq(path))
+        return tuple(self._sq(t) for t in (uT, ell, path) if t is not None)
 
 
-class LGPmcmc:
+class LGPmcmc(_LGHandle):
     """Owns one fbsmi_lg_pmcmc handle: pmcmc_kernel (smc.py:171-258) for `nchains` chains, one hipGraph replay per MCMC
     iteration, nothing on the host between iterations.
 
     With nchains == 1 the chain axis is squeezed from inputs and outputs (the reference's plain pmcmc_kernel); with
     nchains > 1 every per-chain array carries a leading axis of that size, like the reference's
     jax.vmap(pmcmc_kernel, in_axes=[0, 0, 0, 0, None]) (gp_pmcmc.py:161)."""
+
+    _DESTROY = "fbsmi_lg_pmcmc_destroy"
 
     def __init__(self, model: LinearGaussianBridge, nparticles, resampling, nchains=1, delta=None, which_u=0):
         if not model.fused_pmcmc_supported(nparticles):
@@ -519,30 +519,10 @@ class LGPmcmc:
                       LGFilter._RES[resampling], self.C, C.byref(h))
         self.h = h
 
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                _lib.lib().fbsmi_lg_pmcmc_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    def _dev(self, x, shape):
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x, np.float32))
-        return x.to(self.model.device, torch.float32).reshape(shape).contiguous().clone()
-
-    def _key_t(self, key, n):
-        k = np.asarray(key.detach().cpu() if isinstance(key, torch.Tensor) else key).astype(np.uint32).reshape(n, 2)
-        return torch.from_numpy(k.view(np.int32).copy()).to(self.model.device)
-
-    def _sq(self, t, axis=0):
-        return t.squeeze(axis) if self.C == 1 else t
-
     def _state_in(self, uT, log_ell, ys, y0):
         m, Cn = self.model, self.C
-        return (self._dev(uT, (Cn, m.du)), self._dev(log_ell, (Cn,)), self._dev(ys, (Cn, m.T + 1, m.dv)),
-                self._dev(y0, (m.dv,)))
+        return tuple(self._dev(x, torch.float32, shape, clone=True)
+                     for x, shape in ((uT, (Cn, m.du)), (log_ell, (Cn,)), (ys, (Cn, m.T + 1, m.dv)), (y0, (m.dv,))))
 
     def step(self, keys, uT, log_ell, ys, y0, use_graph=True):
         """keys (C,2) [or (2,)], uT (C,du), log_ell (C), ys (C,T+1,dv), y0 (dv,) -> (uT, log_ell, ys, MCMCState)."""
