@@ -2,7 +2,10 @@
 
 Counterpart of the reference driver experiments/toy/gp_twisted.py (same flags, key schedule and .npz schema:
 samples (nsamples, d), gp_mean, gp_cov).  The twisting function's gradient goes through the score by torch
-autograd, as the reference's does by jax.grad; resampling, gathers and normalisations are libfbsmi kernels."""
+autograd, as the reference's does by jax.grad; resampling, gathers and normalisations are libfbsmi kernels.
+
+--fused runs the same sampler on the fused engine (fbs_amd.GaussianTwisted: the gradient in closed form, a whole run one
+graph replay), --batch B conditional samples per call; same key schedule, same .npz."""
 import argparse
 import math
 import os
@@ -11,17 +14,15 @@ import numpy as np
 import torch
 
 from _gp_toy import add_common_args, gp_setting
-from fbs_amd import ops
+from fbs_amd import GaussianTwisted, ops
 from fbs_amd.samplers import stratified
 from fbs_amd.samplers.smc import twisted_smc
 from fbs_amd.sdes import make_linear_sde
 
 
-def main(argv=None):
-    args = add_common_args(argparse.ArgumentParser()).parse_args(argv)
-    dev = torch.device('cuda:0')
-    g = gp_setting(args, dev)
-    key, ts, sde, d, N = g['key'], g['ts'], g['sde'], g['d'], args.nparticles
+def closure_sampler(g, N, dev):
+    """conditional_sampler (:133-141) on the closure tier: key -> one conditional sample (d,)."""
+    ts, sde, d = g['ts'], g['sde'], g['d']
     T, dt, obs_var = float(ts[-1]), float(ts[1] - ts[0]), g['obs_var']
     y0 = g['y0_t']
     discretise = make_linear_sde(sde)[0]
@@ -81,10 +82,42 @@ def main(argv=None):
                                   twisting_prop_sampler, twisting_prop_logpdf, resampling=stratified, nparticles=N)
         return ops.choice(key_select, uvs, p=ops.math_map("exp", log_ws), axis=0)
 
-    samples = torch.empty((args.nsamples, d), device=dev)
+    return conditional_sampler
+
+
+def main(argv=None):
+    parser = add_common_args(argparse.ArgumentParser())
+    parser.add_argument('--fused', action='store_true', help='Run on the fused twisted-SMC engine.')
+    parser.add_argument('--batch', type=int, default=64, help='With --fused: conditional samples per call.')
+    args = parser.parse_args(argv)
+    dev = torch.device('cuda:0')
+    g = gp_setting(args, dev)
+    if args.fused:
+        return finish(args, g, fused_samples(args, g, dev))
+    key, conditional_sampler = g['key'], closure_sampler(g, args.nparticles, dev)
+    samples = torch.empty((args.nsamples, g['d']), device=dev)
     for i in range(args.nsamples):                                                  # :144-148
         key, subkey = ops.split(key)
         samples[i] = conditional_sampler(subkey)
+    return finish(args, g, samples)
+
+
+def fused_samples(args, g, dev):
+    """The driver loop (:144-148) B samples at a time: the subkeys come from the same chain of splits."""
+    model = GaussianTwisted(np.zeros(g['d']), g['cov_mat'], g['sde'], g['ts'], g['obs_var'], g['y0'], device=dev)
+    key, B = g['key'], max(1, min(args.batch, args.nsamples))
+    samples = torch.empty((args.nsamples, g['d']), device=dev)
+    for i0 in range(0, args.nsamples, B):
+        subkeys = []
+        for _ in range(min(B, args.nsamples - i0)):
+            key, subkey = ops.split(key)
+            subkeys.append(np.asarray(subkey, np.uint32))
+        h = model.handle(args.nparticles, 'stratified', nruns=len(subkeys))
+        samples[i0:i0 + len(subkeys)] = h.sample(np.stack(subkeys))
+    return samples
+
+
+def finish(args, g, samples):
     samples = samples.cpu().numpy()
     if not args.quiet:
         err = np.abs(samples.mean(axis=0) - g['gp_mean']).max()

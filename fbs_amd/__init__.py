@@ -10,8 +10,9 @@ from .ops import PRNGKey, split  # noqa: F401
 from . import ops, sdes, samplers  # noqa: F401
 from .linear_gaussian import LinearGaussianBridge  # noqa: F401
 from .gaussian_sb import GaussianSBBridge  # noqa: F401
+from .lg_twisted import GaussianTwisted  # noqa: F401
 
-__all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "GaussianSBBridge", "PRNGKey", "split", "build"]
+__all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "GaussianSBBridge", "GaussianTwisted", "PRNGKey", "split", "build"]
 
 
 def build(force: bool = False) -> str:

@@ -11,7 +11,8 @@ import shutil
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip")]
+_SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip",
+                                                  "fbsmi_tw.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", "fbsmi_device.h"), os.path.join(_HERE, "csrc", "fbsmi_host.h"),
                 os.path.join(_HERE, "csrc", "fbsmi_em_path.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi.h"), os.path.join(_HERE, "..", "include", "fbsmi_math.h"),
@@ -45,7 +46,7 @@ def _stale() -> bool:
 
 def _compile_and_link(force: bool) -> None:
     """One object per source file (kept under lib/obj/, recompiled only when its source or a header is newer), compiled
-    side by side, then linked: a change to one kernel file costs one compilation, not five."""
+    side by side, then linked: a change to one kernel file costs one compilation, not six."""
     os.makedirs(_OBJ_DIR, exist_ok=True)
     hip = _hipcc()
     th = max(os.path.getmtime(h) for h in _HEADERS)
@@ -147,6 +148,13 @@ class LGPmcmcTablesStruct(C.Structure):
                 ("c1", C.c_float), ("use_pcn", C.c_int32), ("which_u", C.c_int32)]
 
 
+class TWModelStruct(C.Structure):
+    _fields_ = [("d", C.c_int32), ("T", C.c_int32), ("dt", C.c_float),
+                ("R", C.c_void_p), ("r", C.c_void_p), ("C", C.c_void_p), ("c", C.c_void_p), ("sd", C.c_void_p),
+                ("lognorm", C.c_void_p), ("m_ref", C.c_void_p), ("Lt", C.c_void_p), ("y", C.c_void_p),
+                ("obs_var", C.c_float), ("lognorm_obs", C.c_float)]
+
+
 class EMMaskStruct(C.Structure):
     _fields_ = [("du", C.c_int32), ("dv", C.c_int32), ("u_off", C.c_void_p), ("v_off", C.c_void_p),
                 ("role", C.c_void_p)]
@@ -202,6 +210,10 @@ SIGNATURES = {
     "fbsmi_lg_pmcmc_destroy": (None, [_vp]),
     "fbsmi_lg_pmcmc_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fbsmi_lg_pmcmc_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "fbsmi_tw_create": (C.c_int, [C.POINTER(TWModelStruct), _i32, C.c_int, _i32, C.c_int, C.POINTER(_vp)]),
+    "fbsmi_tw_destroy": (None, [_vp]),
+    "fbsmi_tw_run": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    "fbsmi_tw_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
     "fbsmi_lg_sweep_profile": (C.c_int, [_vp, C.c_int]),
     "fbsmi_lg_sweep_kernel_us": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "fbsmi_em_concat": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),

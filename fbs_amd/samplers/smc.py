@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..lg_twisted import fused_twisted
 from ..score import bridge_of
 from . import resampling as _resampling
 from .common import MCMCState
@@ -229,7 +230,14 @@ def pmcmc_chain(key, uTs, log_ells, yss, y0, ts, fwd_ys_sampler, sde, ref_sample
 
 def twisted_smc(key, y, ts, init_sampler, transition_logpdf, twisting_logpdf, twisting_prop_sampler,
                 twisting_prop_logpdf, resampling, nparticles, **kwargs):
-    """Twisted SMC baseline (smc.py:261-309; Algorithm 1 of arXiv 2306.17775)."""
+    """Twisted SMC baseline (smc.py:261-309; Algorithm 1 of arXiv 2306.17775).  With the five closures of one
+    GaussianTwisted on its own grid and y, and stratified / systematic resampling, the whole run is one fused launch
+    sequence on the device (TwistedHandle.run); otherwise the host loop below."""
+    fused = fused_twisted(y, ts, init_sampler, transition_logpdf, twisting_logpdf, twisting_prop_sampler,
+                          twisting_prop_logpdf, resampling, nparticles, kwargs)
+    if fused is not None:
+        xs, log_ws = fused[0].handle(nparticles, fused[1]).run(key)
+        return xs[0], log_ws[0]
     nsteps = (ts.shape[0] if hasattr(ts, "shape") else len(ts)) - 1
     key_init, key_filter = ops.split(key, 2)
     keys = ops.split(key_filter, nsteps)

@@ -289,6 +289,65 @@ int fbsmi_lg_pmcmc_chain(fbsmi_lg_pmcmc* h, uint32_t* key, float* uT, float* log
                          int32_t nsamples, float* samples, float* acc_prob, uint8_t* accepted, float* prop_log_ell,
                          float* log_ells, int use_graph, void* stream);
 
+/* ---- fused twisted SMC for the analytic Gaussian model, batched over runs ------------------------
+ * twisted_smc (fbs/samplers/smc.py:261-309) with the closures of experiments/toy/gp_twisted.py:100-129 for a Gaussian
+ * prior N(mean, cov) of x and the observation y of x + N(0, obs_var I): the twisting function is a Gaussian density of
+ * an affine map of the particle, so its gradient (gp_twisted.py:87-89, jax.grad) is affine and a step is two matrix
+ * products and three row-summed Gaussian log-densities.  Tables, one entry per time point j = 0..T of the grid ts
+ * (twisted_smc evaluates the closures at ts[0] for the initial twist and at ts[k+1] in step k); with s = ts[T] - ts[j],
+ * F, Q = discretise(s, ts[0]), P = inv(F^2 cov + Q I), a = drift(1, s), b = dispersion(s), dt = (ts[T] - ts[0]) / T:
+ *   R[j] = -a I - b^2 P,  r[j] = b^2 P (F mean)                     reverse drift rd(u) = R u + r
+ *   B    = I + dt R[j]                                               (the denoising estimate is B u + dt r)
+ *   C[j] = R[j] - (b^2 / obs_var) B^T B,  c[j] = r[j] + (b^2 / obs_var) B^T (y - dt r[j])
+ *                                                                    conditional reverse drift rcd(u) = C u + c
+ *   sd[j] = sqrt(dt) b,  lognorm[j] = log(2 pi sd[j]^2),  lognorm_obs = log(2 pi obs_var)
+ *   m_ref = F_T mean,  Lt = transpose of the lower Cholesky factor of F_T^2 cov + Q_T I   (F_T, Q_T: j = 0)
+ * built in float64 on the host and rounded once to float32 (fbs_amd/lg_twisted.py, lg_twisted_tables).
+ *
+ * Numeric specification (float32, no contraction; tests/tw_restate.py restates it in numpy):
+ *   drift_i(M, m, u): acc = m_i, then acc = fbsmi_fmaf(M[i][c], u[c], acc) for c ascending
+ *   nlp(x, loc, s2, ln) = (ln + ((x - loc) * (x - loc)) / s2) / -2;  a row sum is acc = term_0, then acc + term_i, i ascending
+ *   twist_j(u) = sum_i nlp(y_i, u_i + drift_i(R[j], r[j], u) * dt, obs_var, lognorm_obs)
+ *   init: key_init, key_filter = split(key); keys = split(key_filter, T); z = normal(key_init, (N, d));
+ *         x[n][i] = m_ref[i] + acc with acc = z[n][0] * Lt[0][i], then acc + z[n][c] * Lt[c][i];
+ *         log_ps = twist_0(x); log_ws = log_ps - logsumexp(log_ps)   (the two-level logsumexp of fbsmi_math.h)
+ *   step k (j = k + 1): key_resampling, key_prop = split(keys[k]); inds = resampling(fbsmi_expf(log_ws), key_resampling);
+ *         xp = x[inds], lpp = log_ps[inds]; m_i = xp_i + drift_i(C[j], c[j], xp) * dt; x_i = m_i + sd[j] * z_i with
+ *         z = normal(key_prop, (N, d)); log_ps = twist_j(x);
+ *         tl = sum_i nlp(x_i, xp_i + drift_i(R[j], r[j], xp) * dt, sd[j]^2, lognorm[j]);
+ *         pl = sum_i nlp(x_i, m_i, sd[j]^2, lognorm[j])              (from the stored x_i and m_i)
+ *         lw = ((tl + log_ps) - pl) - lpp; log_ws = lw - logsumexp(lw)
+ *   selection (select != 0): key_filter, key_select = split(key) in front of the run, and after it
+ *         jax.random.choice(key_select, N, p = fbsmi_expf(log_ws)) picks the returned row (gp_twisted.py:133-141). */
+typedef struct fbsmi_tw_model {
+    int32_t d, T;
+    float dt;
+    const float* R;       /* (T+1, d, d) */
+    const float* r;       /* (T+1, d) */
+    const float* C;       /* (T+1, d, d) */
+    const float* c;       /* (T+1, d) */
+    const float* sd;      /* (T+1) */
+    const float* lognorm; /* (T+1) */
+    const float* m_ref;   /* (d) */
+    const float* Lt;      /* (d, d) */
+    const float* y;       /* (d) */
+    float obs_var, lognorm_obs;
+} fbsmi_tw_model;
+typedef struct fbsmi_tw fbsmi_tw; /* opaque: device buffers for nruns runs, a stream and the captured graphs */
+/* resampling 0 stratified | 1 systematic.  The tables stay the caller's and must outlive the handle.  d outside
+ * [1, 128] or nparticles outside [1, 131072]: FBSMI_ERR_UNSUPPORTED.  store_ancestors: keep every step's ancestors. */
+int fbsmi_tw_create(const fbsmi_tw_model* model, int32_t nparticles, int resampling, int32_t nruns, int store_ancestors,
+                    fbsmi_tw** out);
+void fbsmi_tw_destroy(fbsmi_tw* h);
+/* nruns independent runs, one per key of keys (nruns, 2).  Nullable outputs: xs (nruns, N, d) the final particles,
+ * log_ws (nruns, N) their normalised log-weights, samples (nruns, d) the selected rows (select != 0 only). */
+int fbsmi_tw_run(fbsmi_tw* h, const uint32_t* keys, int select, float* xs, float* log_ws, float* samples, int use_graph,
+                 void* stream);
+/* State of the last run, copied to dst (nullable: only *count is set), 4-byte elements: which 0 the ancestors of every
+ * step (nruns, T, N) int32 (store_ancestors); of the last step: 1 log_ps, 2 tl, 3 pl (nruns, N), 4 the particles it
+ * started from (nruns, N, d), 5 its ancestors (nruns, N) int32. */
+int fbsmi_tw_view(fbsmi_tw* h, int which, void* dst, int64_t* count, void* stream);
+
 /* ---- fused SMC step for score-network models (image experiments) --------------------------------
  * The three closures of experiments/imgs/inpainting.py:102-147 (and supr.py; sb_imgs/supr.py:80-127)
  * wrap ONE network evaluation on the joint image concat(u, v) per SMC step (csmc.py:142,145 evaluate it
