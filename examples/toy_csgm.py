@@ -5,7 +5,10 @@ samples (nsamples, d), gp_mean, gp_cov) -- the `csgm` column of the paper's Tabl
 The reverse drift is -a u + b^2 (grad log p_t(u) + grad_u log p(y0 | u_t = u)); both scores are Gaussian, so the drift is
 affine in u: the reference gets the second term by jax.grad of a multivariate-normal log-density, here the same gradient is
 written out (cond_m is affine in u: grad = M^T cond_cov^{-1} (y0 - cond_m(u))) and tabulated per step in float64.  The
-integration is fbs_amd's euler_maruyama (one libfbsmi kernel per step with the noise drawn inside, fbsmi_em_update)."""
+integration is fbs_amd's euler_maruyama (one libfbsmi kernel per step with the noise drawn inside, fbsmi_em_update).
+
+--fused runs the same sampler on the fused engine (fbs_amd.GaussianCSGM: a batch of conditional samples is one kernel
+launch), --batch B conditional samples per call; same key schedule, same .npz."""
 import argparse
 import os
 
@@ -13,18 +16,14 @@ import numpy as np
 import torch
 
 from _gp_toy import add_common_args, gp_setting
-from fbs_amd import ops
+from fbs_amd import GaussianCSGM, ops
 from fbs_amd.sdes import make_linear_sde
 from fbs_amd.sdes.simulators import euler_maruyama
 
 
-def main(argv=None):
-    p = add_common_args(argparse.ArgumentParser())
-    p.set_defaults(d=100)                                                           # gp_csgm.py:12
-    args = p.parse_args(argv)
-    dev = torch.device('cuda:0')
-    g = gp_setting(args, dev)
-    key, ts, sde, d = g['key'], g['ts'], g['sde'], g['d']
+def closure_sampler(g, dev):
+    """conditional_sampler (gp_csgm.py:103-108) on the closure tier: key -> one conditional sample (d,)."""
+    ts, sde, d = g['ts'], g['sde'], g['d']
     T, cov_mat, obs_var, y0 = float(ts[-1]), g['cov_mat'], g['obs_var'], g['y0'].astype(np.float64)
     discretise = make_linear_sde(sde)[0]
     eye = np.eye(d)
@@ -69,11 +68,43 @@ def main(argv=None):
         u0 = m_ref_t + cov_ref_t @ ops.normal(key_init, (d,), device=dev)
         return euler_maruyama(key_sde, u0, ts, reverse_drift, reverse_dispersion, integration_nsteps=1, return_path=False)
 
-    samples = torch.empty((args.nsamples, d), device=dev)
+    return conditional_sampler
+
+
+def main(argv=None):
+    p = add_common_args(argparse.ArgumentParser())
+    p.set_defaults(d=100)                                                           # gp_csgm.py:12
+    p.add_argument('--fused', action='store_true', help='Run on the fused CSGM engine.')
+    p.add_argument('--batch', type=int, default=64, help='With --fused: conditional samples per call.')
+    args = p.parse_args(argv)
+    dev = torch.device('cuda:0')
+    g = gp_setting(args, dev)
+    if args.fused:
+        return finish(args, g, fused_samples(args, g, dev).cpu().numpy())
+    key, conditional_sampler = g['key'], closure_sampler(g, dev)
+    samples = torch.empty((args.nsamples, g['d']), device=dev)
     for i in range(args.nsamples):                                                  # gp_csgm.py:111-116
         key, subkey = ops.split(key)
         samples[i] = conditional_sampler(subkey)
-    samples = samples.cpu().numpy()
+    return finish(args, g, samples.cpu().numpy())
+
+
+def fused_samples(args, g, dev):
+    """The driver loop (gp_csgm.py:111-116) B samples at a time: the subkeys come from the same chain of splits."""
+    model = GaussianCSGM(np.zeros(g['d']), g['cov_mat'], g['sde'], g['ts'], g['obs_var'], g['y0'], device=dev)
+    key, B = g['key'], max(1, min(args.batch, args.nsamples))
+    h = model.handle(B)
+    samples = torch.empty((args.nsamples, g['d']), device=dev)
+    for i0 in range(0, args.nsamples, B):
+        subkeys = []
+        for _ in range(min(B, args.nsamples - i0)):
+            key, subkey = ops.split(key)
+            subkeys.append(np.asarray(subkey, np.uint32))
+        samples[i0:i0 + len(subkeys)] = h.sample(np.stack(subkeys))
+    return samples
+
+
+def finish(args, g, samples):
     if not args.quiet:
         err = np.abs(samples.mean(axis=0) - g['gp_mean']).max()
         print(f'ID: {args.id} | csgm | {args.nsamples} samples | max |mean - gp_mean| = {err:.3f}')

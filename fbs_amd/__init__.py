@@ -11,8 +11,9 @@ from . import ops, sdes, samplers  # noqa: F401
 from .linear_gaussian import LinearGaussianBridge  # noqa: F401
 from .gaussian_sb import GaussianSBBridge  # noqa: F401
 from .lg_twisted import GaussianTwisted  # noqa: F401
+from .lg_csgm import GaussianCSGM  # noqa: F401
 
-__all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "GaussianSBBridge", "GaussianTwisted", "PRNGKey", "split", "build"]
+__all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "GaussianSBBridge", "GaussianTwisted", "GaussianCSGM", "PRNGKey", "split", "build"]
 
 
 def build(force: bool = False) -> str:

@@ -12,7 +12,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip",
-                                                  "fbsmi_tw.hip")]
+                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", "fbsmi_device.h"), os.path.join(_HERE, "csrc", "fbsmi_host.h"),
                 os.path.join(_HERE, "csrc", "fbsmi_em_path.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi.h"), os.path.join(_HERE, "..", "include", "fbsmi_math.h"),
@@ -155,6 +155,11 @@ class TWModelStruct(C.Structure):
                 ("obs_var", C.c_float), ("lognorm_obs", C.c_float)]
 
 
+class CSGMModelStruct(C.Structure):
+    _fields_ = [("d", C.c_int32), ("T", C.c_int32), ("A", C.c_void_p), ("cvec", C.c_void_p), ("ddt", C.c_void_p),
+                ("s", C.c_void_p), ("m_ref", C.c_void_p), ("S_ref", C.c_void_p)]
+
+
 class EMMaskStruct(C.Structure):
     _fields_ = [("du", C.c_int32), ("dv", C.c_int32), ("u_off", C.c_void_p), ("v_off", C.c_void_p),
                 ("role", C.c_void_p)]
@@ -214,6 +219,10 @@ SIGNATURES = {
     "fbsmi_tw_destroy": (None, [_vp]),
     "fbsmi_tw_run": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "fbsmi_tw_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
+    "fbsmi_csgm_create": (C.c_int, [C.POINTER(CSGMModelStruct), _i32, C.c_int, C.POINTER(_vp)]),
+    "fbsmi_csgm_destroy": (None, [_vp]),
+    "fbsmi_csgm_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "fbsmi_csgm_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
     "fbsmi_lg_sweep_profile": (C.c_int, [_vp, C.c_int]),
     "fbsmi_lg_sweep_kernel_us": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "fbsmi_em_concat": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),

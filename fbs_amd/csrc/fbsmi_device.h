@@ -66,6 +66,14 @@ __host__ __device__ __forceinline__ void random_bits_pair(uint32_t k0, uint32_t 
     threefry2x32(k0, k1, (uint32_t)i, (uint32_t)(i + (n >> 1)), lo, hi);
 }
 
+// the same for any n: elements i (< half) and i + half of the draw, half = (n + 1) / 2; for odd n the last call's second
+// counter is the zero pad of random_bits_at and its `hi` word belongs to no element (i + half == n)
+__host__ __device__ __forceinline__ void random_bits_pair_padded(uint32_t k0, uint32_t k1, uint64_t n, uint64_t i, uint32_t& lo,
+                                                                 uint32_t& hi) {
+    const uint64_t b = i + ((n + 1) >> 1);
+    threefry2x32(k0, k1, (uint32_t)i, b < n ? (uint32_t)b : 0u, lo, hi);
+}
+
 __host__ __device__ __forceinline__ float uniform_at(uint32_t k0, uint32_t k1, uint64_t n, uint64_t i) {
     return fbsmi_bits_to_unit(random_bits_at(k0, k1, n, i));
 }

@@ -4,7 +4,7 @@
 closures on torch tensors, so their time loop is host Python with the noise drawn by the JAX-
 compatible device PRNG.  ``doob_bridge_simulator`` has a drift that is affine in x for every
 scalar linear SDE, so the whole (T x integration_nsteps)-step path is ONE kernel launch
-(fbsmi_affine_em_path).
+(fbsmi_affine_em_path), and so is ``euler_maruyama`` on the closures of a ``GaussianCSGM`` (fbsmi_csgm_run).
 """
 from __future__ import annotations
 
@@ -38,6 +38,16 @@ def euler_maruyama(key, x0, ts, drift, dispersion, integration_nsteps: int = 1, 
     if not isinstance(x0, torch.Tensor):
         x0 = torch.as_tensor(np.asarray(x0, np.float32), device=ops._default_device())
     ops._require_cuda(x0, "x0")
+    from ..lg_csgm import fused_csgm
+    hit = fused_csgm(x0, ts_np, drift, dispersion, integration_nsteps, key)
+    if hit is not None:
+        # the closures of one GaussianCSGM on its own grid: the whole path is one kernel launch (fbsmi_csgm_run)
+        model, B = hit
+        h = model.handle(B, store_path=bool(return_path))
+        xT = h.integrate(key, x0.reshape(B, model.d))
+        if return_path:
+            return h.views()["path"].reshape((n + 1,) + tuple(x0.shape))
+        return xT.reshape(x0.shape)
     keys = ops.split(key, n)
     x = x0.to(torch.float32).contiguous()
     path = [x]

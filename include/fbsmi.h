@@ -348,6 +348,50 @@ int fbsmi_tw_run(fbsmi_tw* h, const uint32_t* keys, int select, float* xs, float
  * started from (nruns, N, d), 5 its ancestors (nruns, N) int32. */
 int fbsmi_tw_view(fbsmi_tw* h, int which, void* dst, int64_t* count, void* stream);
 
+/* ---- fused, batched conditional score sampler (CSGM) for the analytic Gaussian model --------------
+ * The `csgm` method of experiments/toy/gp_csgm.py (Song et al., 2021) for a Gaussian prior N(mean, cov) of x and the
+ * observation y of x + N(0, obs_var I): the marginal score and the score of p(y | u_t) are both Gaussian, so the reverse
+ * drift is affine, f(u) = A[k] u + cvec[k] (gp_csgm.py:80-94 takes the second score with jax.grad).  Tables, one entry
+ * per step k = 0..T-1 of the grid ts; with s = ts[T] - ts[k], F, Q = discretise(s, ts[0]), a = drift(1, s),
+ * b = dispersion(s), Sx = F^2 cov + Q I, M = F cov inv(Sx), cond_cov = cov + obs_var I - M (F cov),
+ * Gm = M^T inv(cond_cov):
+ *   A[k]    = -a I + b^2 (-inv(Sx) - Gm M)
+ *   cvec[k] = b^2 (inv(Sx) F mean + Gm (y - mean + M F mean))
+ *   ddt[k]  = float32(|ts[k+1] - ts[k]|),  s[k] = float32(b sqrt(|ts[k+1] - ts[k]|))
+ *   m_ref   = F_T mean + F_T cov inv(Kyy) (y - mean),  S_ref = F_T^2 cov + Q_T I - F_T cov inv(Kyy) F_T cov,
+ *             Kyy = cov + obs_var I   (gp_csgm.py:69-76; the initial normal is multiplied by S_ref itself, as there)
+ * built in float64 on the host and rounded once to float32 (fbs_amd/lg_csgm.py, lg_csgm_tables).
+ *
+ * Numeric specification (float32, no contraction beyond the chains named; tests/csgm_restate.py restates it in numpy):
+ *   u0 == NULL (sample mode): key_init, key_sde = split(keys[b], 2); z = normal(key_init, (d,));
+ *         u0[i]: acc = m_ref[i], then acc = fbsmi_fmaf(S_ref[i][c], z[c], acc) for c = 0..d-1
+ *   u0 != NULL (integrate mode): keys[b] is key_sde, x = u0[b]
+ *   step k: xi = normal(split(key_sde, T)[k], (1, d))[0]      (euler_maruyama's schedule with integration_nsteps = 1)
+ *         f_i: acc = cvec[k][i], then acc = fbsmi_fmaf(A[k][i][c], x[c], acc) for c ascending
+ *         x_i <- (x_i + f_i * ddt[k]) + s[k] * xi_i             (separate float32 operations)
+ *   out[b] = x after step T-1;  path[0] = u0, path[k+1] = x after step k.
+ * One kernel launch per fbsmi_csgm_run, on the caller's stream. */
+typedef struct fbsmi_csgm_model {
+    int32_t d, T;
+    const float* A;     /* (T, d, d) */
+    const float* cvec;  /* (T, d) */
+    const float* ddt;   /* (T) */
+    const float* s;     /* (T) */
+    const float* m_ref; /* (d) */
+    const float* S_ref; /* (d, d) */
+} fbsmi_csgm_model;
+typedef struct fbsmi_csgm fbsmi_csgm; /* opaque: the tables in the kernel's operand order, the u0 and path buffers */
+/* B = nsamples trajectories per call.  The tables are read here, once (the handle keeps its own copy in the order the
+ * kernel's matrix-core operands want).  d outside [1, 128] or nsamples outside [1, 131072]: FBSMI_ERR_UNSUPPORTED.
+ * store_path: keep every step's state. */
+int fbsmi_csgm_create(const fbsmi_csgm_model* model, int32_t nsamples, int store_path, fbsmi_csgm** out);
+void fbsmi_csgm_destroy(fbsmi_csgm* h);
+/* keys (B, 2); u0 (B, d) or NULL (see above); out (B, d). */
+int fbsmi_csgm_run(fbsmi_csgm* h, const uint32_t* keys, const float* u0, float* out, void* stream);
+/* State of the last run, copied to dst (nullable: only *count is set): which 0 the initial states u0 (B, d), 1 the
+ * path (T+1, B, d) (store_path only). */
+int fbsmi_csgm_view(fbsmi_csgm* h, int which, void* dst, int64_t* count, void* stream);
+
 /* ---- fused SMC step for score-network models (image experiments) --------------------------------
  * The three closures of experiments/imgs/inpainting.py:102-147 (and supr.py; sb_imgs/supr.py:80-127)
  * wrap ONE network evaluation on the joint image concat(u, v) per SMC step (csmc.py:142,145 evaluate it
