@@ -34,7 +34,7 @@
 //       through an LDS queue); chunks of a thread move as 16-byte accesses.  (The draws by a launch of their own, one
 //       Threefry call per element pair, through HBM: measured 10 % slower at 2^22, 6 % at 2^20 -- not kept.)
 //   N a power of two, 512 .. 65536                  : TWO kernels per step -- the bisection over the canonical cumsum is a
-//       descent of the summation tree, so norm publishes tree nodes and k_lg_prop1t / k_lg_prop2t walk them; no cdf
+//       descent of the summation tree, so norm publishes tree nodes and k_lg_prop1t / k_lg_prop1tp / k_lg_prop2t walk them; no cdf
 //   N = 2^k + 1 (explicit_final on such an ensemble) : the same two kernels over the first 2^k slots' tree + one extra tile
 #include <hip/hip_runtime.h>
 
@@ -1160,6 +1160,9 @@ __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
 //   substituted -> descent to a tile -> that tile's w fetched whole, its leaves and tree rebuilt in LDS -> descent.
 //   Cat(w) per slot: top levels + three levels of every tile in LDS, then (killed slots only) three levels from the
 //   tile's published heap in one round trip and the last four leaves of w in another.
+// Workgroups: k_lg_prop1t, one tile each (a single chain, pinned launches, N = 2^k + 1); k_lg_prop1tp, two or four tiles N/2
+// apart, the trees built once by the first 256 threads and the noise drawn once per pair of slots by the others meanwhile
+// (from two tiles per CU on); k_lg_prop2t, two slots N/2 apart per thread (from five tiles per CU on).
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool tree_walk(float2 nd, float q, float& P, float& E) {
     const float t = P + nd.x;
@@ -1376,8 +1379,9 @@ __device__ __forceinline__ int tree_leaves_walk(float4 w4, int lo, float q, floa
     return q <= e1 ? leaf : leaf + 1;
 }
 
-// HALVES = 2, 4: a workgroup of 512 / 1024 threads owns adjacent tiles; its first 256 threads build the trees and find J
-// (the other waves wait at the barriers instead of repeating ~450 instructions each), then every thread does its slot.
+// One tile per workgroup: a single chain's launches, the pinned launches and N = 2^k + 1.  Only HALVES = 1 is launched since
+// k_lg_prop1tp (below) took over the workgroups of several tiles; the text is the kernel as it was measured with them (the
+// same kernel with the HALVES > 1 branches taken out compiles to another schedule, 3 % slower for a single chain at N = 65 536).
 template <int DMAX, int HALVES>
 __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) {
     const LgDev d = chain_view(dd, blockIdx.y);
@@ -1521,6 +1525,185 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
         mx = fmaxf(fmaxf(part[0][h4], part[0][h4 + 1]), fmaxf(part[0][h4 + 2], part[0][h4 + 3]));
         TreePath pth;
         const float sw_ = wave_upsweep(fbsmi_expf(lv[0] - finite_or_zero_f(mx)), pth);
+        if (lane == 0) part[1][h4 + wv] = sw_;
+        __syncthreads();
+        sx = (part[1][h4] + part[1][h4 + 1]) + (part[1][h4 + 2] + part[1][h4 + 3]);
+    }
+    if (tid == 0) {
+        d.bmax[tileb] = mx;
+        d.bsumexp[tileb] = sx;
+    }
+}
+
+// k_lg_prop1tp, HALVES = 2, 4: a workgroup of 512 / 1024 threads owns tiles N/2 APART -- HALVES / 2 adjacent tiles from blockIdx.x * HALVES / 2
+// on (the lower side) and the tiles nb / 2 further on (the upper side) -- so thread p of the lower side and thread p of the
+// upper side hold the slots m and m + N/2: the two elements that jax's random_bits puts on the two output words of ONE Threefry
+// call of the noise draw.  The first 256 threads build the trees and find J (the other waves wait at the barriers instead
+// of repeating ~450 instructions each); meanwhile the upper side draws the noise of BOTH slots of its pairs and hands the
+// lower side's through LDS (kPairNoise), so the tree-building waves draw no noise and the workgroup makes one noise call
+// per pair.  Then every thread does its slot.  Every output is written per tile / per slot exactly as by the one-tile
+// workgroups: only the owner changes.
+// The kill-test and redraw uniforms are source-indexed and pair up the same way (the rotation keeps the two sources N/2
+// apart), and the redraw searches of the ~7 % killed slots can be dealt out from an LDS queue as in k_lg_propQ: both were
+// built and measured on top of this kernel and left out -- the two workgroup barriers they need after J (exchange /
+// queue, results) cost more than the ~270 instructions per wave they save.
+template <int DMAX, int HALVES>
+__global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1tp(LgDev dd, int s) {
+    static_assert(HALVES == 2 || HALVES == 4, "two sides of HALVES / 2 tiles");
+    constexpr int HP = HALVES / 2, NP = kBlock * HP;   // tiles per side; pairs
+    // The partner's noise goes through LDS, 4 * DMAX * NP bytes: up to 8 KB for the instantiations up to DMAX = 4.  DMAX = 16
+    // would take 16 / 32 KB next to the 22 KB of trees, so there every slot draws its own noise (same bits: random_bits_at
+    // is the same call with the other word kept).
+    constexpr bool kPairNoise = DMAX <= 4;
+    // The ancestor is one of the last four leaves or the slot behind them: for narrow states its row is fetched together
+    // with those leaves (one dependent round trip less).
+    constexpr bool kEarlyRow = DMAX <= 2;
+    const LgDev d = chain_view(dd, blockIdx.y);
+    __shared__ TreeLds L;
+    __shared__ float part[2][4 * HALVES];
+    __shared__ int Jsh;
+    __shared__ float lastsh;
+    __shared__ float xish[kPairNoise ? DMAX : 1][NP];   // noise of the lower slots, drawn by their partners
+    const int N = d.N, tid = threadIdx.x & (kBlock - 1), half = threadIdx.x / kBlock, lane = threadIdx.x & 63;
+    const bool upper = half >= HP;                       // (wave-uniform)
+    const int pr = (int)threadIdx.x - (upper ? NP : 0);  // the pair
+    const int mL = blockIdx.x * NP + pr;                 // its lower slot, < N/2
+    const int m = upper ? mL + (N >> 1) : mL;
+    const int tileb = m / kBlock;
+    const uint32_t* kt = d.keytab + 8 * s;
+    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
+    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
+    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
+    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    // ---- round 0: everything addressable now
+    const float w_max = d.scal[1];
+    const float inv_n = 1.0f / (float)N;   // N is a power of two: x / N == x * inv_n exactly
+    TreeEntry te{};
+    if (half == 0) te = tree_entry_loads(d, i_ref);
+    float uref[DMAX];
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) uref[r] = r < d.du ? up[(size_t)r * N + i_ref] : 0.0f;
+    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
+    const float* v_prev = d.vs + (size_t)s * d.dv;
+    const float* v = d.vs + (size_t)(s + 1) * d.dv;
+    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
+    const float u3 = __uint_as_float(kt[4]);
+    float xi[DMAX];
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) xi[r] = 0.0f;
+    if (!kPairNoise) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r)
+            if (r < d.du) xi[r] = normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
+    } else if (upper) {   // element mL * du + r is in the first half of the draw, its partner belongs to slot mL + N/2
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r) {
+            if (r < d.du) {
+                uint32_t lo_, hi_;
+                random_bits_pair(t0, t1, (uint64_t)N * d.du, (uint64_t)mL * d.du + r, lo_, hi_);
+                xish[r][pr] = normal_from_bits(lo_);
+                xi[r] = normal_from_bits(hi_);
+            }
+        }
+    }
+    float last;
+    int J;
+    if (half == 0) {
+        float rootW;
+        J = tree_build(d, te, L, i_ref, u3, w_max, inv_n, last, rootW);
+        if (tid == 0) {
+            Jsh = J;
+            lastsh = last;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kTreeBuildBarriers; ++k) __syncthreads();   // the barriers of tree_build
+    }
+    __syncthreads();
+    J = Jsh;
+    last = lastsh;   // == the root of the w tree (powers of two only)
+    int shift = (j_ref - J) % N;   // roll by j - J (:85)
+    if (shift < 0) shift += N;
+    int src = m - shift;
+    if (src < 0) src += N;
+    // ---- round 2
+    const float ws = d.w[src];
+    float u[DMAX];
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * N + src] : 0.0f;
+    if (kPairNoise && !upper) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r)
+            if (r < d.du) xi[r] = xish[r][pr];
+    }
+    const float u1 = uniform_at(a0, a1, (uint64_t)N, (uint64_t)src);
+    const float u2 = uniform_at(b0, b1, (uint64_t)N, (uint64_t)src);
+    const float q = last * (1.0f - u2);                                     // resamplings.py:73-74
+    float P = 0.0f, E = last;
+    int tile, h, red = 0;
+    tree_search_lds(L, d.nb, q, P, E, tile, h);
+    const bool killed = u1 * w_max >= ws;                                   // :71
+    // ---- rounds 3, 4 (killed slots only)
+    float ucand[DMAX];
+    if (killed) {
+        const TreeRound rd = tree_round_load(d, tile, h);
+        const int lo = tree_round_walk(rd, tile, h, q, P, E);
+        const float4 w4 = *reinterpret_cast<const float4*>(d.w + lo);
+        float4 ug[DMAX];
+        float ue[DMAX];
+        if (kEarlyRow) {
+            const int en = lo + 4 < N ? lo + 4 : N - 1;
+#pragma unroll
+            for (int r = 0; r < DMAX; ++r) {
+                ug[r] = r < d.du ? *reinterpret_cast<const float4*>(up + (size_t)r * N + lo) : make_float4(0.f, 0.f, 0.f, 0.f);
+                ue[r] = r < d.du ? up[(size_t)r * N + en] : 0.0f;
+            }
+        }
+        red = tree_leaves_walk(w4, lo, q, P, E);
+        if (kEarlyRow) {
+            const int k = red - lo;
+#pragma unroll
+            for (int r = 0; r < DMAX; ++r) {
+                const float lo2 = (k & 1) ? ug[r].y : ug[r].x, hi2 = (k & 1) ? ug[r].w : ug[r].z;
+                ucand[r] = k >= 4 ? ue[r] : ((k & 2) ? hi2 : lo2);
+            }
+        }
+    }
+    const bool pinned = m == j_ref;
+    const int a = pinned ? i_ref : (killed ? red : src);                    // :86
+    // ---- round 5
+    if (killed && !pinned) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r)
+            if (r < d.du) u[r] = kEarlyRow ? ucand[r] : up[(size_t)r * N + a];
+    }
+    if (pinned) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r) u[r] = uref[r];
+    }
+    if (d.As) d.As[(size_t)s * N + m] = a;
+    // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) {
+        if (r < d.du) {
+            const float dr = drift_row<DMAX>(t, r, u, v_prev);
+            float x = (u[r] + dr * t.dt) + t.sd * xi[r];
+            if (pinned) x = ustar[r];
+            un[(size_t)r * N + m] = x;
+            if (d.uss) d.uss[((size_t)(s + 1) * N + m) * d.du + r] = x;
+        }
+    }
+    const float l = lg_loglik<DMAX>(t, u, v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
+    d.lw[m] = l;
+    float mx, sx;
+    {   // the tile's (max, sumexp): block_lse_partial per tile
+        const int wv = (threadIdx.x >> 6) & 3, h4 = half * 4;
+        const float mw = wave_max(l);
+        if (lane == 0) part[0][h4 + wv] = mw;
+        __syncthreads();
+        mx = fmaxf(fmaxf(part[0][h4], part[0][h4 + 1]), fmaxf(part[0][h4 + 2], part[0][h4 + 3]));
+        TreePath pth;
+        const float sw_ = wave_upsweep(fbsmi_expf(l - finite_or_zero_f(mx)), pth);
         if (lane == 0) part[1][h4 + wv] = sw_;
         __syncthreads();
         sx = (part[1][h4] + part[1][h4 + 1]) + (part[1][h4 + 2] + part[1][h4 + 3]);
@@ -3599,7 +3782,7 @@ struct fbsmi_lg_sweep {
     int two_slot_prop = -1;  // FBSMI_TWO_SLOT_PROP=0|1: never / always (where applicable) k_lg_prop2; unset: by batch size
     bool tree_step = true;  // FBSMI_TREE_STEP=0: keep the cdf launch also where the two-launch step applies
     bool tree_plus1 = true;  // FBSMI_TREE_PLUS1=0: no two-launch step for N = 2^k + 1
-    int tree_halves = -1;   // FBSMI_TREE_HALVES=1|2|4: tiles per workgroup of k_lg_prop1t (unset: as many as there are tiles per CU, up to 4)
+    int tree_halves = -1;   // FBSMI_TREE_HALVES=1|2|4: tiles per workgroup of k_lg_prop1t / k_lg_prop1tp (unset: two from two tiles per CU on)
     bool pin = true;        // FBSMI_PIN=0: no pinned launches of the narrow two-launch step (LgDev.pin)
     bool wide_pin = true;   // FBSMI_WIDE_PIN=0: no pinned launches of the one-tile wide step
     bool em = false;     // fbsmi_lg_sweep_set_em_forward: Euler-Maruyama forward paths (k_lg_em_noise, k_lg_em_path)
@@ -3814,8 +3997,9 @@ void sweep_steps_narrow(fbsmi_lg_sweep* s, hipStream_t st) {
     const LgDev& d = s->d;
     const int nb = d.nb;
     const dim3 gtile(nb, d.C);
-    // enough workgroups that instruction issue, not latency, bounds the step (measured crossover: between four and six
-    // 256-slot workgroups per CU): two slots per thread, three Threefry calls instead of six
+    // enough workgroups that instruction issue, not latency, bounds the step (measured crossover: between four and five
+    // 256-slot workgroups per CU -- 1024 tiles per launch 23.1 against 24.2 G particle-steps/s for k_lg_prop1tp<., 2>, 1280
+    // tiles 24.5 against 20.9 for k_lg_prop1tp<., 4>): two slots per thread, three Threefry calls instead of six
     const bool two_slot = s->items == 1 && d.N % (2 * kBlock) == 0 &&
                           (s->two_slot_prop == 1 || (s->two_slot_prop < 0 && (int64_t)nb * d.C >= 5 * 256));
     // N a power of two: the searches walk the summation tree, no cdf launch (k_lg_prop1t)
@@ -3825,14 +4009,16 @@ void sweep_steps_narrow(fbsmi_lg_sweep* s, hipStream_t st) {
         ProfScope p(s, 2, st);
         if (tree && two_slot && !d.plus1) {
             LG_DMAX(s, k_lg_prop2t<DMAX><<<dim3(nb / 2, d.C), kBlock, 0, st>>>(d, k));
-        } else if (tree && !d.plus1 && nb % 4 == 0 && (s->tree_halves == 4 || (s->tree_halves < 0 && (int64_t)nb * d.C >= 4 * 256))) {
-            // four tiles per 1024-thread workgroup once there are four tiles per CU (measured 8.57 against 8.80 ms per
-            // 4-chain sweep with two; a single chain is fastest with one tile per workgroup)
-            LG_DMAX(s, k_lg_prop1t<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k));
+        } else if (tree && !d.plus1 && nb % 4 == 0 && s->tree_halves == 4) {
+            // four tiles (two pairs N/2 apart) per 1024-thread workgroup: on request only.  With tiles N/2 apart it no longer
+            // wins where it used to be the rule (four tiles per CU, 1024 tiles per launch: 22.4 against 24.2 G particle-steps/s
+            // with two, 8 chains as two launches of four) nor below (512 tiles per launch: 14.7 against 16.5).
+            LG_DMAX(s, k_lg_prop1tp<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k));
         } else if (tree && !d.plus1 && nb % 2 == 0 && (s->tree_halves == 2 || (s->tree_halves < 0 && (int64_t)nb * d.C >= 2 * 256))) {
-            // two adjacent tiles per 512-thread workgroup: half the waves skip the tree building (measured +2 % at 4 chains,
-            // -1 % for a single chain, which keeps one tile per workgroup)
-            LG_DMAX(s, k_lg_prop1t<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k));
+            // two tiles N/2 apart per 512-thread workgroup: half the waves skip the tree building and draw the noise of both
+            // tiles meanwhile, one Threefry call per pair of slots (512 tiles per launch, 4 chains as two groups: 16.5 G
+            // particle-steps/s against 15.6 with one tile per workgroup; a single chain keeps one tile per workgroup)
+            LG_DMAX(s, k_lg_prop1tp<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k));
         } else if (tree) {
             LG_DMAX(s, k_lg_prop1t<DMAX, 1><<<dim3(nb * (d.pin ? 8 : 1), d.C), kBlock, 0, st>>>(d, k));
         } else if (two_slot) {
