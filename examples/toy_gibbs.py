@@ -34,9 +34,6 @@ def main(argv=None):
     parser.add_argument('--outdir', type=str, default='./toy/results')
     parser.add_argument('--quiet', action='store_true')
     args = parser.parse_args(argv)
-    if args.marg:
-        raise NotImplementedError('--marg routes through the closure tier (fbs_amd.samplers.gibbs_kernel with '
-                                  'marg_y=True); this driver covers the fused configurations of the shipped scripts')
     dev = torch.device('cuda:0')
     key = ops.PRNGKey(args.id)                                                   # gp_gibbs.py:30
 
@@ -76,7 +73,8 @@ def main(argv=None):
     bs_stars = np.zeros((nchains, nsteps + 1), np.int32)
 
     # Gibbs loop, gp_gibbs.py:180-190: per iteration key, subkey = split(key); key_chains = split(subkey, nchains)
-    sweep = bridge.sweep_handle(nparticles, args.explicit_backward, args.explicit_final, nchains=nchains)
+    # (--marg: gibbs_kernel(marg_y=True), the observation path re-drawn by the Doob bridge inside every fused sweep, gp_gibbs.py:167)
+    sweep = bridge.sweep_handle(nparticles, args.explicit_backward, args.explicit_final, nchains=nchains, marg_y=args.marg)
     key, x0s, bs_stars, samples = sweep.chain(key, x0s, y0, bs_stars, nsamples)
     gibbs_samples = samples.permute(1, 0, 2).cpu().numpy()                          # (nchains, nsamples, d)
     if not args.quiet:

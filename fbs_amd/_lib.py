@@ -142,6 +142,10 @@ class EMForwardStruct(C.Structure):
     _fields_ = [("nsub", C.c_int32), ("M", C.c_void_p), ("c", C.c_void_p), ("ddt", C.c_void_p), ("s", C.c_void_p)]
 
 
+class DoobBridgeStruct(C.Structure):
+    _fields_ = [("nsub", C.c_int32), ("A", C.c_void_p), ("B", C.c_void_p), ("S", C.c_void_p), ("ddt", C.c_void_p)]
+
+
 class LGPmcmcTablesStruct(C.Structure):
     _fields_ = [("m_u", C.c_void_p), ("m_v", C.c_void_p), ("gain", C.c_void_p), ("chol", C.c_void_p),
                 ("mean_coef", C.c_void_p), ("c0", C.c_float), ("beta", C.c_float), ("one_minus_beta", C.c_float),
@@ -205,6 +209,7 @@ SIGNATURES = {
     "fbsmi_lg_gibbs_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_int, _vp]),
     "fbsmi_lg_sweep_set_group": (C.c_int, [_vp, _i32, _i32]),
     "fbsmi_lg_sweep_set_em_forward": (C.c_int, [_vp, C.POINTER(EMForwardStruct)]),
+    "fbsmi_lg_sweep_set_bridge": (C.c_int, [_vp, C.POINTER(DoobBridgeStruct)]),
     "fbsmi_lg_gibbs_chain_groups": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, C.c_int, _vp]),
     "fbsmi_lg_sweep_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
     "fbsmi_lg_filter_create": (C.c_int, [C.POINTER(LGModelStruct), _i32, C.c_int, C.c_int, C.c_int, _i32, C.POINTER(_vp)]),

@@ -84,7 +84,7 @@ struct LgDev {
     int32_t* bs;     // [C][T+1]
     // derived per sweep
     uint32_t* keytab;  // [T][8]: key_1, key_2, key_3 of the killing resampler, key_transition
-    uint32_t* misc;    // [16]: 0 key_fwd, 2 key_init, 4 key_x0(force_move), 6 key_us, 8 key_bs, 10 key_bwd
+    uint32_t* misc;    // [16]: 0 key_fwd, 2 key_init, 4 key_x0(force_move), 6 key_us, 8 key_bs, 10 key_bwd, 12 key_bridge
     float* xi1;        // [T][D] noise of the first forward path
     float* xi2;        // [T][D] noise of the second forward path (us_star_next)
     float* path;       // [T+1][D]
@@ -217,7 +217,8 @@ __global__ void __launch_bounds__(kBlock) k_lg_keys(LgDev dd, int chain) {
         }
         uint32_t f0, f1, c0, c1;
         split_at(k0, k1, 3, 0, f0, f1);  // key_fwd
-        split_at(k0, k1, 3, 1, c0, c1);  // key_csmc  (key_bridge unused: marg_y=False)
+        split_at(k0, k1, 3, 1, c0, c1);  // key_csmc
+        split_at(k0, k1, 3, 2, d.misc[12], d.misc[13]);  // key_bridge (read by k_lg_bridge_noise alone: marg_y=True)
         uint32_t cf0, cf1;
         if (d.eb) {
             split_at(c0, c1, 4, 0, cf0, cf1);                    // key_csmc_fwd
@@ -371,6 +372,146 @@ __global__ void __launch_bounds__(kEmPathMaxD) k_lg_em_path(LgDev dd, EmDev e, i
             d.acc[k] = b != d.bs[k];
             d.bsn[k] = b;
         }
+    }
+}
+
+// marg_y=True (fbsmi_lg_sweep_set_bridge; gibbs.py:17-20,130): after k_lg_path(which = 0) the observation path vs is
+// replaced by the time-reversed Doob bridge from path_y[0] to path_y[T], Euler-Maruyama with nsub sub-steps per interval
+// (the arithmetic of k_affine_em_path, fbsmi_sde.hip).  The recurrence is serial in all T * nsub sub-steps, so everything
+// that is not the recurrence is done beforehand and in parallel: the handle's own tables (k_lg_bridge_pack, once) and the
+// scaled noise (k_lg_bridge_noise, every sweep, dependent on the key alone).
+constexpr int kBridgeChunk = 16;   // sub-steps whose operands k_lg_bridge fetches at once, one chunk ahead of their use
+
+// The handle's tables are laid out in whole chunks: every interval's nsub rows padded to Np = a multiple of kBridgeChunk,
+// row k * Np + j for sub-step j of interval k, plus one chunk at the end (the fetch that runs one chunk ahead never needs
+// a bound).  The pad is zero, fetched and never applied.
+struct BridgeDev {
+    int nsub;
+    int Np;            // nsub rounded up to kBridgeChunk
+    int Rp;            // T * Np + kBridgeChunk: rows of the tables
+    const float* tA;   // [Rp] A[r]
+    const float* tB;   // [Rp] B[r]
+    const float* tH;   // [Rp] ddt[k]
+    const float* tSq;  // [Rp] S[r] * fbsmi_sqrtf(ddt[k])
+    float* sn;         // [C][dv][Rp]: (S[r] * sq) * xi of every sub-step -- coordinate-major, so that the one thread that owns
+                       // coordinate c reads its operands as consecutive 16-byte words
+};
+
+__global__ void k_lg_bridge_pack(const float* A, const float* B, const float* S, const float* ddt, int R, BridgeDev b, float* tA,
+                                 float* tB, float* tH, float* tSq) {
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < R; r += gridDim.x * blockDim.x) {
+        const int k = r / b.nsub, rp = k * b.Np + (r - k * b.nsub);
+        const float h = ddt[k];
+        tA[rp] = A[r];
+        tB[rp] = B[r];
+        tH[rp] = h;
+        tSq[rp] = S[r] * fbsmi_sqrtf(h);
+    }
+}
+
+// Interval k draws normal(split(key_bridge, T)[k], (nsub, dv)): n = nsub * dv elements, of which i and i + half
+// (half = (n + 1) / 2) are the two words of ONE block-cipher call; an odd n leaves the last call's second word unused
+// (random_bits_pair_padded).  One thread per call, T * half calls in all.  The interval keys a workgroup's calls need (two
+// as a rule, at most one per call) are derived once per workgroup into LDS, not once per thread.
+__global__ void __launch_bounds__(kBlock) k_lg_bridge_noise(LgDev dd, BridgeDev b) {
+    const LgDev d = chain_view(dd, blockIdx.y);
+    __shared__ uint32_t sk[2 * kBlock];
+    const int n = b.nsub * d.dv, half = (n + 1) >> 1;
+    const int64_t calls = (int64_t)d.T * half;
+    float* sn = b.sn + (size_t)d.dv * b.Rp * blockIdx.y;
+    const uint32_t kb0 = d.misc[12], kb1 = d.misc[13];
+    for (int64_t q0 = (int64_t)blockIdx.x * kBlock; q0 < calls; q0 += (int64_t)gridDim.x * kBlock) {   // (uniform in the workgroup)
+        const int64_t qlast = q0 + kBlock - 1 < calls ? q0 + kBlock - 1 : calls - 1;
+        const int kfirst = (int)(q0 / half), klast = (int)(qlast / half);
+        __syncthreads();
+        if ((int)threadIdx.x <= klast - kfirst) split_at(kb0, kb1, d.T, kfirst + threadIdx.x, sk[2 * threadIdx.x], sk[2 * threadIdx.x + 1]);
+        __syncthreads();
+        const int64_t q = q0 + threadIdx.x;
+        if (q < calls) {
+            const int k = (int)(q / half), i = (int)(q - (int64_t)k * half);
+            uint32_t lo, hi;
+            random_bits_pair_padded(sk[2 * (k - kfirst)], sk[2 * (k - kfirst) + 1], (uint64_t)n, (uint64_t)i, lo, hi);
+            const int j = i / d.dv, rp = k * b.Np + j;
+            sn[(size_t)(i - j * d.dv) * b.Rp + rp] = b.tSq[rp] * normal_from_bits(lo);
+            const int i2 = i + half;
+            if (i2 < n) {
+                const int j2 = i2 / d.dv, rp2 = k * b.Np + j2;
+                sn[(size_t)(i2 - j2 * d.dv) * b.Rp + rp2] = b.tSq[rp2] * normal_from_bits(hi);
+            }
+        }
+    }
+}
+
+// the operands of one chunk of sub-steps, as fetched
+struct BridgeOps {
+    float4 A[kBridgeChunk / 4], B[kBridgeChunk / 4], H[kBridgeChunk / 4], Z[kBridgeChunk / 4];
+};
+
+// sub-steps 0 .. lim-1 of a chunk (FULL: all of them, no test)
+template <bool FULL>
+__device__ __forceinline__ float bridge_chunk(const BridgeOps& o, float x, float tg, int lim) {
+    float a[kBridgeChunk], bt[kBridgeChunk], h[kBridgeChunk], z[kBridgeChunk];
+#pragma unroll
+    for (int j = 0; j < kBridgeChunk / 4; ++j) {
+        a[4 * j] = o.A[j].x; a[4 * j + 1] = o.A[j].y; a[4 * j + 2] = o.A[j].z; a[4 * j + 3] = o.A[j].w;
+        bt[4 * j] = o.B[j].x * tg; bt[4 * j + 1] = o.B[j].y * tg; bt[4 * j + 2] = o.B[j].z * tg; bt[4 * j + 3] = o.B[j].w * tg;
+        h[4 * j] = o.H[j].x; h[4 * j + 1] = o.H[j].y; h[4 * j + 2] = o.H[j].z; h[4 * j + 3] = o.H[j].w;
+        z[4 * j] = o.Z[j].x; z[4 * j + 1] = o.Z[j].y; z[4 * j + 2] = o.Z[j].z; z[4 * j + 3] = o.Z[j].w;
+    }
+#pragma unroll
+    for (int j = 0; j < kBridgeChunk; ++j) {
+        if (FULL || j < lim) {
+            const float drift = a[j] * x + bt[j];
+            x = (x + drift * h[j]) + z[j];
+        }
+    }
+    return x;
+}
+
+// One thread per observed coordinate.  Per sub-step the dependent chain is A x -> + bt -> * h -> x + -> + sn; bt = B[r] tg is
+// formed off it, sn comes ready from k_lg_bridge_noise.  A chunk's operands are fetched while the chunk before it is folded
+// in (k_lg_path's scheme), into two register sets used in turn, so nothing is copied; the wave issues in order, so what
+// counts is the instruction count per sub-step: 6 vector operations, a quarter of a load, and the bookkeeping once per chunk.
+// Only the last chunk of an interval (nsub not a multiple of kBridgeChunk) tests its sub-steps.  Interval k's end value goes
+// to vs[T-1-k]; vs[0] keeps the target (replace=True), vs[T] the start.
+__global__ void __launch_bounds__(128) k_lg_bridge(LgDev dd, BridgeDev b) {
+    const LgDev d = chain_view(dd, blockIdx.y);
+    const int c = threadIdx.x;
+    if (c >= d.dv) return;
+    const float4* sn = reinterpret_cast<const float4*>(b.sn + ((size_t)d.dv * blockIdx.y + c) * b.Rp);
+    const float4 *tA = reinterpret_cast<const float4*>(b.tA), *tB = reinterpret_cast<const float4*>(b.tB),
+                 *tH = reinterpret_cast<const float4*>(b.tH);
+    const float tg = d.vs[c];
+    float x = d.vs[(size_t)d.T * d.dv + c];
+    const int cpi = b.Np / kBridgeChunk, total = d.T * cpi;   // chunks per interval, chunks in all
+    auto fetch = [&](BridgeOps& o, int g) {                   // chunk g <= total (the last one is the pad)
+#pragma unroll
+        for (int j = 0; j < kBridgeChunk / 4; ++j) {
+            const int i = g * (kBridgeChunk / 4) + j;
+            o.A[j] = tA[i];
+            o.B[j] = tB[i];
+            o.H[j] = tH[i];
+            o.Z[j] = sn[i];
+        }
+    };
+    int k = 0, m = 0;   // the current interval and the chunk of it
+    auto fold = [&](const BridgeOps& o) {
+        const int lim = b.nsub - m * kBridgeChunk;
+        x = lim >= kBridgeChunk ? bridge_chunk<true>(o, x, tg, lim) : bridge_chunk<false>(o, x, tg, lim);
+        if (++m == cpi) {
+            if (k < d.T - 1) d.vs[(size_t)(d.T - 1 - k) * d.dv + c] = x;
+            ++k;
+            m = 0;
+        }
+    };
+    BridgeOps p, q;
+    fetch(p, 0);
+    for (int g = 0; g < total; g += 2) {
+        fetch(q, g + 1);
+        fold(p);
+        if (g + 1 >= total) break;
+        fetch(p, g + 2);
+        fold(q);
     }
 }
 
@@ -3787,6 +3928,8 @@ struct fbsmi_lg_sweep {
     bool wide_pin = true;   // FBSMI_WIDE_PIN=0: no pinned launches of the one-tile wide step
     bool em = false;     // fbsmi_lg_sweep_set_em_forward: Euler-Maruyama forward paths (k_lg_em_noise, k_lg_em_path)
     EmDev emd{};
+    bool bridge = false; // fbsmi_lg_sweep_set_bridge: marg_y=True, vs re-drawn by the Doob bridge (k_lg_bridge_noise, k_lg_bridge)
+    BridgeDev brd{};
     std::vector<hipEvent_t> prof_ev[kNumProfKernels];  // pairs (start, stop)
     double prof_us[kNumProfKernels] = {0, 0, 0};
     int64_t prof_n[kNumProfKernels] = {0, 0, 0};
@@ -3912,7 +4055,10 @@ void sweep_prologue(fbsmi_lg_sweep* s, hipStream_t st, int chain, const WideGeom
         k_lg_em_path<<<dim3(1, d.C), (unsigned)((d.D + 63) / 64 * 64), 0, st>>>(d, s->emd, 0);
     } else {
         k_lg_noise<<<dim3(grid_1d((int64_t)d.T * d.D, 256, 1024), d.C), 256, 0, st>>>(d);
+        if (s->bridge)   // (needs the key alone: ahead of the path, whose end points the recurrence waits for)
+            k_lg_bridge_noise<<<dim3(grid_1d((int64_t)d.T * ((s->brd.nsub * d.dv + 1) / 2), kBlock, 1024), d.C), kBlock, 0, st>>>(d, s->brd);
         k_lg_path<<<dim3((d.D + 63) / 64, d.C), 64, 0, st>>>(d, 0);
+        if (s->bridge) k_lg_bridge<<<dim3(1, d.C), (unsigned)((d.dv + 63) / 64 * 64), 0, st>>>(d, s->brd);
     }
     if (d.wide) {
         k_lgw_init<<<gtile, kBlock, 0, st>>>(d);
@@ -4384,6 +4530,31 @@ int fbsmi_lg_sweep_set_em_forward(fbsmi_lg_sweep* s, const fbsmi_em_forward* f) 
     s->emd.t = EmTables{f->nsub, f->M, f->c, f->ddt, f->s};
     s->emd.xi = xi;
     s->em = true;
+    return FBSMI_OK;
+}
+
+int fbsmi_lg_sweep_set_bridge(fbsmi_lg_sweep* s, const fbsmi_doob_bridge* b) {
+    if (!s || !b || b->nsub < 1 || !b->A || !b->B || !b->S || !b->ddt)
+        return fail(FBSMI_ERR_ARG, "lg_sweep_set_bridge: bad arguments");
+    if (s->em)
+        return fail(FBSMI_ERR_UNSUPPORTED, "lg_sweep_set_bridge: a handle with an Euler-Maruyama forward process has no scalar linear SDE to bridge");
+    if (s->graph_single || s->graph_chain || s->bridge)
+        return fail(FBSMI_ERR_ARG, "lg_sweep_set_bridge: call it once, before the handle's first sweep");
+    const LgDev& d = s->d;
+    if (((int64_t)d.T * (b->nsub + kBridgeChunk) + kBridgeChunk) * d.dv > 2147483647ll)
+        return fail(FBSMI_ERR_UNSUPPORTED, "lg_sweep_set_bridge: T * nsub * dv does not fit 31 bits");
+    const int R = d.T * b->nsub, Np = (b->nsub + kBridgeChunk - 1) / kBridgeChunk * kBridgeChunk, Rp = d.T * Np + kBridgeChunk;
+    float *tab = nullptr, *sn = nullptr;
+    if (dev_alloc(s, &tab, 4 * (size_t)Rp) || dev_alloc(s, &sn, (size_t)d.C * d.dv * Rp)) return FBSMI_ERR_HIP;
+    const BridgeDev bd{b->nsub, Np, Rp, tab, tab + Rp, tab + 2 * (size_t)Rp, tab + 3 * (size_t)Rp, sn};
+    // the workspace's zeroing and the caller's table uploads may be pending on other streams
+    FBSMI_HIP_TRY(hipDeviceSynchronize());
+    k_lg_bridge_pack<<<grid_1d(R, 256, 1024), 256, 0, s->stream>>>(b->A, b->B, b->S, b->ddt, R, bd, tab, tab + Rp, tab + 2 * (size_t)Rp,
+                                                                   tab + 3 * (size_t)Rp);
+    if (int rc = launch_status("lg_sweep_set_bridge")) return rc;
+    FBSMI_HIP_TRY(hipStreamSynchronize(s->stream));
+    s->brd = bd;
+    s->bridge = true;
     return FBSMI_OK;
 }
 

@@ -12,7 +12,7 @@ the GPU, and exposes
 * the reference's closures (``transition_sampler``, ``transition_logpdf``, ``likelihood_logpdf``,
   ``fwd_sampler``, ``fwd_ys_sampler``, ``unpack``, ``ref_sampler``) with the reference's
   signatures, each one a HIP kernel launch;
-* the fused whole-sweep engine (``gibbs_kernel`` / ``gibbs_chain``), which
+* the fused whole-sweep engine (``gibbs_kernel`` / ``sweep_handle(...).chain``, with or without ``marg_y``), which
   ``fbs_amd.samplers.gibbs_kernel`` dispatches to when it is handed these closures.
 """
 from __future__ import annotations
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .sdes.linear import LinearSDE, discretise_linear_sde_np
+from .sdes.linear import LinearSDE, discretise_linear_sde_np, doob_bridge_tables
 
 
 def lg_tables(m0, cov0, sde: LinearSDE, ts, du: int, dt: Optional[float] = None) -> dict:
@@ -238,10 +238,32 @@ class LinearGaussianBridge:
             h = self._sweeps[keyt] = make()
         return h
 
+    def fused_marg_y_supported(self) -> bool:
+        """What fbsmi_lg_sweep_set_bridge accepts: a model with a scalar linear SDE to bridge and the exact forward
+        transition (a model with an Euler-Maruyama forward process has neither)."""
+        return getattr(self, "em_struct", None) is None and self.sde is not None
+
+    def bridge_tables(self, nsub: int = 100):
+        """The device copy of doob_bridge_tables(sde, ts, nsub) -- the float32 tables doob_bridge_simulator feeds its kernel
+        -- as an fbsmi_doob_bridge struct (cached; the struct keeps its arrays alive through ``_keep``; ``_host`` is the
+        host copy)."""
+        if not self.fused_marg_y_supported():
+            raise NotImplementedError("marg_y needs the Doob bridge of a scalar linear SDE; this model has none")
+
+        def make():
+            tab = doob_bridge_tables(self.sde, self.ts_np, nsub)
+            dev = {k: torch.from_numpy(tab[k]).to(self.device) for k in ("A", "B", "S", "ddt")}
+            st = _lib.DoobBridgeStruct(int(nsub), *(dev[k].data_ptr() for k in ("A", "B", "S", "ddt")))
+            st._keep, st._host = dev, tab
+            return st
+
+        return self._cached(("bridge_tables", int(nsub)), make)
+
     def sweep_handle(self, nparticles: int, explicit_backward=True, explicit_final=False, store_path=None,
-                     nchains: int = 1):
+                     nchains: int = 1, marg_y: bool = False):
+        """marg_y: every sweep re-draws the observation path by the Doob bridge (bridge_sampler, gibbs.py:17-20,130)."""
         store = (not explicit_backward) if store_path is None else bool(store_path)
-        keyt = (int(nparticles), bool(explicit_backward), bool(explicit_final), store, int(nchains))
+        keyt = (int(nparticles), bool(explicit_backward), bool(explicit_final), store, int(nchains), bool(marg_y))
         return self._cached(keyt, lambda: LGSweep(self, *keyt))
 
     def filter_handle(self, nparticles: int, flow: str, resampling: str = "stratified", store_path: bool = False,
@@ -285,9 +307,9 @@ class LinearGaussianBridge:
         return self._cached(keyt, lambda: LGPmcmc(self, int(nparticles), resampling, int(nchains), delta, int(which_u)))
 
     def gibbs_kernel(self, key, x0, y0, bs_star, nparticles, explicit_backward=True, explicit_final=False,
-                     use_graph=True):
+                     use_graph=True, marg_y=False):
         """One fused sweep; same returns as fbs.samplers.gibbs_kernel: (x0, us_star, bs_star, acc)."""
-        h = self.sweep_handle(nparticles, explicit_backward, explicit_final)
+        h = self.sweep_handle(nparticles, explicit_backward, explicit_final, marg_y=marg_y)
         return h.sweep(key, x0, y0, bs_star, use_graph=use_graph)
 
 
@@ -329,9 +351,10 @@ class LGSweep(_LGHandle):
 
     _DESTROY = "fbsmi_lg_sweep_destroy"
 
-    def __init__(self, model: LinearGaussianBridge, nparticles, eb, ef, store, nchains=1, _group=None):
+    def __init__(self, model: LinearGaussianBridge, nparticles, eb, ef, store, nchains=1, marg_y=False, _group=None):
         self.model = model
         self.nparticles, self.eb, self.ef, self.store, self.C = nparticles, eb, ef, store, int(nchains)
+        self.marg_y = bool(marg_y)
         self.n_rows = nparticles + 1 if ef else nparticles
         self.children, self.h = [], None
         # A batch of four or more chains is driven as two handles of half the chains each, on their own streams: the step
@@ -365,7 +388,7 @@ class LGSweep(_LGHandle):
                 sz = [self.C // G + (1 if g < self.C % G else 0) for g in range(G)]
         if sz is not None and len(sz) > 1:
             first = np.cumsum([0] + sz[:-1])
-            self.children = [LGSweep(model, nparticles, eb, ef, store, n, _group=(self.C, int(f))) for n, f in zip(sz, first)]
+            self.children = [LGSweep(model, nparticles, eb, ef, store, n, marg_y, _group=(self.C, int(f))) for n, f in zip(sz, first)]
             self._harr = (C.c_void_p * len(sz))(*[c.h for c in self.children])
             return
         h = C.c_void_p()
@@ -376,6 +399,8 @@ class LGSweep(_LGHandle):
             em = getattr(model, "em_struct", None)   # Euler-Maruyama forward process (fbs_amd.gaussian_sb.GaussianSBBridge)
             if em is not None:
                 _lib.call("fbsmi_lg_sweep_set_em_forward", self.h, C.byref(em))
+            if self.marg_y:     # the Doob bridge of the observation path, 100 sub-steps per interval (gibbs.py:17-20)
+                _lib.call("fbsmi_lg_sweep_set_bridge", self.h, C.byref(model.bridge_tables(100)))
         if _group is not None:
             _lib.call("fbsmi_lg_sweep_set_group", self.h, int(_group[0]), int(_group[1]))
 

@@ -1,9 +1,9 @@
 """The forward-backward Gibbs sampler (fbs/samplers/gibbs.py).
 
 ``gibbs_kernel`` keeps the reference's signature.  When the closures it receives come from a
-``fbs_amd.LinearGaussianBridge`` (analytic score) the whole sweep -- forward noising, T-step
-conditional SMC with killing resampling, forced move, fresh reference trajectory -- runs fused on
-the device as one hipGraph replay.  Any other closures take the generic tier: a host loop whose
+``fbs_amd.LinearGaussianBridge`` (analytic score) the whole sweep -- forward noising, with
+``marg_y`` the Doob bridge of the observation path, T-step conditional SMC with killing resampling, forced move,
+fresh reference trajectory -- runs fused on the device as one hipGraph replay.  Any other closures take the generic tier: a host loop whose
 sampler-side operations are HIP kernels.
 """
 from __future__ import annotations
@@ -97,12 +97,19 @@ def gibbs_kernel(key, x0, y0, us_star, bs_star, ts, fwd_sampler, sde, unpack, np
     Returns (x0, us_star, bs_star, acc) like the reference."""
     # the fused engine runs the model's OWN grid, SDE and split: take it only when the caller passed exactly those
     model = _lg_model_of(fwd_sampler, transition_sampler, likelihood_logpdf, unpack)
-    # (with marg_y=False the reference never touches `sde` (gibbs.py:130) and its drivers may pass None, experiments/sb/gibbs.py:171)
-    if model is not None and not marg_y and not kwargs and (sde is None or _same_sde(sde, model.sde)) and model.same_grid(ts) and \
+    # (with marg_y=False the reference never touches `sde` (gibbs.py:130) and its drivers may pass None, experiments/sb/gibbs.py:171;
+    # with marg_y=True the bridge is the SDE's, so it must be the model's own, and the model must have one to bridge)
+    if model is None:
+        sde_ok = False
+    elif marg_y:
+        sde_ok = sde is not None and model.fused_marg_y_supported() and _same_sde(sde, model.sde)
+    else:
+        sde_ok = sde is None or _same_sde(sde, model.sde)
+    if sde_ok and not kwargs and model.same_grid(ts) and \
             (explicit_backward or _lg_model_of(transition_logpdf) is model) and \
             model.fused_sweep_supported(nparticles, explicit_final):
         with torch.cuda.device(model.device):
-            return model.gibbs_kernel(key, x0, y0, bs_star, nparticles, explicit_backward, explicit_final)
+            return model.gibbs_kernel(key, x0, y0, bs_star, nparticles, explicit_backward, explicit_final, marg_y=marg_y)
 
     key_fwd, key_csmc, key_bridge = ops.split(key, 3)                               # :126
     path_xy = fwd_sampler(key_fwd, x0, y0, **kwargs)                                # :127

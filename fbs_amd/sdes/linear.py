@@ -35,6 +35,26 @@ def _bridge_drift_coeffs(sde, t, T):
     return a - b2 * F * F / Q, b2 * F / Q
 
 
+def doob_bridge_tables(sde, ts, nsub: int) -> dict:
+    """Coefficient tables of the Doob bridge of a scalar linear SDE on the grid ts with nsub Euler-Maruyama sub-steps per
+    interval (doob_bridge_simulator, fbs/sdes/simulators.py:126-160): A, B (bridge drift A x + B target) and S (the
+    dispersion) at every sub-step time, [T * nsub]; ddt [T] the sub-step length of every interval.  Evaluated in float64
+    on the host and rounded ONCE to float32 -- what both the stand-alone simulator and the fused sweep feed their kernels."""
+    ts_np = _as_np(ts).reshape(-1)
+    T, nsub = ts_np.size - 1, int(nsub)
+    Tend = float(ts_np[-1])
+    A, B, S, ddt = np.zeros(T * nsub), np.zeros(T * nsub), np.zeros(T * nsub), np.zeros(T)
+    for k in range(T):
+        t, t_next = float(ts_np[k]), float(ts_np[k + 1])
+        h = abs(t_next - t) / nsub
+        ddt[k] = h
+        for j, t_ in enumerate(np.linspace(t, t_next - h, nsub)):
+            A[k * nsub + j], B[k * nsub + j] = _bridge_drift_coeffs(sde, float(t_), Tend)
+            S[k * nsub + j] = float(sde.dispersion(float(t_)))
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    return dict(nsub=nsub, A=f32(A), B=f32(B), S=f32(S), ddt=f32(ddt))
+
+
 class StationaryConstLinearSDE(LinearSDE):
     """dX(t) = a X(t) dt + b dW(t), where `b^2 / a = 2 sigma^2`.  (fbs/sdes/linear.py:13-45)"""
 

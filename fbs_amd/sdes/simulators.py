@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
-from .linear import LinearSDE, _as_np, _bridge_drift_coeffs
+from .linear import LinearSDE, _as_np, doob_bridge_tables
 
 
 def reverse_simulator(key, u0, ts, score, drift, dispersion, integration_nsteps: int = 1,
@@ -91,7 +91,7 @@ def doob_bridge_simulator(key, sde: LinearSDE, x0, xT, ts, integration_nsteps: i
     """Doob h-transform bridge of a linear SDE from x0 to xT (fbs/sdes/simulators.py:126-160).
 
     bridge_drift(x, t) = A(t) x + B(t) xT is affine in x, so the path is one kernel launch: the
-    host tabulates A, B and the dispersion at every sub-step time (float64 -> float32)."""
+    host tabulates A, B and the dispersion at every sub-step time (float64 -> float32, doob_bridge_tables)."""
     ts_np = _as_np(ts).reshape(-1)
     T = ts_np.size - 1
     nsub = int(integration_nsteps)
@@ -102,22 +102,11 @@ def doob_bridge_simulator(key, sde: LinearSDE, x0, xT, ts, integration_nsteps: i
     xTt = xTt.to(dev, torch.float32).contiguous()
     shape = tuple(x0t.shape)
     D = x0t.numel()
-    Tend = float(ts_np[-1])
-    A = np.zeros(T * nsub)
-    B = np.zeros(T * nsub)
-    S = np.zeros(T * nsub)
-    ddt = np.zeros(T)
-    for k in range(T):
-        t, t_next = float(ts_np[k]), float(ts_np[k + 1])
-        h = abs(t_next - t) / nsub
-        ddt[k] = h
-        for j, t_ in enumerate(np.linspace(t, t_next - h, nsub)):
-            A[k * nsub + j], B[k * nsub + j] = _bridge_drift_coeffs(sde, float(t_), Tend)
-            S[k * nsub + j] = float(sde.dispersion(float(t_)))
+    tab = doob_bridge_tables(sde, ts_np, nsub)
     keys = ops.split(key, T)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+    up = lambda a: torch.from_numpy(a).to(dev)
     keys_t = torch.from_numpy(keys.view(np.int32).copy()).to(dev)
-    At, Bt, St, ht = up(A), up(B), up(S), up(ddt)
+    At, Bt, St, ht = up(tab["A"]), up(tab["B"]), up(tab["S"]), up(tab["ddt"])
     out = torch.empty((T + 1, D), dtype=torch.float32, device=dev)
     _lib.call("fbsmi_affine_em_path", keys_t.data_ptr(), At.data_ptr(), Bt.data_ptr(), St.data_ptr(), ht.data_ptr(),
               xTt.reshape(-1).data_ptr(), x0t.reshape(-1).data_ptr(), T, nsub, D, int(bool(replace)), out.data_ptr(),

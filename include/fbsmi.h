@@ -180,7 +180,8 @@ int fbsmi_lg_transition_logpdf(const fbsmi_lg_model* m, int32_t k, float sd_k, f
 
 typedef struct fbsmi_lg_sweep fbsmi_lg_sweep; /* opaque: device buffers + captured hipGraph */
 
-/* Create the state for gibbs_kernel sweeps (fbs/samplers/gibbs.py:68-168, marg_y=False) with
+/* Create the state for gibbs_kernel sweeps (fbs/samplers/gibbs.py:68-168; marg_y=False until
+ * fbsmi_lg_sweep_set_bridge switches the handle to marg_y=True) with
  * `nparticles` particles, for `nchains` independent chains batched in every launch -- the
  * reference's jax.vmap over chains (experiments/toy/gp_gibbs.py:25,172-173).  store_path != 0 keeps
  * As / uss / log_wss (needed when explicit_backward == 0).  Allocates device memory (not
@@ -218,6 +219,28 @@ int fbsmi_lg_gibbs_chain_groups(fbsmi_lg_sweep* const* groups, int32_t ngroups, 
  * always.  Call once, before the handle's first sweep; the tables must cover the model's T and D = du + dv and outlive the
  * handle.  Allocates the handle's noise workspace (2 * nchains * T * nsub * D floats). */
 int fbsmi_lg_sweep_set_em_forward(fbsmi_lg_sweep* s, const fbsmi_em_forward* f);
+/* marg_y=True (gibbs.py:17-20,130): every sweep of the handle re-draws the observation path by the Doob bridge of the
+ * scalar linear SDE, bridge_sampler = doob_bridge_simulator(key_bridge, sde, y_0, y_T, ts, integration_nsteps = nsub,
+ * replace = True).  After the forward path of key_fwd has produced path_y, vs = reverse(bridge), where bridge is exactly
+ * what fbsmi_affine_em_path defines with x0 = path_y[0], target = path_y[T], keys split(key_bridge, T), key_bridge =
+ * split(key, 3)[2], replace_last = 1; us_star, the CSMC, the forced move and the second forward path are untouched.
+ * Numeric specification (fbsmi_affine_em_path's, restated; no contraction, every operation separately rounded), for
+ * sub-step j of interval k, r = k * nsub + j, coordinate c, tg = target[c]:
+ *   sq = fbsmi_sqrtf(ddt[k]);  drift = A[r] * x + B[r] * tg;  x = (x + drift * ddt[k]) + (S[r] * sq) * xi,
+ *   xi = element j * dv + c of normal(split(key_bridge, T)[k], (nsub, dv)).
+ * A, B, S: [T * nsub] device float32 (the bridge drift's two scalar coefficients and the dispersion at every sub-step
+ * time), ddt: [T].  Call once, before the handle's first sweep.  The tables are read DURING this call only, after a device-wide
+ * synchronise (they need not outlive it): the handle keeps its own packed copy and allocates the bridge's noise
+ * workspace (nchains * T * nsub * dv floats).  FBSMI_ERR_UNSUPPORTED on a handle with an
+ * Euler-Maruyama forward process (such a model has no scalar linear SDE to bridge). */
+typedef struct fbsmi_doob_bridge {
+    int32_t nsub;
+    const float* A;
+    const float* B;
+    const float* S;
+    const float* ddt;
+} fbsmi_doob_bridge;
+int fbsmi_lg_sweep_set_bridge(fbsmi_lg_sweep* s, const fbsmi_doob_bridge* b);
 /* Parity views of the last sweep: copies view `which` into dst (device, nullable) and reports its
  * element count.  which: 0 final particles (n,du) row-major, 1 final normalised log-weights (n),
  * 2 As (T,n) int32, 3 uss (T+1,n,du), 4 log_wss (T+1,n) [2-4 only with store_path],
