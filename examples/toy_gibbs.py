@@ -68,8 +68,22 @@ def main(argv=None):
                                nparticles, stratified, log=True, return_last=False)[0]
         return uss[-1, 0], bootstrap_backward_smoother(key_bwd, uss, vs, ts, bridge.transition_logpdf)
 
+    # the same for all chains at once: ONE batched filter handle and ONE batched backward-simulation handle, chain c with
+    # exactly the keys gibbs_init(keys_[c]) uses (bootstrap_filter draws the initial particles with split(key_bf)[0])
+    def gibbs_init_batch(keys_):
+        k3 = [ops.split(k, 3) for k in keys_]                                          # key_fwd, key_bwd, key_bf
+        vs = torch.stack([torch.flip(bridge.fwd_ys_sampler(k[0], y0_t), [0]) for k in k3], 0)
+        u0s = torch.stack([bridge.ref_sampler(ops.split(k[2], 2)[0], vs[c, 0], nparticles) for c, k in enumerate(k3)], 0)
+        filt = bridge.filter_handle(nparticles, "bootstrap", "stratified", store_path=True, nchains=nchains)
+        uss = filt.run(np.stack([k[2] for k in k3]), vs, u0s)[2].reshape(nchains, nsteps + 1, nparticles, d)
+        us_stars = bridge.backsim_handle(nparticles, "smoother", nchains).run(np.stack([k[1] for k in k3]), vs, uss)
+        return uss[:, -1, 0], us_stars.reshape(nchains, nsteps + 1, d)
+
     key, subkey = ops.split(key)
-    x0s = torch.stack([gibbs_init(k)[0] for k in ops.split(subkey, nchains)], 0)      # gp_gibbs.py:176-178
+    if bridge.fused_filter_supported(nparticles) and bridge.fused_backsim_supported(nparticles):
+        x0s = gibbs_init_batch(ops.split(subkey, nchains))[0]                         # gp_gibbs.py:176-178
+    else:
+        x0s = torch.stack([gibbs_init(k)[0] for k in ops.split(subkey, nchains)], 0)
     bs_stars = np.zeros((nchains, nsteps + 1), np.int32)
 
     # Gibbs loop, gp_gibbs.py:180-190: per iteration key, subkey = split(key); key_chains = split(subkey, nchains)

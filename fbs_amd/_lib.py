@@ -12,7 +12,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip",
-                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip")]
+                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip", "fbsmi_bs.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", "fbsmi_device.h"), os.path.join(_HERE, "csrc", "fbsmi_host.h"),
                 os.path.join(_HERE, "csrc", "fbsmi_em_path.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi.h"), os.path.join(_HERE, "..", "include", "fbsmi_math.h"),
@@ -220,6 +220,9 @@ SIGNATURES = {
     "fbsmi_lg_pmcmc_destroy": (None, [_vp]),
     "fbsmi_lg_pmcmc_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fbsmi_lg_pmcmc_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "fbsmi_lg_backsim_create": (C.c_int, [C.POINTER(LGModelStruct), _i32, C.c_int, _i32, C.POINTER(_vp)]),
+    "fbsmi_lg_backsim_destroy": (None, [_vp]),
+    "fbsmi_lg_backsim_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fbsmi_tw_create": (C.c_int, [C.POINTER(TWModelStruct), _i32, C.c_int, _i32, C.c_int, C.POINTER(_vp)]),
     "fbsmi_tw_destroy": (None, [_vp]),
     "fbsmi_tw_run": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),

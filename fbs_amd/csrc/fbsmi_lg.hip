@@ -4218,25 +4218,6 @@ int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
     return launch_status("sweep");
 }
 
-// Run `enqueue` on st: directly, or (use_graph) as a graph captured on first use into `slot` and replayed from then on.
-template <typename Enqueue>
-int launch_captured(hipGraphExec_t& slot, hipStream_t st, bool use_graph, Enqueue&& enqueue) {
-    if (!use_graph) return enqueue();
-    if (!slot) {
-        hipGraph_t g = nullptr;
-        FBSMI_HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-        int rc = enqueue();
-        hipError_t e = hipStreamEndCapture(st, &g);
-        if (!rc && e != hipSuccess) rc = fail(FBSMI_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        if (!rc && (e = hipGraphInstantiate(&slot, g, nullptr, nullptr, 0)) != hipSuccess)
-            rc = fail(FBSMI_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-        if (g) (void)hipGraphDestroy(g);
-        if (rc) return rc;
-    }
-    FBSMI_HIP_TRY(hipGraphLaunch(slot, st));
-    return FBSMI_OK;
-}
-
 int run_sweep(fbsmi_lg_sweep* s, int chain, int use_graph) {
     // (no graph while profiling: ProfScope's events belong between the launches)
     return launch_captured(chain ? s->graph_chain : s->graph_single, s->stream, use_graph && !s->profile,

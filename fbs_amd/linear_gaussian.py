@@ -231,6 +231,10 @@ class LinearGaussianBridge:
             return True
         return max(self.du, self.dv) <= 128 and nparticles <= 131072
 
+    def fused_backsim_supported(self, nslots: int) -> bool:
+        """What fbsmi_lg_backsim_create accepts: 1 <= nslots <= 131072 rows per time slice and du, dv <= 128."""
+        return 1 <= int(nslots) <= 131072 and max(self.du, self.dv) <= 128
+
     def _cached(self, keyt, make):
         """Get-or-create in the bridge's cache of engine handles and device tables."""
         h = self._sweeps.get(keyt)
@@ -270,6 +274,12 @@ class LinearGaussianBridge:
                       nchains: int = 1):
         keyt = ("filter", int(nparticles), flow, resampling, bool(store_path), int(nchains))
         return self._cached(keyt, lambda: LGFilter(self, int(nparticles), flow, resampling, bool(store_path), int(nchains)))
+
+    def backsim_handle(self, nslots: int, mode: str, nchains: int = 1):
+        """The fused backward simulation on stored paths of `nslots` rows per time slice: mode 'smoother'
+        (bootstrap_backward_smoother) or 'sampling' (backward_sampling_pass)."""
+        keyt = ("backsim", int(nslots), mode, int(nchains))
+        return self._cached(keyt, lambda: LGBacksim(self, int(nslots), mode, int(nchains)))
 
     def fused_pmcmc_supported(self, nparticles: int) -> bool:
         """What fbsmi_lg_pmcmc_create accepts: the fused filter's sizes, and an exact forward transition (a model with an
@@ -314,7 +324,7 @@ class LinearGaussianBridge:
 
 
 class _LGHandle:
-    """What the three engine handles share: the handle's lifetime (``_DESTROY`` names its destroy entry of libfbsmi) and
+    """What the engine handles share: the handle's lifetime (``_DESTROY`` names its destroy entry of libfbsmi) and
     the staging of a call's keys and tensors.  A subclass sets ``model``, ``C`` (chains) and ``h`` (the handle)."""
 
     _DESTROY = None
@@ -520,6 +530,43 @@ class LGFilter(_LGHandle):
         _lib.call("fbsmi_lg_filter_run", self.h, kt.data_ptr(), vst.data_ptr(), u0t.data_ptr(), uT.data_ptr(),
                   ell.data_ptr(), path.data_ptr() if path is not None else None, int(bool(use_graph)), ops._stream())
         return tuple(self._sq(t) for t in (uT, ell, path) if t is not None)
+
+
+class LGBacksim(_LGHandle):
+    """Fused backward simulation for the analytic model (fbsmi_lg_backsim): bootstrap_backward_smoother (mode 'smoother',
+    smc.py:91-112) or backward_sampling_pass (mode 'sampling', csmc.py:167-227) for `nchains` independent stored paths at
+    once, one hipGraph replay per call.
+
+    With nchains == 1 the chain axis is squeezed from inputs and outputs; with nchains > 1 keys (C,2), vs (C,T+1,dv),
+    path (C,T+1,n,du) and log_wss (C,T+1,n) carry it and so does every output.  ``runs`` counts the calls."""
+
+    _MODE = {"smoother": 0, "sampling": 1}
+    _DESTROY = "fbsmi_lg_backsim_destroy"
+
+    def __init__(self, model: LinearGaussianBridge, nslots, mode, nchains=1):
+        if not model.fused_backsim_supported(nslots):
+            raise NotImplementedError("the fused backward simulation takes 1 <= nslots <= 131072 and du, dv <= 128")
+        self.model, self.n, self.mode, self.C, self.runs = model, int(nslots), self._MODE[mode], int(nchains), 0
+        h = C.c_void_p()
+        with torch.cuda.device(model.device):
+            _lib.call("fbsmi_lg_backsim_create", C.byref(model.struct), self.n, self.mode, self.C, C.byref(h))
+        self.h = h
+
+    def run(self, key, vs, path, log_wss=None, use_graph=True):
+        """-> traj ([C,] T+1, du) (smoother), or (xs ([C,] T+1, du), Bs ([C,] T+1) int32) (sampling).  `path` (and
+        `log_wss`) are read in place."""
+        m, Cn = self.model, self.C
+        kt = self._key_t(key, Cn)
+        vst = self._dev(vs, torch.float32, (Cn, m.T + 1, m.dv))
+        pt = self._dev(path, torch.float32, (Cn, m.T + 1, self.n, m.du))
+        lwt = self._dev(log_wss, torch.float32, (Cn, m.T + 1, self.n)) if self.mode == 1 else None
+        traj = torch.empty((Cn, m.T + 1, m.du), dtype=torch.float32, device=m.device)
+        bs = torch.empty((Cn, m.T + 1), dtype=torch.int32, device=m.device) if self.mode == 1 else None
+        _lib.call("fbsmi_lg_backsim_run", self.h, kt.data_ptr(), vst.data_ptr(), pt.data_ptr(),
+                  lwt.data_ptr() if lwt is not None else None, traj.data_ptr(), bs.data_ptr() if bs is not None else None,
+                  int(bool(use_graph)), ops._stream())
+        self.runs += 1
+        return self._sq(traj) if bs is None else (self._sq(traj), self._sq(bs))
 
 
 class LGPmcmc(_LGHandle):

@@ -77,7 +77,12 @@ def forward_pass(key, us_star, bs_star, vs, ts, init_sampler, init_likelihood_lo
 
 
 def backward_sampling_pass(key, transition_logpdf, vs, ts, uss, log_ws, *args, **kwargs):
-    """Backward sampling pass (csmc.py:167-227)."""
+    """Backward sampling pass (csmc.py:167-227).  With the transition_logpdf of one LinearGaussianBridge on its own
+    grid the whole pass runs fused on the device (LGBacksim); otherwise the host loop."""
+    from ..smc import fused_backsim
+    model = fused_backsim(transition_logpdf, args, kwargs, ts, uss)
+    if model is not None and isinstance(log_ws, torch.Tensor) and tuple(log_ws.shape) == tuple(uss.shape[:2]):
+        return model.backsim_handle(uss.shape[1], "sampling").run(key, vs, uss, log_ws)
     K_plus_one = uss.shape[0]
     keys = ops.split(key, K_plus_one)                                              # :194
     W_T = normalise(log_ws[-1])                                                    # :200

@@ -74,8 +74,26 @@ def bootstrap_filter(transition_sampler, measurement_cond_pdf, vs, ts, init_samp
     return torch.stack(filtering, 0), log_nell
 
 
+def fused_backsim(transition_logpdf, args, kwargs, ts, path):
+    """The model whose fused backward simulation (LGBacksim) applies to a stored float32 path (T+1, n, du): the closure is
+    one LinearGaussianBridge's own transition_logpdf, called without extra arguments on the bridge's own grid, and the
+    engine takes the size; else None."""
+    model = getattr(transition_logpdf, "_fbsmi_lg", None)
+    if model is None or getattr(transition_logpdf, "_role", "") != "transition_logpdf" or args or kwargs:
+        return None
+    if not isinstance(path, torch.Tensor) or path.dtype != torch.float32 or path.dim() != 3:
+        return None
+    if path.shape[0] != model.T + 1 or path.shape[2] != model.du or not model.fused_backsim_supported(path.shape[1]):
+        return None
+    return model if model.same_grid(ts) else None
+
+
 def bootstrap_backward_smoother(key, filter_us, vs, ts, transition_logpdf, *args, **kwargs):
-    """Backward particle smoother on bootstrap-filter output (smc.py:91-112)."""
+    """Backward particle smoother on bootstrap-filter output (smc.py:91-112).  With the transition_logpdf of one
+    LinearGaussianBridge on its own grid the whole pass runs fused on the device (LGBacksim); otherwise the host loop."""
+    model = fused_backsim(transition_logpdf, args, kwargs, ts, filter_us)
+    if model is not None:
+        return model.backsim_handle(filter_us.shape[1], "smoother").run(key, vs, filter_us)
     nsteps = filter_us.shape[0] - 1
     key_last, key_smoother = ops.split(key, 2)                                      # :108
     uT = ops.choice(key, filter_us[-1], axis=0)   # :109 -- the reference draws with the PARENT key

@@ -312,6 +312,37 @@ int fbsmi_lg_pmcmc_chain(fbsmi_lg_pmcmc* h, uint32_t* key, float* uT, float* log
                          int32_t nsamples, float* samples, float* acc_prob, uint8_t* accepted, float* prop_log_ell,
                          float* log_ells, int use_graph, void* stream);
 
+/* ---- fused backward simulation for the analytic model, batched over chains -----------------------
+ * mode 0  bootstrap_backward_smoother (fbs/samplers/smc.py:91-112) on a stored filtering path;
+ * mode 1  backward_sampling_pass (fbs/samplers/csmc/csmc.py:167-227), the backward pass of csmc_kernel(backward=True),
+ *         on the stored particles and normalised log-weights of a CSMC forward pass.
+ * nslots = n, the rows of a time slice (particles; particles + 1 for a CSMC forward pass).  The handle reads only
+ * G, g, sd, lognorm and dt of the model (F and sqQ may be placeholders).  Supported: 1 <= n <= 131072 (one-item
+ * logsumexp tiles, fbsmi_tile_items(n) == 1) and max(du, dv) <= 128; anything else is FBSMI_ERR_UNSUPPORTED.
+ * Numeric specification (no contraction anywhere; every operation separately rounded):
+ *   tlp(t, x, i)   acc_r = g[t][r], then acc_r = fbsmi_fmaf(G[t][r][c], z[c], acc_r) for c ascending over
+ *                  z = (path[t][i], vs[t]);  mean_r = path[t][i][r] + acc_r * dt;
+ *                  lp_r = (lognorm[t] + ((x_r - mean_r) * (x_r - mean_r)) / (sd[t] * sd[t])) / -2;
+ *                  tlp = lp_0, then + lp_r for r = 1 .. du-1                 (transition_logpdf, gp_gibbs.py:124-129);
+ *   lse(x)         the two-level logsumexp of fbsmi_math.h;
+ *   cat(key, w)    c = cumsum(w) in the canonical tree order (fbsmi_cumsum); r = c[n-1] * (1 - uniform(key, ()));
+ *                  the fixed-length bisection of fbsmi_searchsorted on (c, r)                        (fbsmi_categorical);
+ *   mode 0         iT = randint(key, (), 0, n) with the PARENT key (smc.py:109); keys = split(split(key, 2)[1], T);
+ *                  traj[T] = path[T][iT]; for s = 0 .. T-1, t = T-1-s: lw_i = tlp(t, traj[t+1], i);
+ *                  w_i = fbsmi_expf(lw_i - lse(lw)); traj[t] = path[t][cat(keys[s], w)];
+ *   mode 1         keys = split(key, T+1); B_T = cat(keys[T], fbsmi_expf(log_wss[T] - lse(log_wss[T])));
+ *                  for s = 0 .. T-1, t = T-1-s: gl_i = tlp(t, traj[t+1], i); x_i = (gl_i - max(gl)) + log_wss[t][i];
+ *                  w_i = fbsmi_expf(x_i - lse(x)); B_t = cat(keys[s], w); bs[t] = B_t, traj[t] = path[t][B_t].
+ * keys (C,2), vs (C,T+1,dv), path (C,T+1,n,du) row-major, log_wss (C,T+1,n) (mode 1 only) are device inputs; path and
+ * log_wss are read in place (never copied) and must stay valid until the call's work on `stream` has finished.
+ * traj (C,T+1,du) and bs (C,T+1) (mode 1; nullable) are device outputs.  use_graph != 0 replays one linear hipGraph
+ * captured on the handle's first call. */
+typedef struct fbsmi_lg_backsim fbsmi_lg_backsim;
+int fbsmi_lg_backsim_create(const fbsmi_lg_model* model, int32_t nslots, int mode, int32_t nchains, fbsmi_lg_backsim** out);
+void fbsmi_lg_backsim_destroy(fbsmi_lg_backsim* h);
+int fbsmi_lg_backsim_run(fbsmi_lg_backsim* h, const uint32_t* keys, const float* vs, const float* path, const float* log_wss,
+                         float* traj, int32_t* bs, int use_graph, void* stream);
+
 /* ---- fused twisted SMC for the analytic Gaussian model, batched over runs ------------------------
  * twisted_smc (fbs/samplers/smc.py:261-309) with the closures of experiments/toy/gp_twisted.py:100-129 for a Gaussian
  * prior N(mean, cov) of x and the observation y of x + N(0, obs_var I): the twisting function is a Gaussian density of
