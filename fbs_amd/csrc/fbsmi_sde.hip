@@ -25,16 +25,17 @@
 
 namespace fbsmi {
 
-// one thread per coordinate; xi is (T, D) row-major noise already drawn
+// one coordinate's whole path per loop turn, the grid striding over the coordinates (the launch caps the grid, any D >= 1);
+// xi is (T, D) row-major noise already drawn
 __global__ void k_linear_path(const float* F, const float* S, const float* x0, const float* xi, int T, int64_t D,
                               float* out) {
-    const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (c >= D) return;
-    float x = x0[c];
-    out[c] = x;
-    for (int k = 0; k < T; ++k) {
-        x = F[k] * x + S[k] * xi[(int64_t)k * D + c];
-        out[(int64_t)(k + 1) * D + c] = x;
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < D; c += (int64_t)gridDim.x * blockDim.x) {
+        float x = x0[c];
+        out[c] = x;
+        for (int k = 0; k < T; ++k) {
+            x = F[k] * x + S[k] * xi[(int64_t)k * D + c];
+            out[(int64_t)(k + 1) * D + c] = x;
+        }
     }
 }
 
@@ -43,25 +44,25 @@ __global__ void k_linear_path(const float* F, const float* S, const float* x0, c
 __global__ void k_affine_em_path(const uint32_t* keys, const float* A, const float* B, const float* S,
                                  const float* ddt, const float* target, const float* x0, int T, int nsub,
                                  int64_t D, int replace_last, float* out) {
-    const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (c >= D) return;
-    float x = x0[c];
-    const float tg = target[c];
-    out[c] = x;
     const uint64_t n = (uint64_t)nsub * (uint64_t)D;
-    for (int k = 0; k < T; ++k) {
-        const uint32_t k0 = keys[2 * k], k1 = keys[2 * k + 1];
-        const float h = ddt[k];
-        const float sq = fbsmi_sqrtf(h);
-        for (int j = 0; j < nsub; ++j) {
-            const int r = k * nsub + j;
-            const float xi = normal_at(k0, k1, n, (uint64_t)j * D + c);
-            const float drift = A[r] * x + B[r] * tg;
-            x = (x + drift * h) + (S[r] * sq) * xi;
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < D; c += (int64_t)gridDim.x * blockDim.x) {
+        float x = x0[c];
+        const float tg = target[c];
+        out[c] = x;
+        for (int k = 0; k < T; ++k) {
+            const uint32_t k0 = keys[2 * k], k1 = keys[2 * k + 1];
+            const float h = ddt[k];
+            const float sq = fbsmi_sqrtf(h);
+            for (int j = 0; j < nsub; ++j) {
+                const int r = k * nsub + j;
+                const float xi = normal_at(k0, k1, n, (uint64_t)j * D + c);
+                const float drift = A[r] * x + B[r] * tg;
+                x = (x + drift * h) + (S[r] * sq) * xi;
+            }
+            out[(int64_t)(k + 1) * D + c] = x;
         }
-        out[(int64_t)(k + 1) * D + c] = x;
+        if (replace_last) out[(int64_t)T * D + c] = tg;
     }
-    if (replace_last) out[(int64_t)T * D + c] = tg;
 }
 
 // Matrix-affine Euler-Maruyama path (include/fbsmi.h, fbsmi_em_forward): one workgroup; the noise of sub-step j of interval

@@ -103,14 +103,16 @@ int fbsmi_backtrace(const int32_t* As, int32_t T, int32_t n, const int32_t* B_T,
 
 /* ---- single-trajectory SDE paths ------------------------------------------------------------
  * out (T+1, D): out[0] = x0, out[k+1] = F[k]*out[k] + S[k]*xi[k]  -- the exact forward noising
- * transition of simulate_cond_forward(keep_path=True), fbs/sdes/linear.py:190-221; xi (T, D). */
+ * transition of simulate_cond_forward(keep_path=True), fbs/sdes/linear.py:190-221; xi (T, D).  Any D >= 1 is supported
+ * (the launch is capped and strides over the coordinates); T = 0 writes out[0] only. */
 int fbsmi_linear_path(const float* F, const float* S, const float* x0, const float* xi, int32_t T, int64_t D,
                       float* out, void* stream);
 /* Euler-Maruyama with nsub sub-steps per interval for a drift affine in x:
  *   x += (A[r] x + B[r] target) ddt[k] + S[r] sqrt(ddt[k]) xi,  r = k*nsub + j,
  * xi = normal(keys[k], (nsub, D)) (fbs/sdes/simulators.py:53-106).  With the Doob bridge drift of a
  * scalar linear SDE this is doob_bridge_simulator (simulators.py:126-160), the bridge_sampler of
- * fbs/samplers/gibbs.py:17-20.  keys (T,2) uint32 device; out (T+1, D). */
+ * fbs/samplers/gibbs.py:17-20.  keys (T,2) uint32 device; out (T+1, D).  Any D >= 1 is supported (the launch is capped
+ * and strides over the coordinates). */
 int fbsmi_affine_em_path(const uint32_t* keys, const float* A, const float* B, const float* S, const float* ddt,
                          const float* target, const float* x0, int32_t T, int32_t nsub, int64_t D, int replace_last,
                          float* out, void* stream);

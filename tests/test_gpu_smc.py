@@ -335,6 +335,9 @@ def test_sharded_module_world1_on_gpu(oracle, dev):
     _eq(part, full[32:72], "normal rows slice")
     fullu = _np(ops.uniform(key, (N,), device=dev))
     _eq(_np(ops.uniform(key, (N,), device=dev, rows=(90, 6))), fullu[90:96], "uniform rows slice")
+    # ... and of the oracle's draw (tests/test_gpu_sde_edges.py takes the slices to their edges)
+    _eq(part, oracle.normal(key, (N, 3))[32:72], "normal rows slice vs the oracle")
+    _eq(_np(ops.uniform(key, (N,), device=dev, rows=(90, 6))), oracle.uniform(key, (N,))[90:96], "uniform rows slice vs the oracle")
     # a row-sliced transition equals the slice of the full transition
     us_prev = torch.from_numpy(rng.normal(size=(N, br.du)).astype(np.float32)).to(dev)
     v_prev = torch.from_numpy(rng.normal(size=br.dv).astype(np.float32)).to(dev)
