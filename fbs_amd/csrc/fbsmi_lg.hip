@@ -3841,6 +3841,75 @@ __global__ void __launch_bounds__(kBlock) k_pm_accept(PmDev p, int chain) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// bootstrap-filter conditional sampler (experiments/toy/gp_filter.py:134-142) round the flow-0 filter:
+//   k_fs_front -> k_pm_u0 -> [enqueue_filter] -> k_fs_tail, the sample on blockIdx.y
+// The engine's device state is a PmDev with the sample in the chain's place: ikeys the call's keys, pk[4b..4b+1]
+// key_init, uT the samples, log_ell the negative log-likelihood estimates; the pCN and chain fields stay zero.
+// ------------------------------------------------------------------------------------------
+constexpr int kFsBlockMax = 128;   // a thread per coordinate: du, dv <= 128 in every model the filter takes
+
+// keys (gp_filter.py:135, smc.py:77), the forward observation path written reversed into the filter's vs
+// (gp_filter.py:136-137), and the conditional mean of ref_sampler.  Thread j < dv owns coordinate j and draws
+// normal(key_fwd, (T, dv))[k][j] where it consumes it: the draws of kPmChunk steps are issued together, ahead of the
+// chunk's dependent F * r + sqQ * xi chain, and no noise buffer exists.  Threads from dv on run coordinate dv - 1 again
+// and store nothing, so no load of the path is predicated per lane.
+__global__ void __launch_bounds__(kFsBlockMax) k_fs_front(PmDev p) {
+    const int b = blockIdx.y;
+    __shared__ uint32_t sk[2];
+    __shared__ float syT[kFsBlockMax];
+    if (threadIdx.x == 0) {
+        const uint32_t k0 = p.ikeys[2 * b], k1 = p.ikeys[2 * b + 1];
+        uint32_t f0, f1;
+        split_at(k0, k1, 3, 0, sk[0], sk[1]);                            // key_fwd  (key_bwd = split(key, 3)[1] is unused)
+        split_at(k0, k1, 3, 2, f0, f1);                                  // key_bf
+        p.fkeys[2 * b] = f0;                                             // the filter derives split(key_bf, 2)[1] itself
+        p.fkeys[2 * b + 1] = f1;
+        split_at(f0, f1, 2, 0, p.pk[4 * b], p.pk[4 * b + 1]);            // key_init, where k_pm_u0 reads its key
+    }
+    __syncthreads();
+    const int T = p.T, dv = p.dv;
+    const bool live = (int)threadIdx.x < dv;
+    const int j = live ? (int)threadIdx.x : dv - 1;
+    const uint32_t s0 = sk[0], s1 = sk[1];
+    const uint64_t n = (uint64_t)T * dv;
+    float* vs = p.vs + (size_t)b * ((size_t)T + 1) * dv;
+    float r = p.y0[j];
+    if (live) vs[(size_t)T * dv + j] = r;                                // vs[k] = r[T - k]
+    for (int k0 = 0; k0 < T; k0 += kPmChunk) {
+        float f[kPmChunk], sq[kPmChunk], z[kPmChunk];
+#pragma unroll
+        for (int i = 0; i < kPmChunk; ++i) {
+            const int k = k0 + i < T ? k0 + i : T - 1;
+            f[i] = p.F[k];
+            sq[i] = p.sqQ[k];
+            z[i] = normal_at(s0, s1, n, (uint64_t)k * dv + j);
+        }
+#pragma unroll
+        for (int i = 0; i < kPmChunk; ++i) {
+            if (k0 + i < T) {
+                r = f[i] * r + sq[i] * z[i];
+                if (live) vs[(size_t)(T - 1 - k0 - i) * dv + j] = r;
+            }
+        }
+    }
+    if (live) syT[j] = r;                                                // yT = vs[0]
+    __syncthreads();
+    for (int u = threadIdx.x; u < p.du; u += blockDim.x) {
+        double s = 0.0;
+        for (int cc = 0; cc < dv; ++cc) s = s + p.gain[(size_t)u * dv + cc] * ((double)syT[cc] - p.m_v[cc]);
+        p.mcond[(size_t)b * p.du + u] = (float)(p.m_u[u] + s);
+    }
+}
+
+// samples[b] = uT[b][0] (gp_filter.py:141-142, `[0][0]`) and the filter's negative log-likelihood estimate
+__global__ void __launch_bounds__(kFsBlockMax) k_fs_tail(PmDev p) {
+    const int b = blockIdx.y;
+    const float* row0 = p.usT + (size_t)b * p.N * p.du;
+    for (int r = threadIdx.x; r < p.du; r += blockDim.x) p.uT[(size_t)b * p.du + r] = row0[r];
+    if (threadIdx.x == 0) p.log_ell[b] = p.ell[b];
+}
+
 }  // namespace fbsmi
 
 using namespace fbsmi;
@@ -4956,6 +5025,126 @@ int fbsmi_lg_pmcmc_chain(fbsmi_lg_pmcmc* h, uint32_t* key, float* uT, float* log
         if (int rc = run_pmcmc(h, 1, use_graph)) return rc;
     FBSMI_HIP_TRY(hipMemcpyAsync(key, h->p.key, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     return pmcmc_end(h, uT, log_ell, ys, ust);
+}
+
+// ---- fused bootstrap-filter conditional sampler ----------------------------------------------
+struct fbsmi_lg_fsamp {
+    fbsmi_lg_filter* filt = nullptr;   // flow 0, nchains = B: buffers, stream, events
+    PmDev p{};                         // C = B samples; the pCN and chain fields are unused
+    void* slab = nullptr;
+    int rows = 1;                      // particles per workgroup of k_pm_u0
+    int front_block = 64;              // max(du, dv) rounded up to a wave
+    hipGraphExec_t graph = nullptr;
+};
+
+namespace {
+
+// the launch sequence of a batch of conditional samples: three launches round the filter's own
+int enqueue_fsamp(fbsmi_lg_fsamp* h, hipStream_t st) {
+    const PmDev& p = h->p;
+    k_fs_front<<<dim3(1, p.C), h->front_block, 0, st>>>(p);
+    k_pm_u0<<<dim3((p.N + h->rows - 1) / h->rows, p.C), kBlock, 0, st>>>(p, h->rows, 0);
+    if (int rc = enqueue_filter(h->filt, st)) return rc;
+    k_fs_tail<<<dim3(1, p.C), h->front_block, 0, st>>>(p);
+    return launch_status("fsamp");
+}
+
+}  // namespace
+
+int fbsmi_lg_fsamp_create(const fbsmi_lg_model* m, const fbsmi_lg_pmcmc_tables* t, int32_t nparticles, int resampling,
+                          int32_t nsamples, fbsmi_lg_fsamp** out) {
+    if (!m || !t || !out) return fail(FBSMI_ERR_ARG, "lg_fsamp_create: null argument");
+    if (!t->m_u || !t->m_v || !t->gain || !t->chol) return fail(FBSMI_ERR_ARG, "lg_fsamp_create: null table");
+    if (!m->F || !m->sqQ || m->T < 1) return fail(FBSMI_ERR_ARG, "lg_fsamp_create: null model table");
+    if (nsamples < 1) return fail(FBSMI_ERR_ARG, "lg_fsamp_create: nsamples < 1");
+    if (m->du > kFsBlockMax || m->dv > kFsBlockMax || nsamples > 65535)   // a thread per coordinate, the sample on blockIdx.y
+        return fail(FBSMI_ERR_UNSUPPORTED, "lg_fsamp: du, dv > 128 or more than 65535 samples per call are not supported");
+    {
+        // The observation path is the EXACT forward transition; a model whose forward process is Euler-Maruyama carries
+        // all-zero placeholders here (as in fbsmi_lg_pmcmc_create).
+        std::vector<float> F((size_t)m->T), Q((size_t)m->T);
+        FBSMI_HIP_TRY(hipMemcpy(F.data(), m->F, sizeof(float) * F.size(), hipMemcpyDeviceToHost));
+        FBSMI_HIP_TRY(hipMemcpy(Q.data(), m->sqQ, sizeof(float) * Q.size(), hipMemcpyDeviceToHost));
+        bool any = false;
+        for (size_t k = 0; k < F.size(); ++k) any = any || F[k] != 0.0f || Q[k] != 0.0f;
+        if (!any) return fail(FBSMI_ERR_UNSUPPORTED, "lg_fsamp: the model has no exact forward transition (F, sqQ)");
+    }
+    fbsmi_lg_filter* filt = nullptr;
+    int rc = fbsmi_lg_filter_create(m, nparticles, 0, resampling, 0, nsamples, &filt);
+    if (rc) return rc;
+    fbsmi_lg_fsamp* h = new (std::nothrow) fbsmi_lg_fsamp();
+    if (!h) {
+        fbsmi_lg_filter_destroy(filt);
+        return fail(FBSMI_ERR_ARG, "out of host memory");
+    }
+    h->filt = filt;
+    const LgDev& d = filt->core->d;
+    PmDev& p = h->p;
+    p.C = d.C; p.N = d.N; p.du = d.du; p.dv = d.dv; p.T = d.T;
+    p.m_u = t->m_u; p.m_v = t->m_v; p.gain = t->gain; p.chol = t->chol;
+    p.F = d.F; p.sqQ = d.sqQ;
+    p.fkeys = d.keys; p.vs = d.vs; p.u0s = filt->u0s; p.usT = d.usT; p.ell = d.ell;
+    h->rows = kPmTile / p.du < kBlock ? kPmTile / p.du : kBlock;
+    h->front_block = (p.du > 64 || p.dv > 64) ? kFsBlockMax : 64;
+    const size_t B = p.C;
+    Slab slab;
+    slab.request(&p.ikeys, B * 2);
+    slab.request(&p.pk, B * 4);
+    slab.request(&p.y0, p.dv);
+    slab.request(&p.mcond, B * p.du);
+    slab.request(&p.uT, B * p.du);
+    slab.request(&p.log_ell, B);
+    if (slab.commit(&h->slab) != hipSuccess) {
+        fbsmi_lg_fsamp_destroy(h);
+        return fail(FBSMI_ERR_HIP, "lg_fsamp_create: device allocation failed");
+    }
+    *out = h;
+    return FBSMI_OK;
+}
+
+void fbsmi_lg_fsamp_destroy(fbsmi_lg_fsamp* h) {
+    if (!h) return;
+    if (h->filt && h->filt->core && h->filt->core->stream) hipStreamSynchronize(h->filt->core->stream);
+    if (h->graph) hipGraphExecDestroy(h->graph);
+    fbsmi_lg_filter_destroy(h->filt);
+    if (h->slab) hipFree(h->slab);
+    delete h;
+}
+
+int fbsmi_lg_fsamp_run(fbsmi_lg_fsamp* h, const uint32_t* keys, const float* y0, float* samples, float* nell,
+                       int use_graph, void* stream) {
+    if (!h || !keys || !y0 || !samples) return fail(FBSMI_ERR_ARG, "lg_fsamp_run: null argument");
+    fbsmi_lg_sweep* s = h->filt->core;
+    const PmDev& p = h->p;
+    hipStream_t ust = (hipStream_t)stream;
+    const size_t B = p.C;
+    if (int rc = join_in(s, ust)) return rc;
+    FBSMI_HIP_TRY(hipMemcpyAsync(p.ikeys, keys, B * 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
+    FBSMI_HIP_TRY(hipMemcpyAsync(p.y0, y0, p.dv * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    if (int rc = launch_captured(h->graph, s->stream, use_graph != 0, [&] { return enqueue_fsamp(h, s->stream); })) return rc;
+    FBSMI_HIP_TRY(hipMemcpyAsync(samples, p.uT, B * p.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    if (nell) FBSMI_HIP_TRY(hipMemcpyAsync(nell, p.log_ell, B * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    return join_out(s, ust);
+}
+
+int fbsmi_lg_fsamp_view(fbsmi_lg_fsamp* h, int which, void* dst, int64_t* count, void* stream) {
+    if (!h) return fail(FBSMI_ERR_ARG, "lg_fsamp_view: null handle");
+    fbsmi_lg_sweep* s = h->filt->core;
+    const PmDev& p = h->p;
+    const void* src = nullptr;
+    int64_t n = 0;
+    switch (which) {
+        case 0: src = p.vs; n = (int64_t)p.C * (p.T + 1) * p.dv; break;
+        case 1: src = p.u0s; n = (int64_t)p.C * p.N * p.du; break;
+        case 2: src = p.usT; n = (int64_t)p.C * p.N * p.du; break;
+        default: return fail(FBSMI_ERR_ARG, "lg_fsamp_view: unknown view");
+    }
+    if (count) *count = n;
+    if (dst && n > 0) {
+        FBSMI_HIP_TRY(hipStreamSynchronize(s->stream));
+        FBSMI_HIP_TRY(hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    return FBSMI_OK;
 }
 
 }  // extern "C"

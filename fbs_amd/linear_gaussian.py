@@ -316,6 +316,17 @@ class LinearGaussianBridge:
         keyt = ("pmcmc", int(nparticles), resampling, int(nchains), None if delta is None else float(delta), int(which_u))
         return self._cached(keyt, lambda: LGPmcmc(self, int(nparticles), resampling, int(nchains), delta, int(which_u)))
 
+    def fused_filter_sampler_supported(self, nparticles: int, nsamples: int = 1) -> bool:
+        """What fbsmi_lg_fsamp_create accepts: the fused filter's sizes with nchains = nsamples (a launch's grid takes at
+        most 65535 samples), and an exact forward transition (a model with an Euler-Maruyama forward process has none)."""
+        return (getattr(self, "em_struct", None) is None and self.sde is not None and 1 <= int(nsamples) <= 65535
+                and int(nparticles) >= 1 and self.fused_filter_supported(nparticles))
+
+    def filter_sampler_handle(self, nparticles: int, resampling: str = "stratified", nsamples: int = 1):
+        """The fused bootstrap-filter conditional sampler (gp_filter.py:134-142) for `nsamples` samples per call."""
+        keyt = ("fsamp", int(nparticles), resampling, int(nsamples))
+        return self._cached(keyt, lambda: LGFilterSampler(self, int(nparticles), resampling, int(nsamples)))
+
     def gibbs_kernel(self, key, x0, y0, bs_star, nparticles, explicit_backward=True, explicit_final=False,
                      use_graph=True, marg_y=False):
         """One fused sweep; same returns as fbs.samplers.gibbs_kernel: (x0, us_star, bs_star, acc)."""
@@ -630,3 +641,54 @@ class LGPmcmc(_LGHandle):
         state = MCMCState(acceptance_prob=self._sq(prob, 1), is_accepted=self._sq(acc.bool(), 1),
                           prop_log_ell=self._sq(prop, 1), log_ell=self._sq(ells, 1))
         return key_out, self._sq(uTt), self._sq(ellt), self._sq(yst), self._sq(samples, 1), state
+
+
+class LGFilterSampler(_LGHandle):
+    """Owns one fbsmi_lg_fsamp handle: the bootstrap-filter conditional sampler (experiments/toy/gp_filter.py:134-142) for
+    up to `nsamples` independent samples per call -- observation paths, initial particles, the batched flow-0 filter and the
+    pick of the first particle in one hipGraph replay, nothing on the host inside a call.  A call with fewer keys than
+    `nsamples` (a ragged last batch) runs on the model's handle of that size."""
+
+    _DESTROY = "fbsmi_lg_fsamp_destroy"
+
+    def __init__(self, model: LinearGaussianBridge, nparticles, resampling="stratified", nsamples=1):
+        if getattr(model, "em_struct", None) is not None or model.sde is None:   # (no terminal moments to build tables from)
+            raise NotImplementedError("the fused filter sampler needs an exact forward transition")
+        self.model, self.n, self.resampling, self.C = model, int(nparticles), resampling, int(nsamples)
+        self._last = self
+        self.tables = model.pmcmc_tables(None)
+        h = C.c_void_p()   # sizes the engine does not take are refused by the library, with its message
+        with torch.cuda.device(model.device):
+            _lib.call("fbsmi_lg_fsamp_create", C.byref(model.struct), C.byref(self.tables), self.n,
+                      LGFilter._RES[resampling], self.C, C.byref(h))
+        self.h = h
+
+    def sample(self, keys, y0, return_nell=False, use_graph=True):
+        """keys (B', 2), or (2,) for one sample, y0 (dv,) -> samples (B', du) [, negative log-likelihood estimates (B')]."""
+        m = self.model
+        k = np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys).astype(np.uint32).reshape(-1, 2)
+        B = k.shape[0]
+        if not 1 <= B <= self.C:
+            raise ValueError(f"{B} keys for a handle of {self.C} samples")
+        if B < self.C:
+            self._last = m.filter_sampler_handle(self.n, self.resampling, B)
+            return self._last.sample(k, y0, return_nell, use_graph)
+        self._last = self
+        kt = self._key_t(k, B)
+        y0t = self._dev(y0, torch.float32, (m.dv,))
+        out = torch.empty((B, m.du), dtype=torch.float32, device=m.device)
+        nell = torch.empty(B, dtype=torch.float32, device=m.device) if return_nell else None
+        with torch.cuda.device(m.device):
+            _lib.call("fbsmi_lg_fsamp_run", self.h, kt.data_ptr(), y0t.data_ptr(), out.data_ptr(),
+                      nell.data_ptr() if return_nell else None, int(bool(use_graph)), ops._stream())
+        return (out, nell) if return_nell else out
+
+    def views(self) -> dict:
+        """Parity views of the last call (copies): vs (B, T+1, dv), u0s (B, n, du), uT (B, n, du)."""
+        h, m = self._last, self.model
+        out = {}
+        for name, which, shape in (("vs", 0, (h.C, m.T + 1, m.dv)), ("u0s", 1, (h.C, h.n, m.du)), ("uT", 2, (h.C, h.n, m.du))):
+            t = torch.empty(shape, dtype=torch.float32, device=m.device)
+            _lib.call("fbsmi_lg_fsamp_view", h.h, which, t.data_ptr(), None, ops._stream())
+            out[name] = t
+        return out

@@ -74,6 +74,74 @@ def bootstrap_filter(transition_sampler, measurement_cond_pdf, vs, ts, init_samp
     return torch.stack(filtering, 0), log_nell
 
 
+FSAMP_STATE_ELEMS = 1 << 26   # B * N * du float32 elements of ONE particle buffer of a fused call: 256 MB
+FSAMP_MAX_SAMPLES = 16384     # samples per fused call (the engine itself takes 65535, the grid's y extent)
+
+
+def plan_filter_chunks(nkeys: int, nparticles: int, du: int, bound: int = FSAMP_STATE_ELEMS,
+                       max_samples: int = FSAMP_MAX_SAMPLES):
+    """[(start, stop), ..] covering range(nkeys) in order, each with (stop - start) * nparticles * du <= bound elements and at
+    most max_samples samples; None when one sample alone exceeds the bound.
+
+    The bound is on one particle buffer (B, N, du), not on the handle: a flow-0 filter of B chains holds four such buffers
+    (two generations, the final particles, the staging of the initial ones) plus five (B, N) weight / cdf rows, and a wide
+    model (du or dv > 16) two more (B, N, du) noise buffers and dv + 1 rows -- 4 + 5 / du times the bound for a narrow model
+    (9 x at du = 1: 2.3 GB at the full bound), about 7 to 8 times for a wide one -- and per-step tables of B * T * (8 + 2 D)
+    words, which max_samples keeps to 0.1 GB at T = 200, D = 2.  Every distinct chunk size is a handle of its own, cached
+    on the bridge for its lifetime."""
+    per = int(nparticles) * int(du)
+    if per > bound:
+        return None
+    step = max(1, min(int(max_samples), bound // per))
+    return [(s, min(s + step, int(nkeys))) for s in range(0, int(nkeys), step)]
+
+
+def _fused_filter_sampler(ts, fwd_ys_sampler, ref_sampler, transition_sampler, likelihood_logpdf, nparticles, resampling):
+    """(model, resampling name) when the fused filter sampler (LGFilterSampler) applies: the four closures belong to one
+    LinearGaussianBridge in their own roles, ts is its grid, its forward transition is exact, the resampler is one the
+    fused filter has and the engine takes the size; else None.  Touches no device."""
+    fused = _fused_filter(transition_sampler, likelihood_logpdf, resampling, {}, nparticles)
+    if fused is None:
+        return None
+    model = fused[0]
+    for closure, role in ((fwd_ys_sampler, "fwd_ys_sampler"), (ref_sampler, "ref_sampler"),
+                          (transition_sampler, "transition_sampler")):
+        if getattr(closure, "_fbsmi_lg", None) is not model or getattr(closure, "_role", "") != role:
+            return None
+    if not model.fused_filter_sampler_supported(nparticles, 1) or not model.same_grid(ts):
+        return None
+    return fused
+
+
+def filter_conditional_sampler(keys, y0, ts, fwd_ys_sampler, ref_sampler, transition_sampler, likelihood_logpdf,
+                               nparticles, resampling, return_nell=False, _bound=FSAMP_STATE_ELEMS):
+    """The bootstrap-filter conditional sampler of experiments/toy/gp_filter.py:134-142 for every key of `keys` (B, 2)
+    [or (2,)]: -> samples (B, du) [, negative log-likelihood estimates (B)].  Each sample depends on its own key only.
+
+    With the closures of one LinearGaussianBridge on its own grid and stratified / systematic resampling the batch runs on
+    the device (LGFilterSampler), in chunks of samples that keep B * N * du within `_bound` elements per call; otherwise
+    the driver's body runs once per key."""
+    k = np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys).astype(np.uint32).reshape(-1, 2)
+    fused = _fused_filter_sampler(ts, fwd_ys_sampler, ref_sampler, transition_sampler, likelihood_logpdf, nparticles,
+                                  resampling)
+    chunks = plan_filter_chunks(k.shape[0], nparticles, fused[0].du, _bound) if fused is not None else None
+    if chunks:
+        model, rname = fused
+        outs = [model.filter_sampler_handle(nparticles, rname, b - a).sample(k[a:b], y0, return_nell=True) for a, b in chunks]
+        samples, nell = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+        return (samples, nell) if return_nell else samples
+    samples, nells = [], []
+    for key_ in k:                                                                  # gp_filter.py:134-142
+        key_fwd, key_bwd, key_bf = ops.split(key_, 3)
+        vs = torch.flip(fwd_ys_sampler(key_fwd, y0), [0])
+        us, nell = bootstrap_filter(transition_sampler, likelihood_logpdf, vs, ts, ref_sampler, key_bf, nparticles,
+                                    resampling, log=True, return_last=True)
+        samples.append(us[0])
+        nells.append(nell.reshape(()))
+    samples, nells = torch.stack(samples), torch.stack(nells)
+    return (samples, nells) if return_nell else samples
+
+
 def fused_backsim(transition_logpdf, args, kwargs, ts, path):
     """The model whose fused backward simulation (LGBacksim) applies to a stored float32 path (T+1, n, du): the closure is
     one LinearGaussianBridge's own transition_logpdf, called without extra arguments on the bridge's own grid, and the

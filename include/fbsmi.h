@@ -314,6 +314,35 @@ int fbsmi_lg_pmcmc_chain(fbsmi_lg_pmcmc* h, uint32_t* key, float* uT, float* log
                          int32_t nsamples, float* samples, float* acc_prob, uint8_t* accepted, float* prop_log_ell,
                          float* log_ells, int use_graph, void* stream);
 
+/* Fused bootstrap-filter conditional sampler for the analytic model: conditional_sampler of
+ * experiments/toy/gp_filter.py:134-142 for `nsamples` = B independent samples in every launch.  A call is the front
+ * launch (keys + forward observation path + reversal + conditional mean), the initial particles, the flow-0 filter's own
+ * launch list with nchains = B, and one tail launch, captured in one hipGraph; nothing returns to the host inside a call.
+ * Of the tables only m_u, m_v, gain and chol are read (the rest may be zero); they must outlive the handle.
+ * Numeric specification (no contraction anywhere; every operation separately rounded), sample b with key = keys[b]:
+ *   keys           key_fwd, key_bwd, key_bf = split(key, 3) (gp_filter.py:135; key_bwd is unused, as in the reference);
+ *                  key_init = split(key_bf, 2)[0] (smc.py:77);
+ *   forward path   r[0] = y0, r[k+1] = F[k] * r[k] + sqQ[k] * xi[k], xi = normal(key_fwd, (T, dv))  (fbsmi_linear_path);
+ *                  vs[k] = r[T - k];
+ *   ref_sampler    u0s = ref_sampler(key_init, vs[0], n), exactly the ref_sampler block of fbsmi_lg_pmcmc above
+ *                  (float64 conditional mean in ascending c; float32 acc over chol in ascending c; u0 = m_ + acc);
+ *   filter         fbsmi_lg_filter_run, flow 0, with key key_bf (it derives split(key_bf, 2)[1] itself), vs, u0s and
+ *                  the handle's resampling;
+ *   outputs        samples[b] = uT[b][0] (the first particle); nell[b] = the filter's negative log-likelihood estimate.
+ * resampling 0 stratified | 1 systematic.  FBSMI_ERR_UNSUPPORTED for what fbsmi_lg_filter_create(..., nchains = nsamples)
+ * does not take, for nsamples > 65535 and for a model without an exact forward transition (F and sqQ all-zero
+ * placeholders); FBSMI_ERR_ARG for null tables. */
+typedef struct fbsmi_lg_fsamp fbsmi_lg_fsamp; /* opaque: a flow-0 filter of B chains, the call's keys and outputs, the graph */
+int fbsmi_lg_fsamp_create(const fbsmi_lg_model* model, const fbsmi_lg_pmcmc_tables* tables, int32_t nparticles,
+                          int resampling, int32_t nsamples, fbsmi_lg_fsamp** out);
+void fbsmi_lg_fsamp_destroy(fbsmi_lg_fsamp* h);
+/* keys (B,2) and y0 (dv) are device inputs, samples (B,du) and nell (B) (nullable) device outputs. */
+int fbsmi_lg_fsamp_run(fbsmi_lg_fsamp* h, const uint32_t* keys, const float* y0, float* samples, float* nell,
+                       int use_graph, void* stream);
+/* Parity views of the last run: copies view `which` into dst (device, nullable) and reports its element count.
+ * which: 0 vs (B,T+1,dv), 1 u0s (B,n,du), 2 uT (B,n,du); any other `which` is FBSMI_ERR_ARG. */
+int fbsmi_lg_fsamp_view(fbsmi_lg_fsamp* h, int which, void* dst, int64_t* count, void* stream);
+
 /* ---- fused backward simulation for the analytic model, batched over chains -----------------------
  * mode 0  bootstrap_backward_smoother (fbs/samplers/smc.py:91-112) on a stored filtering path;
  * mode 1  backward_sampling_pass (fbs/samplers/csmc/csmc.py:167-227), the backward pass of csmc_kernel(backward=True),
