@@ -34,7 +34,7 @@
 //       through an LDS queue); chunks of a thread move as 16-byte accesses.  (The draws by a launch of their own, one
 //       Threefry call per element pair, through HBM: measured 10 % slower at 2^22, 6 % at 2^20 -- not kept.)
 //   N a power of two, 512 .. 65536                  : TWO kernels per step -- the bisection over the canonical cumsum is a
-//       descent of the summation tree, so norm publishes tree nodes and k_lg_prop1t / k_lg_prop1tp / k_lg_prop2t walk them; no cdf
+//       descent of the summation tree, so norm publishes tree nodes and k_lg_prop1t / k_lg_prop1tp / k_lg_prop1th / k_lg_prop2t walk them; no cdf
 //   N = 2^k + 1 (explicit_final on such an ensemble) : the same two kernels over the first 2^k slots' tree + one extra tile
 #include <hip/hip_runtime.h>
 
@@ -1301,9 +1301,11 @@ __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
 //   substituted -> descent to a tile -> that tile's w fetched whole, its leaves and tree rebuilt in LDS -> descent.
 //   Cat(w) per slot: top levels + three levels of every tile in LDS, then (killed slots only) three levels from the
 //   tile's published heap in one round trip and the last four leaves of w in another.
-// Workgroups: k_lg_prop1t, one tile each (a single chain, pinned launches, N = 2^k + 1); k_lg_prop1tp, two or four tiles N/2
-// apart, the trees built once by the first 256 threads and the noise drawn once per pair of slots by the others meanwhile
-// (from two tiles per CU on); k_lg_prop2t, two slots N/2 apart per thread (from five tiles per CU on).
+// Workgroups: k_lg_prop1t, one tile each (a single chain, pinned launches, N = 2^k + 1); k_lg_prop1th, two or four tiles N/2
+// apart, the trees built once by the first 256 threads and the noise drawn once per pair of slots by the others meanwhile,
+// a pair's two slots in lanes l and l + 32 of one wave so that the kill-test and redraw draws are also made once per pair
+// (from two tiles per CU on; k_lg_prop1tp, a pair's slots in two waves and those draws per slot, under
+// FBSMI_PROP_HALFWAVE=0); k_lg_prop2t, two slots N/2 apart per thread (from five tiles per CU on).
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool tree_walk(float2 nd, float q, float& P, float& E) {
     const float t = P + nd.x;
@@ -1687,7 +1689,8 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
 // The kill-test and redraw uniforms are source-indexed and pair up the same way (the rotation keeps the two sources N/2
 // apart), and the redraw searches of the ~7 % killed slots can be dealt out from an LDS queue as in k_lg_propQ: both were
 // built and measured on top of this kernel and left out -- the two workgroup barriers they need after J (exchange /
-// queue, results) cost more than the ~270 instructions per wave they save.
+// queue, results) cost more than the ~270 instructions per wave they save.  k_lg_prop1th (below) pairs the
+// uniforms without a barrier by putting both slots of a pair in one wave; this kernel stays under FBSMI_PROP_HALFWAVE=0.
 template <int DMAX, int HALVES>
 __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1tp(LgDev dd, int s) {
     static_assert(HALVES == 2 || HALVES == 4, "two sides of HALVES / 2 tiles");
@@ -1850,6 +1853,235 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1tp(LgDev dd, int s)
         sx = (part[1][h4] + part[1][h4 + 1]) + (part[1][h4 + 2] + part[1][h4 + 3]);
     }
     if (tid == 0) {
+        d.bmax[tileb] = mx;
+        d.bsumexp[tileb] = sx;
+    }
+}
+
+// max / canonical tree sum over an aligned block of 32 lanes (levels 0-4 of the tile's tree; every lane of the block receives it)
+__device__ __forceinline__ float halfwave_max(float m) {
+    m = fmaxf(m, tree_partner<1>(m));
+    m = fmaxf(m, tree_partner<2>(m));
+    m = fmaxf(m, tree_partner<4>(m));
+    m = fmaxf(m, tree_partner<8>(m));
+    m = fmaxf(m, tree_partner<16>(m));
+    return m;
+}
+
+__device__ __forceinline__ float halfwave_sum(float s) {
+    const int lane = threadIdx.x & 63;
+#define FBSMI_HALFWAVE_LEVEL(m, M)                      \
+    {                                                   \
+        const float o_ = tree_partner<M>(s);            \
+        s = ((lane >> m) & 1) ? o_ + s : s + o_;        \
+    }
+    FBSMI_HALFWAVE_LEVEL(0, 1)
+    FBSMI_HALFWAVE_LEVEL(1, 2)
+    FBSMI_HALFWAVE_LEVEL(2, 4)
+    FBSMI_HALFWAVE_LEVEL(3, 8)
+    FBSMI_HALFWAVE_LEVEL(4, 16)
+#undef FBSMI_HALFWAVE_LEVEL
+    return s;
+}
+
+// k_lg_prop1th, HALVES = 2, 4: k_lg_prop1tp with both slots of a pair in the SAME WAVE.  The workgroup owns the same tiles
+// N/2 apart, but lanes 0-31 of wave v hold 32 consecutive slots of a lower tile (block v & 7 of tile v >> 3 of the lower
+// side) and lanes 32-63 the 32 slots N/2 above them: a tile is spread over eight waves as eight blocks of 32 slots, and
+// lane l and lane l ^ 32 are a pair.  Global accesses stay coalesced, 128 contiguous bytes per half-wave.
+//   The kill-test and redraw uniforms are indexed by the SOURCE slot, and the roll is a rotation mod N: the two sources of
+// a pair are again N/2 apart, so for either draw the pair's two elements are the two output words of ONE Threefry call
+// with counter c = src mod N/2 (word 0: element c, word 1: element c + N/2).  The lower half-wave makes that call with the
+// kill-test key, the upper half-wave with the redraw key; each lane keeps the word of its own source, and the word of its
+// partner's source goes across with one v_permlane32_swap -- one call per lane where k_lg_prop1tp makes two, no LDS
+// traffic and no barrier (the version that passed the words between waves through LDS lost the gain to its two barriers,
+// DESIGN 5.01).  Which word is a lane's own is a per-lane select: the roll can put the lower slot's source in the upper half.
+//   The noise is still drawn once per pair by the waves that wait for the tree builders (thread NP + p draws pair p), but
+// neither slot of a pair belongs to the drawing thread now: both normals are parked in LDS, at the index of the thread that
+// owns the slot (xish[r][threadIdx.x]: conflict-free reads).
+//   The per-tile (max, sumexp): levels 0-4 of the canonical tree are inside a half-wave, levels 5-7 run over the tile's
+// eight blocks, whose partials go through part[][] -- the same two exchanges as before, eight entries per tile.
+// Every output is written per tile / per slot exactly as by k_lg_prop1tp: only the owner changes.
+template <int DMAX, int HALVES>
+__global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s) {
+    static_assert(HALVES == 2 || HALVES == 4, "two sides of HALVES / 2 tiles");
+    constexpr int HP = HALVES / 2, NP = kBlock * HP;   // tiles per side; pairs
+    // Both normals of a pair go through LDS, 8 * DMAX * NP bytes: up to 16 KB for the instantiations up to DMAX = 4.  DMAX = 16
+    // would take 32 / 64 KB next to the 22 KB of trees, so there every slot draws its own noise (same bits: random_bits_at
+    // is the same call with the other word kept).
+    constexpr bool kPairNoise = DMAX <= 4;
+    // The ancestor is one of the last four leaves or the slot behind them: for narrow states its row is fetched together
+    // with those leaves (one dependent round trip less).
+    constexpr bool kEarlyRow = DMAX <= 2;
+    const LgDev d = chain_view(dd, blockIdx.y);
+    __shared__ TreeLds L;
+    __shared__ __attribute__((aligned(16))) float part[2][2][HP][8];   // [max | sumexp][side][tile of the side][block of 32 slots]
+    __shared__ int Jsh;
+    __shared__ float lastsh;
+    __shared__ float xish[kPairNoise ? DMAX : 1][2 * NP];   // noise of every slot, at the index of the thread that owns it
+    const int N = d.N, hN = N >> 1, tid = threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int hw = lane >> 5;                            // 0: a lower slot, 1: its partner N/2 above
+    const bool builder = tid < kBlock;                   // (wave-uniform) the threads of tree_build
+    const int pr = wv * 32 + (lane & 31);                // the pair
+    const int mL = blockIdx.x * NP + pr;                 // its lower slot, < N/2
+    const int m = mL + (hw ? hN : 0);
+    const int ts = wv >> 3, bk = wv & 7;                 // the tile of the side, and this half-wave's block of 32 slots in it
+    const int tileb = blockIdx.x * HP + ts + (hw ? d.nb >> 1 : 0);   // == m / kBlock
+    const uint32_t* kt = d.keytab + 8 * s;
+    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
+    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
+    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
+    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    // ---- round 0: everything addressable now
+    const float w_max = d.scal[1];
+    const float inv_n = 1.0f / (float)N;   // N is a power of two: x / N == x * inv_n exactly
+    TreeEntry te{};
+    if (builder) te = tree_entry_loads(d, i_ref);
+    float uref[DMAX];
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) uref[r] = r < d.du ? up[(size_t)r * N + i_ref] : 0.0f;
+    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
+    const float* v_prev = d.vs + (size_t)s * d.dv;
+    const float* v = d.vs + (size_t)(s + 1) * d.dv;
+    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
+    const float u3 = __uint_as_float(kt[4]);
+    float xi[DMAX];
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) xi[r] = 0.0f;
+    if (!kPairNoise) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r)
+            if (r < d.du) xi[r] = normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
+    } else if (tid >= NP) {   // pair p: element (slot p of the lower side) * du + r is in the first half of the draw, its
+                              // partner belongs to the slot N/2 above; the owners are lanes l and l + 32 of wave p / 32
+        const int p = tid - NP, own = (p >> 5) * 64 + (p & 31);
+        const int mp = blockIdx.x * NP + p;
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r) {
+            if (r < d.du) {
+                uint32_t lo_, hi_;
+                random_bits_pair(t0, t1, (uint64_t)N * d.du, (uint64_t)mp * d.du + r, lo_, hi_);
+                xish[r][own] = normal_from_bits(lo_);
+                xish[r][own + 32] = normal_from_bits(hi_);
+            }
+        }
+    }
+    float last;
+    int J;
+    if (builder) {
+        float rootW;
+        J = tree_build(d, te, L, i_ref, u3, w_max, inv_n, last, rootW);
+        if (tid == 0) {
+            Jsh = J;
+            lastsh = last;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kTreeBuildBarriers; ++k) __syncthreads();   // the barriers of tree_build
+    }
+    __syncthreads();
+    J = Jsh;
+    last = lastsh;   // == the root of the w tree (powers of two only)
+    int shift = (j_ref - J) % N;   // roll by j - J (:85)
+    if (shift < 0) shift += N;
+    int src = m - shift;
+    if (src < 0) src += N;
+    // ---- round 2
+    const float ws = d.w[src];
+    float u[DMAX];
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * N + src] : 0.0f;
+    if (kPairNoise) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r)
+            if (r < d.du) xi[r] = xish[r][tid];
+    }
+    // uniform_at(a0, a1, N, src) and uniform_at(b0, b1, N, src) from one call per lane.  The partner's source is src +- N/2,
+    // so both lanes of a pair have the same counter c; `swp` (the same in both lanes) says that the LOWER slot's source is
+    // element c + N/2, word 1.  Lower lanes hold the kill-test words, upper lanes the redraw words: V0 = the word of the lower
+    // slot's source, V1 = the word of the upper slot's, and the swap (upper half of V0 <-> lower half of V1) leaves the
+    // kill-test word of the lane's own source in V0 and its redraw word in V1, in every lane.
+    const int c = src & (hN - 1);
+    const bool swp = (src >= hN) != (hw != 0);
+    uint32_t o0, o1;
+    threefry2x32(hw ? b0 : a0, hw ? b1 : a1, (uint32_t)c, (uint32_t)(c + hN), o0, o1);
+    const auto xw = __builtin_amdgcn_permlane32_swap(swp ? o1 : o0, swp ? o0 : o1, false, false);
+    const float u1 = fbsmi_bits_to_unit(xw[0]);
+    const float u2 = fbsmi_bits_to_unit(xw[1]);
+    const float q = last * (1.0f - u2);                                     // resamplings.py:73-74
+    float P = 0.0f, E = last;
+    int tile, h, red = 0;
+    tree_search_lds(L, d.nb, q, P, E, tile, h);
+    const bool killed = u1 * w_max >= ws;                                   // :71
+    // ---- rounds 3, 4 (killed slots only)
+    float ucand[DMAX];
+    if (killed) {
+        const TreeRound rd = tree_round_load(d, tile, h);
+        const int lo = tree_round_walk(rd, tile, h, q, P, E);
+        const float4 w4 = *reinterpret_cast<const float4*>(d.w + lo);
+        float4 ug[DMAX];
+        float ue[DMAX];
+        if (kEarlyRow) {
+            const int en = lo + 4 < N ? lo + 4 : N - 1;
+#pragma unroll
+            for (int r = 0; r < DMAX; ++r) {
+                ug[r] = r < d.du ? *reinterpret_cast<const float4*>(up + (size_t)r * N + lo) : make_float4(0.f, 0.f, 0.f, 0.f);
+                ue[r] = r < d.du ? up[(size_t)r * N + en] : 0.0f;
+            }
+        }
+        red = tree_leaves_walk(w4, lo, q, P, E);
+        if (kEarlyRow) {
+            const int k = red - lo;
+#pragma unroll
+            for (int r = 0; r < DMAX; ++r) {
+                const float lo2 = (k & 1) ? ug[r].y : ug[r].x, hi2 = (k & 1) ? ug[r].w : ug[r].z;
+                ucand[r] = k >= 4 ? ue[r] : ((k & 2) ? hi2 : lo2);
+            }
+        }
+    }
+    const bool pinned = m == j_ref;
+    const int a = pinned ? i_ref : (killed ? red : src);                    // :86
+    // ---- round 5
+    if (killed && !pinned) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r)
+            if (r < d.du) u[r] = kEarlyRow ? ucand[r] : up[(size_t)r * N + a];
+    }
+    if (pinned) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r) u[r] = uref[r];
+    }
+    if (d.As) d.As[(size_t)s * N + m] = a;
+    // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) {
+        if (r < d.du) {
+            const float dr = drift_row<DMAX>(t, r, u, v_prev);
+            float x = (u[r] + dr * t.dt) + t.sd * xi[r];
+            if (pinned) x = ustar[r];
+            un[(size_t)r * N + m] = x;
+            if (d.uss) d.uss[((size_t)(s + 1) * N + m) * d.du + r] = x;
+        }
+    }
+    const float l = lg_loglik<DMAX>(t, u, v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
+    d.lw[m] = l;
+    float mx, sx;
+    {   // the tile's (max, sumexp): block_lse_partial per tile, with the tile's 256 slots held as eight blocks of 32 by the
+        // lower (upper) half-waves of eight waves.  Levels 0-4 of the canonical tree stay inside a half-wave; levels 5-7
+        // combine the eight block sums in the tree's order, ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).
+        const float mw = halfwave_max(l);
+        if ((lane & 31) == 0) part[0][hw][ts][bk] = mw;
+        __syncthreads();   // exchange 1 of 2: the blocks' maxima (where k_lg_prop1tp exchanges the waves' maxima)
+        const float4 ma = *reinterpret_cast<const float4*>(&part[0][hw][ts][0]);
+        const float4 mb = *reinterpret_cast<const float4*>(&part[0][hw][ts][4]);
+        mx = fmaxf(fmaxf(fmaxf(ma.x, ma.y), fmaxf(ma.z, ma.w)), fmaxf(fmaxf(mb.x, mb.y), fmaxf(mb.z, mb.w)));
+        const float sw_ = halfwave_sum(fbsmi_expf(l - finite_or_zero_f(mx)));
+        if ((lane & 31) == 0) part[1][hw][ts][bk] = sw_;
+        __syncthreads();   // exchange 2 of 2: the blocks' sums (where k_lg_prop1tp exchanges the waves' sums)
+        const float4 sa = *reinterpret_cast<const float4*>(&part[1][hw][ts][0]);
+        const float4 sb = *reinterpret_cast<const float4*>(&part[1][hw][ts][4]);
+        sx = ((sa.x + sa.y) + (sa.z + sa.w)) + ((sb.x + sb.y) + (sb.z + sb.w));
+    }
+    if (bk == 0 && (lane & 31) == 0) {
         d.bmax[tileb] = mx;
         d.bsumexp[tileb] = sx;
     }
@@ -3992,7 +4224,8 @@ struct fbsmi_lg_sweep {
     int two_slot_prop = -1;  // FBSMI_TWO_SLOT_PROP=0|1: never / always (where applicable) k_lg_prop2; unset: by batch size
     bool tree_step = true;  // FBSMI_TREE_STEP=0: keep the cdf launch also where the two-launch step applies
     bool tree_plus1 = true;  // FBSMI_TREE_PLUS1=0: no two-launch step for N = 2^k + 1
-    int tree_halves = -1;   // FBSMI_TREE_HALVES=1|2|4: tiles per workgroup of k_lg_prop1t / k_lg_prop1tp (unset: two from two tiles per CU on)
+    int tree_halves = -1;   // FBSMI_TREE_HALVES=1|2|4: tiles per workgroup of k_lg_prop1t / k_lg_prop1tp / k_lg_prop1th (unset: two from two tiles per CU on)
+    bool halfwave = true;   // FBSMI_PROP_HALFWAVE=0: k_lg_prop1tp (a pair's slots in two waves) where k_lg_prop1th is the rule
     bool pin = true;        // FBSMI_PIN=0: no pinned launches of the narrow two-launch step (LgDev.pin)
     bool wide_pin = true;   // FBSMI_WIDE_PIN=0: no pinned launches of the one-tile wide step
     bool em = false;     // fbsmi_lg_sweep_set_em_forward: Euler-Maruyama forward paths (k_lg_em_noise, k_lg_em_path)
@@ -4016,6 +4249,7 @@ void read_switches(fbsmi_lg_sweep* s) {
     if (const char* e = getenv("FBSMI_TREE_HALVES")) s->tree_halves = atoi(e) == 1 ? 1 : (atoi(e) == 4 ? 4 : 2);
     s->tree_step = env("FBSMI_TREE_STEP", 1) != 0;
     s->tree_plus1 = env("FBSMI_TREE_PLUS1", 1) != 0;
+    s->halfwave = env("FBSMI_PROP_HALFWAVE", 1) != 0;
     s->pin = env("FBSMI_PIN", 1) != 0;
     s->wide_pin = env("FBSMI_WIDE_PIN", 1) != 0;
 }
@@ -4228,12 +4462,15 @@ void sweep_steps_narrow(fbsmi_lg_sweep* s, hipStream_t st) {
             // four tiles (two pairs N/2 apart) per 1024-thread workgroup: on request only.  With tiles N/2 apart it no longer
             // wins where it used to be the rule (four tiles per CU, 1024 tiles per launch: 22.4 against 24.2 G particle-steps/s
             // with two, 8 chains as two launches of four) nor below (512 tiles per launch: 14.7 against 16.5).
-            LG_DMAX(s, k_lg_prop1tp<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k));
+            if (s->halfwave) LG_DMAX(s, k_lg_prop1th<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k));
+            else LG_DMAX(s, k_lg_prop1tp<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k));
         } else if (tree && !d.plus1 && nb % 2 == 0 && (s->tree_halves == 2 || (s->tree_halves < 0 && (int64_t)nb * d.C >= 2 * 256))) {
             // two tiles N/2 apart per 512-thread workgroup: half the waves skip the tree building and draw the noise of both
             // tiles meanwhile, one Threefry call per pair of slots (512 tiles per launch, 4 chains as two groups: 16.5 G
             // particle-steps/s against 15.6 with one tile per workgroup; a single chain keeps one tile per workgroup)
-            LG_DMAX(s, k_lg_prop1tp<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k));
+            // (k_lg_prop1th: both slots of a pair in one wave, so the kill-test and redraw draws also take one call per pair)
+            if (s->halfwave) LG_DMAX(s, k_lg_prop1th<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k));
+            else LG_DMAX(s, k_lg_prop1tp<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k));
         } else if (tree) {
             LG_DMAX(s, k_lg_prop1t<DMAX, 1><<<dim3(nb * (d.pin ? 8 : 1), d.C), kBlock, 0, st>>>(d, k));
         } else if (two_slot) {
