@@ -230,3 +230,85 @@ def test_kernel_division_equals_ieee_division(dev):
     got = ops.math_map("div_kernel", a, b)
     assert torch.equal(want.view(torch.int32), got.view(torch.int32))
     assert torch.equal(want, a / b)
+
+
+# ---- sparse weight vectors: long runs of exactly-zero weights (plateaus in the cdf, zero subtrees in the summation tree) -------
+SPARSE_SIZES = [2, 257, 1000, 65536, 100001]
+
+
+def _sparse_weights(n):
+    """-> [(name, weights (n,) float32 summing to 1, an index on the support, an index off it or None)]"""
+    out = []
+
+    def add(name, w):
+        w = np.asarray(w, np.float32)
+        on, off = np.flatnonzero(w > 0), np.flatnonzero(w == 0)
+        out.append((name, w, int(on[-1]), int(off[len(off) // 2]) if off.size else None))
+
+    for k in sorted({0, n - 1, 255, 256}):
+        if k < n:
+            w = np.zeros(n, np.float32)
+            w[k] = 1.0
+            add(f"one-hot-{k}", w)
+    w = np.zeros(n, np.float32)
+    w[0], w[n - 1] = 0.25, 0.75
+    add("two-hot", w)
+    rng = np.random.default_rng(n)
+    if n >= 100:
+        w = np.zeros(n, np.float32)
+        support = rng.choice(n, n // 100, replace=False)
+        w[support] = rng.uniform(0.1, 1.0, support.size)
+        add("99-percent-zeros", w / w.sum(dtype=np.float32))
+    if n >= 768:   # zeros on the whole tiles [0, 512) and on everything from the last tile boundary but two on
+        w = np.zeros(n, np.float32)
+        lo, hi = 512 if n >= 1536 else 256, (n // 256 - (2 if n >= 1536 else 1)) * 256
+        w[lo:hi] = rng.uniform(0.1, 1.0, hi - lo)
+        add("zero-blocks", w / w.sum(dtype=np.float32))
+    return out
+
+
+@pytest.mark.parametrize("n", SPARSE_SIZES)
+@pytest.mark.parametrize("kind", ["stratified", "systematic", "multinomial", "killing"])
+def test_unconditional_resamplers_on_sparse_weights(kind, n, oracle, dev):
+    from fbs_amd.samplers import resampling as R
+    for t, (name, w, on, off) in enumerate(_sparse_weights(n)):
+        key = oracle.PRNGKey(500 + t)
+        got = _np(getattr(R, kind)(torch.from_numpy(w).to(dev), key))
+        want = getattr(oracle, kind)(w, key)
+        np.testing.assert_array_equal(got, want, err_msg=name)
+
+
+@pytest.mark.parametrize("n", SPARSE_SIZES)
+@pytest.mark.parametrize("kind", ["multinomial", "killing"])
+def test_conditional_resamplers_on_sparse_weights(kind, n, oracle, dev):
+    from fbs_amd.samplers.csmc import resamplings as CR
+    for t, (name, w, on, off) in enumerate(_sparse_weights(n)):
+        key = oracle.PRNGKey(600 + t)
+        wt = torch.from_numpy(w).to(dev)
+        for i, j in ((on, on), (on, off), (off, on), (off, off)):      # i, j on and off the support
+            if i is None or j is None:
+                continue
+            for conditional in (True, False):
+                got = _np(getattr(CR, kind)(key, wt, i, j, conditional))
+                want = getattr(oracle, "cond_" + kind)(key, w, i, j, conditional)
+                np.testing.assert_array_equal(got, want, err_msg=f"{name} i={i} j={j} conditional={conditional}")
+                if conditional:
+                    assert got[j] == i
+
+
+@pytest.mark.parametrize("n", SPARSE_SIZES)
+def test_categorical_and_force_move_on_sparse_weights(n, oracle, dev):
+    from fbs_amd import ops
+    from fbs_amd.samplers.gibbs import force_move
+    for t, (name, w, on, off) in enumerate(_sparse_weights(n)):
+        wt = torch.from_numpy(w).to(dev)
+        for trial in range(3):
+            key = oracle.PRNGKey(700 + 10 * t + trial)
+            assert int(ops.categorical(key, wt).item()) == int(oracle.choice(key, w, ())), name
+            for k in (on, off):
+                if k is None:
+                    continue
+                gi, ga = force_move(key, wt, k)
+                wi, wa = oracle.force_move(key, w, k)
+                assert int(gi.item()) == wi, f"{name} k={k}"
+                assert np.float32(ga.item()).view(np.uint32) == np.float32(wa).view(np.uint32), f"{name} k={k}: {ga.item()} vs {wa}"
