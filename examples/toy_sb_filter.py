@@ -4,7 +4,10 @@ Counterpart of the reference driver experiments/sb/filter.py (same flags incl. `
 schema `filter-<x0>-<nparticles>-<id>.npz`): the forward observation path is an Euler-Maruyama simulation of the bridge's
 drift from (x0, y0) with x0 a GP-posterior draw ('proper') or N(0, I) ('heuristic'); every sample is one bootstrap_filter run
 on the closure tier (resampling, gathers, normalisation: libfbsmi kernels).  With --fused the closures come from
-fbs_amd.GaussianSBBridge: the forward path is one Euler-Maruyama kernel and every filter one hipGraph replay."""
+fbs_amd.GaussianSBBridge: the forward path is one Euler-Maruyama kernel and every filter one hipGraph replay.
+
+--fused --batch B draws the samples B at a time on the device (fbs_amd.samplers.sb_filter_conditional_sampler): the subkeys
+of the driver's schedule are derived on the host first, each sample depends on its own subkey only."""
 import argparse
 import os
 
@@ -13,12 +16,13 @@ import torch
 
 from toy_sb_gibbs import common_args, sb_setting
 from fbs_amd import ops
-from fbs_amd.samplers import bootstrap_filter, stratified
+from fbs_amd.samplers import bootstrap_filter, sb_filter_conditional_sampler, stratified
 
 
 def main(argv=None):
     parser = common_args(argparse.ArgumentParser())
     parser.add_argument('--x0', type=str, default='heuristic', help="How the forward path's x0 is drawn: 'proper' or 'heuristic'.")
+    parser.add_argument('--batch', type=int, default=0, help='With --fused: samples per fused call (0: one sample per filter run).')
     args = parser.parse_args(argv)
     if args.x0 not in ('proper', 'heuristic'):
         raise ValueError(f'Invalid "{args.x0}" method')
@@ -38,7 +42,19 @@ def main(argv=None):
                                 stratified, log=True, return_last=True)[0][0]
 
     samples = torch.empty((args.nsamples, d), device=dev)
-    for i in range(args.nsamples):                                                   # :167-172
+    batched = args.fused and args.batch > 0
+    if batched:
+        br = g.bridge
+        prior = (g.gp_mean, np.linalg.cholesky(g.gp_cov)) if args.x0 == 'proper' else None
+        subkeys = np.empty((args.nsamples, 2), np.uint32)
+        for i in range(args.nsamples):                                               # :167-168, on the host
+            key, subkeys[i] = ops.split(key)
+        for a in range(0, args.nsamples, args.batch):
+            b = min(a + args.batch, args.nsamples)
+            samples[a:b] = sb_filter_conditional_sampler(subkeys[a:b], g.y0, g.ts, br.fwd_sampler, br.unpack, br.ref_sampler,
+                                                         br.transition_sampler, br.likelihood_logpdf, args.nparticles,
+                                                         stratified, x0_prior=prior)
+    for i in range(0 if batched else args.nsamples):                                 # :167-172
         key, subkey = ops.split(key)
         samples[i] = conditional_sampler(subkey)
     samples = samples.cpu().numpy()

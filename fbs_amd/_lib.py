@@ -222,6 +222,8 @@ SIGNATURES = {
     "fbsmi_lg_pmcmc_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fbsmi_lg_fsamp_create": (C.c_int, [C.POINTER(LGModelStruct), C.POINTER(LGPmcmcTablesStruct), _i32, C.c_int, _i32,
                                         C.POINTER(_vp)]),
+    "fbsmi_lg_fsamp_create_em": (C.c_int, [C.POINTER(LGModelStruct), C.POINTER(EMForwardStruct),
+                                           C.POINTER(LGPmcmcTablesStruct), _vp, _vp, _i32, C.c_int, _i32, C.POINTER(_vp)]),
     "fbsmi_lg_fsamp_destroy": (None, [_vp]),
     "fbsmi_lg_fsamp_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fbsmi_lg_fsamp_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),

@@ -4142,6 +4142,79 @@ __global__ void __launch_bounds__(kFsBlockMax) k_fs_tail(PmDev p) {
     if (threadIdx.x == 0) p.log_ell[b] = p.ell[b];
 }
 
+// The front of the same call for a model whose forward process is Euler-Maruyama (fbsmi_lg_fsamp_create_em; the Gaussian
+// Schrodinger bridge, experiments/sb/filter.py:137-161): the observation path is the y half of a joint (x, y) path from a
+// drawn x0.  What this launch adds to the engine's state:
+struct FsEmDev {
+    EmTables t;
+    const float *x0_mean, *x0_chol;   // (du), (du, du) lower factor: x0 = mean + z @ chol; both null: x0 = z
+    uint32_t* ekeys;                  // [B][T][2] interval keys of a handle with T > kFsEmKeysLds, else null
+};
+
+constexpr int kFsEmKeysLds = 1024;    // intervals whose keys a workgroup keeps in LDS (8 KB)
+
+// keys (sb/filter.py:138,153; smc.py:77), x0 (sb/filter.py:139-144), the joint path by em_path_run from concat(x0, y0)
+// with its y half written reversed into the filter's vs (:147,154), and the conditional mean of ref_sampler.  One
+// workgroup per sample, thread i < D = du + dv owns coordinate i.  The T interval keys split(key_em, T) are derived once,
+// a thread per interval, into LDS (SLAB: into the handle's ekeys); the noise of sub-step (k, j) is drawn by the thread that
+// consumes it, where em_path_run asks for it -- one sub-step ahead of its use -- and no noise buffer exists.  The x half
+// of the path is never stored.
+template <bool SLAB>
+__global__ void __launch_bounds__(kEmPathMaxD) k_fs_front_em(PmDev p, FsEmDev e) {
+    __shared__ float xs[2 * kEmPathMaxD];
+    __shared__ uint32_t sk[4];
+    __shared__ uint32_t skeys[SLAB ? 2 : 2 * kFsEmKeysLds];
+    __shared__ float sz[kEmPathMaxD], syT[kEmPathMaxD];
+    const int b = blockIdx.y, i = threadIdx.x;
+    const int T = p.T, du = p.du, dv = p.dv, D = du + dv;
+    if (i == 0) {
+        const uint32_t k0 = p.ikeys[2 * b], k1 = p.ikeys[2 * b + 1];
+        uint32_t f0, f1, g0, g1;
+        split_at(k0, k1, 3, 0, f0, f1);                                  // key_fwd  (key_bwd = split(key, 3)[1] is unused)
+        split_at(k0, k1, 3, 2, g0, g1);                                  // key_bf
+        p.fkeys[2 * b] = g0;                                             // the filter derives split(key_bf, 2)[1] itself
+        p.fkeys[2 * b + 1] = g1;
+        split_at(g0, g1, 2, 0, p.pk[4 * b], p.pk[4 * b + 1]);            // key_init, where k_pm_u0 reads its key
+        split_at(f0, f1, 2, 0, sk[0], sk[1]);                            // key_x0
+        split_at(f0, f1, 2, 1, sk[2], sk[3]);                            // key_em
+    }
+    __syncthreads();
+    uint32_t* kk = SLAB ? e.ekeys + (size_t)b * T * 2 : skeys;
+    for (int k = i; k < T; k += blockDim.x) split_at(sk[2], sk[3], T, k, kk[2 * k], kk[2 * k + 1]);
+    const bool proper = e.x0_chol != nullptr;
+    float x = 0.0f;
+    if (i < du) {
+        x = normal_at(sk[0], sk[1], (uint64_t)du, (uint64_t)i);          // normal(key_x0, (du,))
+        sz[i] = x;
+    } else if (i < D) {
+        x = p.y0[i - du];
+    }
+    __syncthreads();                                                     // the interval keys and z are in place
+    if (proper && i < du) {
+        float acc = sz[0] * e.x0_chol[i];
+        for (int c = 1; c < du; ++c) acc = acc + sz[c] * e.x0_chol[(size_t)c * du + i];
+        x = e.x0_mean[i] + acc;
+    }
+    float* vs = p.vs + (size_t)b * ((size_t)T + 1) * dv;
+    const int col = i - du;
+    if (i >= du && i < D) vs[(size_t)T * dv + col] = x;                  // vs[T] = y0
+    const uint64_t n = (uint64_t)e.t.nsub * (uint64_t)D;
+    float last = x;
+    em_path_run(e.t, T, D, x, xs,
+                [&](int k, int j) { return normal_at(kk[2 * k], kk[2 * k + 1], n, (uint64_t)j * D + i); },
+                [&](int k, float v) {                                    // (em_path_run calls emit for i < D only)
+                    if (i >= du) vs[(size_t)(T - 1 - k) * dv + col] = v;
+                    last = v;
+                });
+    if (i >= du && i < D) syT[col] = last;                               // yT = vs[0]
+    __syncthreads();
+    if (i < du) {
+        double s = 0.0;
+        for (int cc = 0; cc < dv; ++cc) s = s + p.gain[(size_t)i * dv + cc] * ((double)syT[cc] - p.m_v[cc]);
+        p.mcond[(size_t)b * du + i] = (float)(p.m_u[i] + s);
+    }
+}
+
 }  // namespace fbsmi
 
 using namespace fbsmi;
@@ -5271,6 +5344,9 @@ struct fbsmi_lg_fsamp {
     void* slab = nullptr;
     int rows = 1;                      // particles per workgroup of k_pm_u0
     int front_block = 64;              // max(du, dv) rounded up to a wave
+    bool em = false;                   // fbsmi_lg_fsamp_create_em: the front is k_fs_front_em
+    FsEmDev e{};
+    int em_block = 64;                 // du + dv rounded up to a wave
     hipGraphExec_t graph = nullptr;
 };
 
@@ -5279,7 +5355,9 @@ namespace {
 // the launch sequence of a batch of conditional samples: three launches round the filter's own
 int enqueue_fsamp(fbsmi_lg_fsamp* h, hipStream_t st) {
     const PmDev& p = h->p;
-    k_fs_front<<<dim3(1, p.C), h->front_block, 0, st>>>(p);
+    if (!h->em) k_fs_front<<<dim3(1, p.C), h->front_block, 0, st>>>(p);
+    else if (h->e.ekeys) k_fs_front_em<true><<<dim3(1, p.C), h->em_block, 0, st>>>(p, h->e);
+    else k_fs_front_em<false><<<dim3(1, p.C), h->em_block, 0, st>>>(p, h->e);
     k_pm_u0<<<dim3((p.N + h->rows - 1) / h->rows, p.C), kBlock, 0, st>>>(p, h->rows, 0);
     if (int rc = enqueue_filter(h->filt, st)) return rc;
     k_fs_tail<<<dim3(1, p.C), h->front_block, 0, st>>>(p);
@@ -5287,6 +5365,49 @@ int enqueue_fsamp(fbsmi_lg_fsamp* h, hipStream_t st) {
 }
 
 }  // namespace
+
+// the handle both create entries share: the flow-0 filter of B chains and the engine's own buffers; `em` (nullable) is the
+// Euler-Maruyama front's tables
+static int fsamp_build(const fbsmi_lg_model* m, const fbsmi_lg_pmcmc_tables* t, int32_t nparticles, int resampling,
+                       int32_t nsamples, const FsEmDev* em, fbsmi_lg_fsamp** out) {
+    fbsmi_lg_filter* filt = nullptr;
+    int rc = fbsmi_lg_filter_create(m, nparticles, 0, resampling, 0, nsamples, &filt);
+    if (rc) return rc;
+    fbsmi_lg_fsamp* h = new (std::nothrow) fbsmi_lg_fsamp();
+    if (!h) {
+        fbsmi_lg_filter_destroy(filt);
+        return fail(FBSMI_ERR_ARG, "out of host memory");
+    }
+    h->filt = filt;
+    const LgDev& d = filt->core->d;
+    PmDev& p = h->p;
+    p.C = d.C; p.N = d.N; p.du = d.du; p.dv = d.dv; p.T = d.T;
+    p.m_u = t->m_u; p.m_v = t->m_v; p.gain = t->gain; p.chol = t->chol;
+    p.F = d.F; p.sqQ = d.sqQ;
+    p.fkeys = d.keys; p.vs = d.vs; p.u0s = filt->u0s; p.usT = d.usT; p.ell = d.ell;
+    h->rows = kPmTile / p.du < kBlock ? kPmTile / p.du : kBlock;
+    h->front_block = (p.du > 64 || p.dv > 64) ? kFsBlockMax : 64;
+    if (em) {
+        h->em = true;
+        h->e = *em;
+        h->em_block = (p.du + p.dv + 63) / 64 * 64;
+    }
+    const size_t B = p.C;
+    Slab slab;
+    slab.request(&p.ikeys, B * 2);
+    slab.request(&p.pk, B * 4);
+    slab.request(&p.y0, p.dv);
+    slab.request(&p.mcond, B * p.du);
+    slab.request(&p.uT, B * p.du);
+    slab.request(&p.log_ell, B);
+    if (em && p.T > kFsEmKeysLds) slab.request(&h->e.ekeys, B * (size_t)p.T * 2);
+    if (slab.commit(&h->slab) != hipSuccess) {
+        fbsmi_lg_fsamp_destroy(h);
+        return fail(FBSMI_ERR_HIP, "lg_fsamp_create: device allocation failed");
+    }
+    *out = h;
+    return FBSMI_OK;
+}
 
 int fbsmi_lg_fsamp_create(const fbsmi_lg_model* m, const fbsmi_lg_pmcmc_tables* t, int32_t nparticles, int resampling,
                           int32_t nsamples, fbsmi_lg_fsamp** out) {
@@ -5306,37 +5427,23 @@ int fbsmi_lg_fsamp_create(const fbsmi_lg_model* m, const fbsmi_lg_pmcmc_tables* 
         for (size_t k = 0; k < F.size(); ++k) any = any || F[k] != 0.0f || Q[k] != 0.0f;
         if (!any) return fail(FBSMI_ERR_UNSUPPORTED, "lg_fsamp: the model has no exact forward transition (F, sqQ)");
     }
-    fbsmi_lg_filter* filt = nullptr;
-    int rc = fbsmi_lg_filter_create(m, nparticles, 0, resampling, 0, nsamples, &filt);
-    if (rc) return rc;
-    fbsmi_lg_fsamp* h = new (std::nothrow) fbsmi_lg_fsamp();
-    if (!h) {
-        fbsmi_lg_filter_destroy(filt);
-        return fail(FBSMI_ERR_ARG, "out of host memory");
-    }
-    h->filt = filt;
-    const LgDev& d = filt->core->d;
-    PmDev& p = h->p;
-    p.C = d.C; p.N = d.N; p.du = d.du; p.dv = d.dv; p.T = d.T;
-    p.m_u = t->m_u; p.m_v = t->m_v; p.gain = t->gain; p.chol = t->chol;
-    p.F = d.F; p.sqQ = d.sqQ;
-    p.fkeys = d.keys; p.vs = d.vs; p.u0s = filt->u0s; p.usT = d.usT; p.ell = d.ell;
-    h->rows = kPmTile / p.du < kBlock ? kPmTile / p.du : kBlock;
-    h->front_block = (p.du > 64 || p.dv > 64) ? kFsBlockMax : 64;
-    const size_t B = p.C;
-    Slab slab;
-    slab.request(&p.ikeys, B * 2);
-    slab.request(&p.pk, B * 4);
-    slab.request(&p.y0, p.dv);
-    slab.request(&p.mcond, B * p.du);
-    slab.request(&p.uT, B * p.du);
-    slab.request(&p.log_ell, B);
-    if (slab.commit(&h->slab) != hipSuccess) {
-        fbsmi_lg_fsamp_destroy(h);
-        return fail(FBSMI_ERR_HIP, "lg_fsamp_create: device allocation failed");
-    }
-    *out = h;
-    return FBSMI_OK;
+    return fsamp_build(m, t, nparticles, resampling, nsamples, nullptr, out);
+}
+
+int fbsmi_lg_fsamp_create_em(const fbsmi_lg_model* m, const fbsmi_em_forward* f, const fbsmi_lg_pmcmc_tables* t,
+                             const float* x0_mean, const float* x0_chol, int32_t nparticles, int resampling,
+                             int32_t nsamples, fbsmi_lg_fsamp** out) {
+    if (!m || !f || !t || !out) return fail(FBSMI_ERR_ARG, "lg_fsamp_create_em: null argument");
+    if (!t->m_u || !t->m_v || !t->gain || !t->chol) return fail(FBSMI_ERR_ARG, "lg_fsamp_create_em: null table");
+    if (f->nsub < 1 || !f->M || !f->c || !f->ddt || !f->s) return fail(FBSMI_ERR_ARG, "lg_fsamp_create_em: bad forward tables");
+    if ((x0_mean == nullptr) != (x0_chol == nullptr))
+        return fail(FBSMI_ERR_ARG, "lg_fsamp_create_em: x0_mean and x0_chol are both null or both set");
+    if (m->T < 1 || m->du < 1 || m->dv < 1) return fail(FBSMI_ERR_ARG, "lg_fsamp_create_em: bad model sizes");
+    if (nsamples < 1) return fail(FBSMI_ERR_ARG, "lg_fsamp_create_em: nsamples < 1");
+    if ((int64_t)m->du + m->dv > kEmPathMaxD || nsamples > 65535)   // a thread per coordinate, the sample on blockIdx.y
+        return fail(FBSMI_ERR_UNSUPPORTED, "lg_fsamp: du + dv > 256 or more than 65535 samples per call are not supported");
+    const FsEmDev em{EmTables{f->nsub, f->M, f->c, f->ddt, f->s}, x0_mean, x0_chol, nullptr};
+    return fsamp_build(m, t, nparticles, resampling, nsamples, &em, out);
 }
 
 void fbsmi_lg_fsamp_destroy(fbsmi_lg_fsamp* h) {

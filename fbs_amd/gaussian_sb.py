@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .linear_gaussian import LinearGaussianBridge
+from .linear_gaussian import LGFilter, LGFilterSampler, LinearGaussianBridge
 from .sdes.linear import make_gaussian_bw_sb
 
 
@@ -98,3 +98,45 @@ class GaussianSBBridge(LinearGaussianBridge):
     def terminal_moments(self):
         """The bridge's terminal marginal N(mean1, cov1): ref_sampler draws u0 | v0 from it (sb/gibbs.py:131-134)."""
         return self.mean1, self.cov1
+
+    # -- fused bootstrap-filter conditional sampler (experiments/sb/filter.py) ----------------------
+    def fused_sb_filter_sampler_supported(self, nparticles: int, nsamples: int = 1) -> bool:
+        """What fbsmi_lg_fsamp_create_em accepts: an Euler-Maruyama forward process of du + dv <= 256 coordinates (one
+        workgroup runs a joint path), at most 65535 samples per call and the fused filter's sizes.  Touches no device."""
+        return (getattr(self, "em_struct", None) is not None and self.du + self.dv <= 256 and 1 <= int(nsamples) <= 65535
+                and int(nparticles) >= 1 and self.fused_filter_supported(nparticles))
+
+    def sb_filter_sampler_handle(self, nparticles: int, resampling: str = "stratified", nsamples: int = 1, x0_prior=None):
+        """The fused conditional sampler of sb/filter.py:149-161 for `nsamples` samples per call.  x0_prior = (mean (du),
+        chol_lower (du, du)): the forward path starts from x0 = mean + normal @ chol_lower ('proper'); None: from
+        x0 ~ N(0, I) ('heuristic').  Cached on the bridge by the sizes and the prior's float32 bytes."""
+        prior = None
+        if x0_prior is not None:
+            prior = (np.ascontiguousarray(np.asarray(x0_prior[0], np.float32).reshape(self.du)),
+                     np.ascontiguousarray(np.asarray(x0_prior[1], np.float32).reshape(self.du, self.du)))
+        keyt = ("sb_fsamp", int(nparticles), resampling, int(nsamples),
+                None if prior is None else (prior[0].tobytes(), prior[1].tobytes()))
+        return self._cached(keyt, lambda: SBFilterSampler(self, int(nparticles), resampling, int(nsamples), prior))
+
+
+class SBFilterSampler(LGFilterSampler):
+    """Owns one fbsmi_lg_fsamp handle made by fbsmi_lg_fsamp_create_em: the bootstrap-filter conditional sampler of
+    experiments/sb/filter.py:149-161 for up to `nsamples` independent samples per call -- x0, the joint Euler-Maruyama
+    path, the reversal of its y half, initial particles, the batched flow-0 filter and the pick of the first particle in
+    one hipGraph replay.  sample() and views() are LGFilterSampler's; a ragged call runs on the bridge's handle of that
+    size and the same prior."""
+
+    def __init__(self, model: GaussianSBBridge, nparticles, resampling="stratified", nsamples=1, x0_prior=None):
+        if getattr(model, "em_struct", None) is None:
+            raise NotImplementedError("the fused SB filter sampler needs an Euler-Maruyama forward process")
+        self.prior = x0_prior
+        self._prior_dev = None if x0_prior is None else tuple(torch.from_numpy(a).to(model.device) for a in x0_prior)
+        self._setup(model, nparticles, resampling, nsamples)   # tables: lg_pmcmc_tables of the terminal marginal N(mean1, cov1)
+
+    def _create(self, h):
+        mean, chol = (None, None) if self._prior_dev is None else (t.data_ptr() for t in self._prior_dev)
+        _lib.call("fbsmi_lg_fsamp_create_em", C.byref(self.model.struct), C.byref(self.model.em_struct),
+                  C.byref(self.tables), mean, chol, self.n, LGFilter._RES[self.resampling], self.C, C.byref(h))
+
+    def _of_size(self, B):
+        return self.model.sb_filter_sampler_handle(self.n, self.resampling, B, self.prior)

@@ -654,14 +654,25 @@ class LGFilterSampler(_LGHandle):
     def __init__(self, model: LinearGaussianBridge, nparticles, resampling="stratified", nsamples=1):
         if getattr(model, "em_struct", None) is not None or model.sde is None:   # (no terminal moments to build tables from)
             raise NotImplementedError("the fused filter sampler needs an exact forward transition")
+        self._setup(model, nparticles, resampling, nsamples)
+
+    def _setup(self, model, nparticles, resampling, nsamples):
+        """What every handle of this kind holds; the library's handle comes from the subclass's ``_create``."""
         self.model, self.n, self.resampling, self.C = model, int(nparticles), resampling, int(nsamples)
         self._last = self
         self.tables = model.pmcmc_tables(None)
         h = C.c_void_p()   # sizes the engine does not take are refused by the library, with its message
         with torch.cuda.device(model.device):
-            _lib.call("fbsmi_lg_fsamp_create", C.byref(model.struct), C.byref(self.tables), self.n,
-                      LGFilter._RES[resampling], self.C, C.byref(h))
+            self._create(h)
         self.h = h
+
+    def _create(self, h):
+        _lib.call("fbsmi_lg_fsamp_create", C.byref(self.model.struct), C.byref(self.tables), self.n,
+                  LGFilter._RES[self.resampling], self.C, C.byref(h))
+
+    def _of_size(self, B):
+        """The model's cached handle of this one's kind for B samples per call."""
+        return self.model.filter_sampler_handle(self.n, self.resampling, B)
 
     def sample(self, keys, y0, return_nell=False, use_graph=True):
         """keys (B', 2), or (2,) for one sample, y0 (dv,) -> samples (B', du) [, negative log-likelihood estimates (B')]."""
@@ -671,7 +682,7 @@ class LGFilterSampler(_LGHandle):
         if not 1 <= B <= self.C:
             raise ValueError(f"{B} keys for a handle of {self.C} samples")
         if B < self.C:
-            self._last = m.filter_sampler_handle(self.n, self.resampling, B)
+            self._last = self._of_size(B)
             return self._last.sample(k, y0, return_nell, use_graph)
         self._last = self
         kt = self._key_t(k, B)

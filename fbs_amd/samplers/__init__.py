@@ -1,4 +1,5 @@
 """Mirror of fbs.samplers (fbs/samplers/__init__.py:1-3)."""
-from .smc import bootstrap_filter, filter_conditional_sampler, pmcmc_chain, pmcmc_kernel, twisted_smc
+from .smc import (bootstrap_filter, filter_conditional_sampler, pmcmc_chain, pmcmc_kernel, sb_filter_conditional_sampler,
+                  twisted_smc)
 from .resampling import multinomial, systematic, stratified, killing
 from .gibbs import gibbs_init, gibbs_kernel

@@ -142,6 +142,71 @@ def filter_conditional_sampler(keys, y0, ts, fwd_ys_sampler, ref_sampler, transi
     return (samples, nells) if return_nell else samples
 
 
+def _fused_sb_filter_sampler(ts, fwd_sampler, unpack, ref_sampler, transition_sampler, likelihood_logpdf, nparticles,
+                             resampling):
+    """(model, resampling name) when the fused SB filter sampler (SBFilterSampler) applies: the five closures belong to
+    one GaussianSBBridge in their own roles, ts is its grid, the resampler is one the fused filter has and the engine takes
+    the size; else None.  Touches no device."""
+    fused = _fused_filter(transition_sampler, likelihood_logpdf, resampling, {}, nparticles)
+    if fused is None:
+        return None
+    model = fused[0]
+    for closure, role in ((fwd_sampler, "fwd_sampler"), (unpack, "unpack"), (ref_sampler, "ref_sampler"),
+                          (transition_sampler, "transition_sampler")):
+        if getattr(closure, "_fbsmi_lg", None) is not model or getattr(closure, "_role", "") != role:
+            return None
+    supported = getattr(model, "fused_sb_filter_sampler_supported", None)   # (a LinearGaussianBridge has none)
+    if supported is None or not supported(nparticles, 1) or not model.same_grid(ts):
+        return None
+    return fused
+
+
+def sb_filter_conditional_sampler(keys, y0, ts, fwd_sampler, unpack, ref_sampler, transition_sampler, likelihood_logpdf,
+                                  nparticles, resampling, x0_prior=None, return_nell=False, _bound=FSAMP_STATE_ELEMS):
+    """The bootstrap-filter conditional sampler of experiments/sb/filter.py:137-161 for every key of `keys` (B, 2)
+    [or (2,)]: -> samples (B, du) [, negative log-likelihood estimates (B)].  The observation path is the y half of
+    fwd_sampler's joint path from (x0, y0), x0 = mean + normal @ chol_lower with x0_prior = (mean, chol_lower) ('proper')
+    or x0 = normal with None ('heuristic').  Each sample depends on its own key only.
+
+    With the closures of one GaussianSBBridge on its own grid and stratified / systematic resampling the batch runs on the
+    device (SBFilterSampler), in chunks of samples that keep B * N * du within `_bound` elements per call; otherwise the
+    driver's body runs once per key (x0 then has the prior mean's size, or the du of the bridge that fwd_sampler belongs to;
+    with neither the size is unknown and a ValueError is raised)."""
+    k = np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys).astype(np.uint32).reshape(-1, 2)
+    fused = _fused_sb_filter_sampler(ts, fwd_sampler, unpack, ref_sampler, transition_sampler, likelihood_logpdf,
+                                     nparticles, resampling)
+    chunks = plan_filter_chunks(k.shape[0], nparticles, fused[0].du, _bound) if fused is not None else None
+    if chunks:
+        model, rname = fused
+        outs = [model.sb_filter_sampler_handle(nparticles, rname, b - a, x0_prior).sample(k[a:b], y0, return_nell=True)
+                for a, b in chunks]
+        samples, nell = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+        return (samples, nell) if return_nell else samples
+    model = getattr(fwd_sampler, "_fbsmi_lg", None)
+    if x0_prior is None and model is None:
+        raise ValueError("sb_filter_conditional_sampler: the size of x0 is unknown -- closures that are not a bridge's own "
+                         "need x0_prior = (mean, chol_lower)")
+    dev = y0.device if isinstance(y0, torch.Tensor) else (model.device if model is not None else ops._default_device())
+    y0 = y0 if isinstance(y0, torch.Tensor) else torch.as_tensor(np.asarray(y0, np.float32), device=dev)
+    if x0_prior is not None:
+        mean, chol = (torch.as_tensor(np.asarray(a, np.float32), device=dev) for a in x0_prior)
+    du = int(mean.numel()) if x0_prior is not None else model.du
+    samples, nells = [], []
+    for key_ in k:                                                                  # sb/filter.py:137-161
+        key_fwd, key_bwd, key_bf = ops.split(key_, 3)
+        key_x0, key_em = ops.split(key_fwd)
+        x0 = ops.normal(key_x0, (du,), device=dev)
+        if x0_prior is not None:
+            x0 = mean + x0 @ chol
+        vs = torch.flip(unpack(fwd_sampler(key_em, x0, y0))[1], [0])
+        us, nell = bootstrap_filter(transition_sampler, likelihood_logpdf, vs, ts, ref_sampler, key_bf, nparticles,
+                                    resampling, log=True, return_last=True)
+        samples.append(us[0])
+        nells.append(nell.reshape(()))
+    samples, nells = torch.stack(samples), torch.stack(nells)
+    return (samples, nells) if return_nell else samples
+
+
 def fused_backsim(transition_logpdf, args, kwargs, ts, path):
     """The model whose fused backward simulation (LGBacksim) applies to a stored float32 path (T+1, n, du): the closure is
     one LinearGaussianBridge's own transition_logpdf, called without extra arguments on the bridge's own grid, and the

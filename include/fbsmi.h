@@ -336,6 +336,30 @@ typedef struct fbsmi_lg_fsamp fbsmi_lg_fsamp; /* opaque: a flow-0 filter of B ch
 int fbsmi_lg_fsamp_create(const fbsmi_lg_model* model, const fbsmi_lg_pmcmc_tables* tables, int32_t nparticles,
                           int resampling, int32_t nsamples, fbsmi_lg_fsamp** out);
 void fbsmi_lg_fsamp_destroy(fbsmi_lg_fsamp* h);
+/* The same engine for a model whose forward process is Euler-Maruyama (the Gaussian Schrodinger bridge): conditional_sampler
+ * of experiments/sb/filter.py:149-161 with fwd_ys_sampler of :137-148, both --x0 modes, for `nsamples` = B independent
+ * samples in every launch.  Only the front launch differs: the observation path is the y half of fbsmi_lg_em_path's joint
+ * (x, y) path from a drawn x0; the initial particles, the flow-0 filter and the tail are those of fbsmi_lg_fsamp_create,
+ * and fbsmi_lg_fsamp_run / _view / _destroy serve the handle.  `fwd` covers the model's T and D = du + dv; x0_mean (du)
+ * and x0_chol (du, du), the LOWER factor, are device float32 arrays, both null for x0 ~ N(0, I) ('heuristic') or both set
+ * ('proper').  fwd's tables, the tables' m_u, m_v, gain, chol and the prior must outlive the handle.
+ * Numeric specification (no contraction anywhere; every operation separately rounded), sample b with key = keys[b]:
+ *   keys           key_fwd, key_bwd, key_bf = split(key, 3) (sb/filter.py:153; key_bwd is unused, as in the reference);
+ *                  key_x0, key_em = split(key_fwd, 2) (:138);  key_init = split(key_bf, 2)[0] (smc.py:77);
+ *   x0             z = normal(key_x0, (du,));  heuristic: x0 = z;  proper: acc = z[0] * x0_chol[0][j], then
+ *                  acc = acc + z[c] * x0_chol[c][j] for c = 1 .. du-1, float32;  x0[j] = x0_mean[j] + acc
+ *                  (mean + z @ chol in ref_sampler's order);
+ *   forward path   out = exactly the fbsmi_em_forward block above from concat(x0, y0) with key key_em: interval k draws
+ *                  normal(split(key_em, T)[k], (nsub, D)), element j * D + i for sub-step j, coordinate i;
+ *                  vs[T] = y0, vs[T - 1 - k][c] = out[k + 1][du + c]  (the x half is never stored);
+ *   ref_sampler    u0s = ref_sampler(key_init, vs[0], n), exactly the ref_sampler block of fbsmi_lg_pmcmc above;
+ *   filter, outputs   as fbsmi_lg_fsamp_create.
+ * FBSMI_ERR_ARG for a null fwd or tables (or a null array in either), fwd->nsub < 1, and exactly one of x0_mean / x0_chol
+ * null; FBSMI_ERR_UNSUPPORTED for du + dv > 256, nsamples > 65535 and what fbsmi_lg_filter_create(..., nchains =
+ * nsamples) does not take.  (fbsmi_lg_fsamp_create keeps refusing such a model.) */
+int fbsmi_lg_fsamp_create_em(const fbsmi_lg_model* model, const fbsmi_em_forward* fwd,
+                             const fbsmi_lg_pmcmc_tables* tables, const float* x0_mean, const float* x0_chol,
+                             int32_t nparticles, int resampling, int32_t nsamples, fbsmi_lg_fsamp** out);
 /* keys (B,2) and y0 (dv) are device inputs, samples (B,du) and nell (B) (nullable) device outputs. */
 int fbsmi_lg_fsamp_run(fbsmi_lg_fsamp* h, const uint32_t* keys, const float* y0, float* samples, float* nell,
                        int use_graph, void* stream);
