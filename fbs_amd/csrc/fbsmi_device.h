@@ -578,6 +578,23 @@ __device__ __forceinline__ void block_lse_partial(const float (&l)[ITEMS], float
     s_out = tot[0];
 }
 
+// the same for one log-weight per thread in a workgroup of several 256-thread tiles (tile q = threadIdx.x / kBlock, each for
+// itself; all tiles pass the two barriers together): lds_a, lds_b hold 4 floats per tile
+// (A second text of block_lse_partial<1>: results are pinned bit for bit, so the two must stay identical in the order of
+// the sums, (w0 + w1) + (w2 + w3) over the wave totals, and in the finite_or_zero_f guard.)
+__device__ __forceinline__ void block_lse_partial_tiles(float l, float* lds_a, float* lds_b, float& m_out, float& s_out) {
+    const int lane = threadIdx.x & 63, q4 = (threadIdx.x / kBlock) * 4, wv = (threadIdx.x >> 6) & 3;
+    const float mw = wave_max(l);
+    if (lane == 0) lds_a[q4 + wv] = mw;
+    __syncthreads();
+    m_out = fmaxf(fmaxf(lds_a[q4], lds_a[q4 + 1]), fmaxf(lds_a[q4 + 2], lds_a[q4 + 3]));
+    TreePath pth;
+    const float sw = wave_upsweep(fbsmi_expf(l - finite_or_zero_f(m_out)), pth);
+    if (lane == 0) lds_b[q4 + wv] = sw;
+    __syncthreads();
+    s_out = (lds_b[q4] + lds_b[q4 + 1]) + (lds_b[q4 + 2] + lds_b[q4 + 3]);
+}
+
 // two tiles at once (a workgroup that owns slot t of tile A and slot t of tile B): one LDS exchange per stage
 __device__ __forceinline__ void block_lse_partial2(float lA, float lB, float* lds8a, float* lds8b, float& mA, float& sA,
                                                    float& mB, float& sB) {

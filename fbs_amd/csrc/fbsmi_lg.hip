@@ -16,6 +16,10 @@
 //   prop  : J ~ Cat(J_prob); per slot: rotate by j*-J, kill test, Cat(w) draw for killed slots,
 //           pin, gather the ancestor, Euler-Maruyama step, pin the reference, Gaussian
 //           log-weight, per-workgroup (max, sumexp)                      [resamplings.py:71-86, csmc.py:140-145]
+//           The per-slot part -- entry loads, roll, ancestor, Euler-Maruyama, pin, log-weight -- is ONE text for all narrow
+//           propagation kernels (GibbsStep / gibbs_step_entry / roll_source / gibbs_slot_gather / gibbs_slot_finish, beside
+//           the model closures; tree_redraw / tree_build_shared beside the tree walks): a kernel holds only its variant --
+//           who owns which slot, where its draws come from, how J and the Cat(w) search are done, how (max, sumexp) goes out
 //
 // Particle state is structure-of-arrays u[r][p] so that every per-slot access is coalesced.
 // A whole sweep (2T + ~10 launches when N is a power of two, 3T + ~10 otherwise) is captured once into a hipGraph and replayed.
@@ -541,6 +545,13 @@ __device__ __forceinline__ StepTables<DMAX> step_tables(const LgDev& d, int s) {
     return t;
 }
 
+// row p of a narrow (structure-of-arrays) particle buffer
+template <int DMAX>
+__device__ __forceinline__ void load_row(const LgDev& d, const float* up, int p, float (&u)[DMAX]) {
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * d.N + p] : 0.0f;
+}
+
 // drift_r = g_r + sum_c G_rc z_c, a c-ordered fma chain started at g_r, z = (u, v_prev)
 template <int DMAX>
 __device__ __forceinline__ float drift_row(const StepTables<DMAX>& t, int r, const float (&u)[DMAX],
@@ -576,6 +587,142 @@ __device__ __forceinline__ float lg_loglik(const StepTables<DMAX>& t, const floa
         }
     }
     return acc;
+}
+
+// ------------------------------------------------------------------------------------------
+// The per-slot step of the narrow Gibbs sweep, one text for k_lg_prop1, k_lg_propQ, k_lg_prop1t, k_lg_prop1tp, k_lg_prop1th,
+// k_lg_prop2t, k_lg_prop2 and lg_step1_body.  A kernel keeps its variant: who owns which slot, where the noise and the
+// uniforms come from, how J and the Cat(w) search are done, how the tile's (max, sumexp) is published.
+// (k_lg_prop2 shares the entry alone and keeps its own pair draws and slot tail, on a measurement: DESIGN 5.0001.)
+// ------------------------------------------------------------------------------------------
+// What a step reads at entry: all of it is addressable when the kernel starts ("round 0"), so it is loaded at the top of the
+// kernel, ahead of the noise draw, never behind a barrier and never "when needed".  Two calls, and a kernel's own entry loads
+// go BETWEEN them: gibbs_step_entry issues the scalar loads (keys, reference indices); gibbs_step_entry_rows what waits for
+// them (the reference row) and the tables.  An unused member costs no load (lg_step1_body: resampler keys, uref).
+template <int DMAX>
+struct GibbsStep {
+    uint32_t a0, a1, b0, b1, t0, t1;   // key_1 (kill test), key_2 (redraw), key_transition of step s (k_lg_keys)
+    float u3;                          // the uniform of the rotation J, drawn by k_lg_keys
+    int i_ref, j_ref;                  // the reference indices bs[s], bs[s + 1]
+    const float* up;                   // particles of step s (ping-pong u0 / u1)
+    float* un;                         // ... of step s + 1
+    float uref[DMAX];                  // the reference row up[:, i_ref]
+    StepTables<DMAX> t;
+    const float *v_prev, *v, *ustar;   // vs[s], vs[s + 1], us_star[s + 1]
+};
+
+template <int DMAX>
+__device__ __forceinline__ GibbsStep<DMAX> gibbs_step_entry(const LgDev& d, int s) {
+    GibbsStep<DMAX> g;
+    const uint32_t* kt = d.keytab + 8 * s;
+    g.a0 = kt[0]; g.a1 = kt[1]; g.b0 = kt[2]; g.b1 = kt[3]; g.t0 = kt[6]; g.t1 = kt[7];
+    g.u3 = __uint_as_float(kt[4]);
+    g.i_ref = d.bs[s];
+    g.j_ref = d.bs[s + 1];
+    g.up = (s & 1) ? d.u1 : d.u0;
+    g.un = (s & 1) ? d.u0 : d.u1;
+    return g;
+}
+
+template <int DMAX>
+__device__ __forceinline__ void gibbs_step_entry_rows(const LgDev& d, int s, GibbsStep<DMAX>& g) {
+    load_row<DMAX>(d, g.up, g.i_ref, g.uref);
+    g.t = step_tables<DMAX>(d, s);
+    g.v_prev = d.vs + (size_t)s * d.dv;
+    g.v = d.vs + (size_t)(s + 1) * d.dv;
+    g.ustar = d.us_star + (size_t)(s + 1) * d.du;
+}
+
+// roll by j* - J (resamplings.py:85): slot m receives the particle of slot roll_source(m, roll_shift(j*, J, N), N)
+__device__ __forceinline__ int roll_shift(int j_ref, int J, int N) {
+    const int shift = (j_ref - J) % N;
+    return shift < 0 ? shift + N : shift;
+}
+
+__device__ __forceinline__ int roll_source(int m, int shift, int N) {
+    const int src = m - shift;
+    return src < 0 ? src + N : src;
+}
+
+// The ancestor of slot m (resamplings.py:86) and its row.  `u` comes in as the row of the source `src` (a survivor is its own
+// ancestor); a killed slot takes the redrawn index `red`, whose row is fetched now or, EARLY, was picked into `ucand` by
+// tree_redraw; the slot j* is pinned to the reference i*.  The ancestor is stored where `live`.
+template <int DMAX, bool EARLY>
+__device__ __forceinline__ void gibbs_slot_gather(const LgDev& d, const GibbsStep<DMAX>& g, int s, int m, int src, bool killed,
+                                                  int red, float (&u)[DMAX], const float* ucand = nullptr, bool live = true) {
+    const bool pinned = m == g.j_ref;
+    const int a = pinned ? g.i_ref : (killed ? red : src);
+    if (killed && !pinned) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r)
+            if (r < d.du) u[r] = EARLY ? ucand[r] : g.up[(size_t)r * d.N + a];
+    }
+    if (pinned) {
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r) u[r] = g.uref[r];
+    }
+    if (d.As && live) d.As[(size_t)s * d.N + m] = a;
+}
+
+// Slot m from its ancestor's row `u` and its noise `xi`: transition_sampler (gp_gibbs.py:120-122) with the pin of csmc.py:143,
+// the stored path, and likelihood_logpdf on the gathered particle (csmc.py:145).  Returns the new log-weight (-inf unless
+// `live`); everything is computed, but stored only where `live` (a constant true folds away).
+template <int DMAX>
+__device__ __forceinline__ float gibbs_slot_finish(const LgDev& d, const GibbsStep<DMAX>& g, int s, int m, const float (&u)[DMAX],
+                                                   const float (&xi)[DMAX], bool live = true) {
+    const bool pinned = m == g.j_ref;
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) {
+        if (r < d.du) {
+            const float dr = drift_row<DMAX>(g.t, r, u, g.v_prev);
+            float x = (u[r] + dr * g.t.dt) + g.t.sd * xi[r];
+            if (pinned) x = g.ustar[r];
+            if (live) {
+                g.un[(size_t)r * d.N + m] = x;
+                if (d.uss) d.uss[((size_t)(s + 1) * d.N + m) * d.du + r] = x;
+            }
+        }
+    }
+    const float l = live ? lg_loglik<DMAX>(g.t, u, g.v, g.v_prev) : -__builtin_inff();
+    if (live) d.lw[m] = l;
+    return l;
+}
+
+// Two slots per thread, mA and mA + N/2: jax's random_bits puts elements i and i + n/2 of a draw on the two output words of
+// ONE Threefry call.  The noise: element mA * du + r is in the first half of the draw, its partner belongs to slot mA + N/2.
+template <int DMAX>
+__device__ __forceinline__ void pair_noise(const LgDev& d, const GibbsStep<DMAX>& g, int mA, float (&xiA)[DMAX], float (&xiB)[DMAX]) {
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) {
+        xiA[r] = 0.0f;
+        xiB[r] = 0.0f;
+        if (r < d.du) {
+            uint32_t lo_, hi_;
+            random_bits_pair(g.t0, g.t1, (uint64_t)d.N * d.du, (uint64_t)mA * d.du + r, lo_, hi_);
+            xiA[r] = normal_from_bits(lo_);
+            xiB[r] = normal_from_bits(hi_);
+        }
+    }
+}
+
+// ... their sources: the roll is a rotation mod N, so they are N/2 apart too
+__device__ __forceinline__ void pair_sources(int mA, int j_ref, int J, int N, int (&src)[2]) {
+    src[0] = roll_source(mA, roll_shift(j_ref, J, N), N);
+    src[1] = src[0] < (N >> 1) ? src[0] + (N >> 1) : src[0] - (N >> 1);
+}
+
+// ... and the kill-test and redraw uniforms uniform_at(key, N, src[h]) of both, one call per draw: the lower source is word 0
+template <int DMAX>
+__device__ __forceinline__ void pair_uniforms(const GibbsStep<DMAX>& g, int N, const int (&src)[2], float (&u1)[2], float (&u2)[2]) {
+    const bool a_low = src[0] < (N >> 1);
+    const int pbase = a_low ? src[0] : src[1];
+    uint32_t k_lo, k_hi, r_lo, r_hi;
+    random_bits_pair(g.a0, g.a1, (uint64_t)N, (uint64_t)pbase, k_lo, k_hi);
+    random_bits_pair(g.b0, g.b1, (uint64_t)N, (uint64_t)pbase, r_lo, r_hi);
+    u1[0] = fbsmi_bits_to_unit(a_low ? k_lo : k_hi);
+    u1[1] = fbsmi_bits_to_unit(a_low ? k_hi : k_lo);
+    u2[0] = fbsmi_bits_to_unit(a_low ? r_lo : r_hi);
+    u2[1] = fbsmi_bits_to_unit(a_low ? r_hi : r_lo);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -989,13 +1136,9 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop1(LgDev dd, int s) {
     __shared__ float heapJ[kHeapSizeJ];
     __shared__ float win[kBlock];
     const int N = d.N;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
     const int m = blockIdx.x * kBlock + threadIdx.x;
     const bool live = m < N;
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
     // ---- round 0
     const float lastJ = d.cdfJ[N - 1];
     const float last = d.cdf[N - 1];
@@ -1005,36 +1148,24 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop1(LgDev dd, int s) {
     const float4 hw0 = reinterpret_cast<const float4*>(d.hpW)[2 * threadIdx.x];
     const float4 hw1 = reinterpret_cast<const float4*>(d.hpW)[2 * threadIdx.x + 1];
     const float hj = d.hpJ[threadIdx.x];
-    float uref[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) uref[r] = r < d.du ? up[(size_t)r * N + i_ref] : 0.0f;
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const float u3 = __uint_as_float(kt[4]);
+    gibbs_step_entry_rows<DMAX>(d, s, g);
     float xi[DMAX];
 #pragma unroll
     for (int r = 0; r < DMAX; ++r)
-        xi[r] = (r < d.du && live) ? normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r) : 0.0f;
+        xi[r] = (r < d.du && live) ? normal_at(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r) : 0.0f;
     reinterpret_cast<float4*>(heapW)[2 * threadIdx.x] = hw0;
     reinterpret_cast<float4*>(heapW)[2 * threadIdx.x + 1] = hw1;
     heapJ[threadIdx.x] = hj;
     __syncthreads();
-    // ---- round 1: J = choice(key_3, N, (), p=J_prob) (resamplings.py:84); roll by j - J (:85)
-    const int J = bisect_uniform(d.cdfJ, N, d.levels, d.lh_j, heapJ, win, lastJ * (1.0f - u3));
-    int shift = (j_ref - J) % N;
-    if (shift < 0) shift += N;
-    int src = m - shift;
-    if (src < 0) src += N;
-    if (!live) src = 0;
+    // ---- round 1: J = choice(key_3, N, (), p=J_prob) (resamplings.py:84)
+    const int J = bisect_uniform(d.cdfJ, N, d.levels, d.lh_j, heapJ, win, lastJ * (1.0f - g.u3));
+    const int src = live ? roll_source(m, roll_shift(g.j_ref, J, N), N) : 0;
     // ---- round 2
     const float ws = d.w[src];
     float u[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * N + src] : 0.0f;
-    const float u1 = uniform_at(a0, a1, (uint64_t)N, (uint64_t)src);
-    const float u2 = uniform_at(b0, b1, (uint64_t)N, (uint64_t)src);
+    load_row<DMAX>(d, g.up, src, u);
+    const float u1 = uniform_at(g.a0, g.a1, (uint64_t)N, (uint64_t)src);
+    const float u2 = uniform_at(g.b0, g.b1, (uint64_t)N, (uint64_t)src);
     const float qK = last * (1.0f - u2);                                    // resamplings.py:73-74
     int lo, hi;
     bisect_lds_levels(N, d.lh_w, heapW, qK, lo, hi);
@@ -1042,36 +1173,10 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop1(LgDev dd, int s) {
     // ---- rounds 3, 4
 #pragma unroll 1
     for (int rem = d.levels - d.lh_w; rem > 0; rem -= 3) bisect_round3(d.cdf, lo, hi, qK, killed);
-    const bool pinned = m == j_ref;
-    const int a = pinned ? i_ref : (killed ? hi : src);                     // :86
     // ---- round 5
-    if (killed && !pinned) {
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) u[r] = up[(size_t)r * N + a];
-    }
-    if (pinned) {
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) u[r] = uref[r];
-    }
+    gibbs_slot_gather<DMAX, false>(d, g, s, m, src, killed, hi, u, nullptr, live);
     float lv[1] = {-__builtin_inff()};
-    if (live) {
-        if (d.As) d.As[(size_t)s * N + m] = a;
-        // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) {
-            if (r < d.du) {
-                const float dr = drift_row<DMAX>(t, r, u, v_prev);
-                float x = (u[r] + dr * t.dt) + t.sd * xi[r];
-                if (pinned) x = ustar[r];
-                un[(size_t)r * N + m] = x;
-                if (d.uss) d.uss[((size_t)(s + 1) * N + m) * d.du + r] = x;
-            }
-        }
-        const float l = lg_loglik<DMAX>(t, u, v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
-        d.lw[m] = l;
-        lv[0] = l;
-    }
+    if (live) lv[0] = gibbs_slot_finish<DMAX>(d, g, s, m, u, xi);
     float mx, sx;
     block_lse_partial<1>(lv, xch[0], xch[1], mx, sx);
     if (threadIdx.x == 0) {
@@ -1125,12 +1230,8 @@ __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
     __shared__ uint16_t queue[TILE];
     __shared__ int qn;
     const int N = d.N;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
     const int tile0 = blockIdx.x * TILE;
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
     // ---- round 0
     const float lastJ = d.cdfJ[N - 1];
     const float last = d.cdf[N - 1];
@@ -1139,20 +1240,15 @@ __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
     const float4 hw0 = reinterpret_cast<const float4*>(d.hpW)[2 * threadIdx.x];
     const float4 hw1 = reinterpret_cast<const float4*>(d.hpW)[2 * threadIdx.x + 1];
     const float hj = d.hpJ[threadIdx.x];
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const float u3 = __uint_as_float(kt[4]);
+    gibbs_step_entry_rows<DMAX>(d, s, g);
     reinterpret_cast<float4*>(heapW)[2 * threadIdx.x] = hw0;
     reinterpret_cast<float4*>(heapW)[2 * threadIdx.x + 1] = hw1;
     heapJ[threadIdx.x] = hj;
     if (threadIdx.x == 0) qn = 0;
     __syncthreads();
     // ---- round 1: J = choice(key_3, N, (), p=J_prob) (resamplings.py:84); roll by j - J (:85)
-    const int J = bisect_uniform(d.cdfJ, N, d.levels, d.lh_j, heapJ, win, lastJ * (1.0f - u3));
-    int shift = (j_ref - J) % N;
-    if (shift < 0) shift += N;
+    const int J = bisect_uniform(d.cdfJ, N, d.levels, d.lh_j, heapJ, win, lastJ * (1.0f - g.u3));
+    const int shift = roll_shift(g.j_ref, J, N);
     // ---- phase 1: the kill tests (resamplings.py:71), the sources' weights rotated but contiguous
     uint32_t kmask = 0;
     const int lane = threadIdx.x & 63;
@@ -1165,14 +1261,12 @@ __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
         for (int k = 0; k < B; ++k) {
             const int m = tile0 + (i0 + k) * kBlock + (int)threadIdx.x;
             live[k] = m < N;
-            int sc = m - shift;
-            if (sc < 0) sc += N;
-            src[k] = live[k] ? sc : 0;
+            src[k] = live[k] ? roll_source(m, shift, N) : 0;
             ws[k] = d.w[src[k]];
         }
 #pragma unroll
         for (int k = 0; k < B; ++k) {
-            const float u1 = uniform_at(a0, a1, (uint64_t)N, (uint64_t)src[k]);
+            const float u1 = uniform_at(g.a0, g.a1, (uint64_t)N, (uint64_t)src[k]);
             const bool killed = live[k] && (u1 * w_max >= ws[k]);
             kmask |= (killed ? 1u : 0u) << (i0 + k);
             const unsigned long long bal = __ballot(killed);
@@ -1201,9 +1295,8 @@ __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
             const int e = e0 + k * kBlock + (int)threadIdx.x;
             on[k] = e < nq;
             slot[k] = on[k] ? (int)queue[e] : 0;
-            int sc = tile0 + slot[k] - shift;
-            if (sc < 0) sc += N;
-            const float u2 = uniform_at(b0, b1, (uint64_t)N, (uint64_t)(on[k] ? sc : 0));
+            const int sc = roll_source(tile0 + slot[k], shift, N);
+            const float u2 = uniform_at(g.b0, g.b1, (uint64_t)N, (uint64_t)(on[k] ? sc : 0));
             qK[k] = last * (1.0f - u2);
         }
         bisect_lds_levels_x2(N, d.lh_w, heapW, qK, lo, hi);
@@ -1225,42 +1318,28 @@ __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
             const int slot = (i0 + k) * kBlock + (int)threadIdx.x;
             m[k] = tile0 + slot;
             live[k] = m[k] < N;
-            int sc = m[k] - shift;
-            if (sc < 0) sc += N;
+            const int sc = roll_source(m[k], shift, N);
             const bool killed = (kmask >> (i0 + k)) & 1u;
             const int red = anc[slot];                 // (garbage unless killed)
-            a[k] = !live[k] ? 0 : (m[k] == j_ref ? i_ref : (killed ? red : sc));          // :86
+            a[k] = !live[k] ? 0 : (m[k] == g.j_ref ? g.i_ref : (killed ? red : sc));      // :86
         }
 #pragma unroll
         for (int k = 0; k < B; ++k) {
 #pragma unroll
-            for (int r = 0; r < DMAX; ++r) u[k][r] = r < d.du ? up[(size_t)r * N + a[k]] : 0.0f;
+            for (int r = 0; r < DMAX; ++r) u[k][r] = r < d.du ? g.up[(size_t)r * N + a[k]] : 0.0f;
         }
 #pragma unroll
         for (int k = 0; k < B; ++k) {
 #pragma unroll
             for (int r = 0; r < DMAX; ++r)
-                xi[k][r] = r < d.du ? normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)(live[k] ? m[k] : 0) * d.du + r) : 0.0f;
+                xi[k][r] = r < d.du ? normal_at(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)(live[k] ? m[k] : 0) * d.du + r) : 0.0f;
         }
 #pragma unroll
         for (int k = 0; k < B; ++k) {
-            const bool pinned = m[k] == j_ref;
             float l = -__builtin_inff();
             if (live[k]) {
                 if (d.As) d.As[(size_t)s * N + m[k]] = a[k];
-                // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-                for (int r = 0; r < DMAX; ++r) {
-                    if (r < d.du) {
-                        const float dr = drift_row<DMAX>(t, r, u[k], v_prev);
-                        float x = (u[k][r] + dr * t.dt) + t.sd * xi[k][r];
-                        if (pinned) x = ustar[r];
-                        un[(size_t)r * N + m[k]] = x;
-                        if (d.uss) d.uss[((size_t)(s + 1) * N + m[k]) * d.du + r] = x;
-                    }
-                }
-                l = lg_loglik<DMAX>(t, u[k], v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
-                d.lw[m[k]] = l;
+                l = gibbs_slot_finish<DMAX>(d, g, s, m[k], u[k], xi[k]);
             }
             lvs[(i0 + k) * kBlock + threadIdx.x] = l;
         }
@@ -1340,7 +1419,7 @@ struct TreeEntry {
     float4 stg[kMidN / 2];  // this thread's part of trWtop
 };
 
-__device__ __forceinline__ TreeEntry tree_entry_loads(const LgDev& d, int i_ref) {
+__device__ __forceinline__ TreeEntry tree_entry_loads(const LgDev& d) {
     const int tid = threadIdx.x, nb = d.nb - d.plus1;   // tiles of the power-of-two part
     TreeEntry e;
     const bool tl = tid < nb;
@@ -1522,156 +1601,123 @@ __device__ __forceinline__ int tree_leaves_walk(float4 w4, int lo, float q, floa
     return q <= e1 ? leaf : leaf + 1;
 }
 
-// One tile per workgroup: a single chain's launches, the pinned launches and N = 2^k + 1.  Only HALVES = 1 is launched since
-// k_lg_prop1tp (below) took over the workgroups of several tiles; the text is the kernel as it was measured with them (the
-// same kernel with the HALVES > 1 branches taken out compiles to another schedule, 3 % slower for a single chain at N = 65 536).
+// The ancestor of a killed slot is one of the last four leaves or the slot behind them: for narrow states its row is fetched
+// together with those leaves (one dependent round trip less).
+template <int DMAX>
+constexpr bool kEarlyRow = DMAX <= 2;
+
+// A killed slot's redraw below the LDS levels (rounds 3, 4 of k_lg_prop1t / k_lg_prop1tp / k_lg_prop1th), from the node
+// (tile, h, P, E) where tree_search_lds stopped: the published nodes in one round trip, the last four leaves of w -- and with
+// kEarlyRow the rows of the five candidate ancestors -- in another.  Returns the redrawn index; kEarlyRow: its row in `ucand`.
+template <int DMAX>
+__device__ __forceinline__ int tree_redraw(const LgDev& d, const float* up, int tile, int h, float q, float P, float E,
+                                           float (&ucand)[DMAX]) {
+    const int N = d.N;
+    const TreeRound rd = tree_round_load(d, tile, h);
+    const int lo = tree_round_walk(rd, tile, h, q, P, E);
+    const float4 w4 = *reinterpret_cast<const float4*>(d.w + lo);
+    float4 ug[DMAX];
+    float ue[DMAX];
+    if (kEarlyRow<DMAX>) {
+        const int en = lo + 4 < N ? lo + 4 : N - 1;
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r) {
+            ug[r] = r < d.du ? *reinterpret_cast<const float4*>(up + (size_t)r * N + lo) : make_float4(0.f, 0.f, 0.f, 0.f);
+            ue[r] = r < d.du ? up[(size_t)r * N + en] : 0.0f;
+        }
+    }
+    const int red = tree_leaves_walk(w4, lo, q, P, E);
+    if (kEarlyRow<DMAX>) {
+        const int k = red - lo;
+#pragma unroll
+        for (int r = 0; r < DMAX; ++r) {
+            const float lo2 = (k & 1) ? ug[r].y : ug[r].x, hi2 = (k & 1) ? ug[r].w : ug[r].z;
+            ucand[r] = k >= 4 ? ue[r] : ((k & 2) ? hi2 : lo2);
+        }
+    }
+    return red;
+}
+
+// tree_build in a workgroup of several tiles (powers of two only): the first 256 threads (`builder`, wave-uniform) build the
+// trees and find J, the other waves wait at tree_build's barriers instead of repeating ~450 instructions each.  Returns J to
+// every thread; `last` = cdf[N - 1] = the root of the w tree.
+__device__ __forceinline__ int tree_build_shared(const LgDev& d, const TreeEntry& e, TreeLds& L, bool builder, int i_ref, float u3,
+                                                 float w_max, float inv_n, float& last) {
+    __shared__ int Jsh;
+    __shared__ float lastsh;
+    if (builder) {
+        float lastb, rootW;
+        const int J = tree_build(d, e, L, i_ref, u3, w_max, inv_n, lastb, rootW);
+        if (threadIdx.x == 0) {
+            Jsh = J;
+            lastsh = lastb;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kTreeBuildBarriers; ++k) __syncthreads();   // the barriers of tree_build
+    }
+    __syncthreads();
+    last = lastsh;
+    return Jsh;
+}
+
+// k_lg_prop1t, one tile per workgroup: a single chain's launches, the pinned launches and N = 2^k + 1.  Every workgroup builds
+// the trees and finds J itself, every slot draws its own noise and uniforms.  The one kernel of the tree walk with dead slots
+// (the extra tile of N = 2^k + 1 holds one): they run the whole step on source 0 and store nothing.
+// Only HALVES = 1 is launched.  The parameter and its branches stay because the kernel without them compiles to a schedule
+// that runs a single chain at N = 65 536 4 % slower (measured again with the shared slot body).
 template <int DMAX, int HALVES>
 __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) {
     const LgDev d = chain_view(dd, blockIdx.y);
     __shared__ TreeLds L;
     __shared__ float part[2][4 * HALVES];
-    __shared__ int Jsh;
-    __shared__ float lastsh;
     const int N = d.N, tid = threadIdx.x & (kBlock - 1), half = threadIdx.x / kBlock;
     int bx = blockIdx.x;
-    if (dd.pin) {   // (pinned launches use HALVES == 1)
+    if (dd.pin) {   // pinned launches (HALVES == 1): only every eighth block works (LgDev.pin)
         if (blockIdx.x & 7) return;
         bx = blockIdx.x >> 3;
     }
     const int tileb = bx * HALVES + half;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
     const int m = tileb * kBlock + tid;   // N is a multiple of the tile: every slot is live -- but for N = 2^k + 1, whose last
-    const bool live = m < N;              // workgroup holds one slot (LgDev.plus1; HALVES == 1 then)
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    const bool live = m < N;              // workgroup holds one slot (LgDev.plus1)
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
     // ---- round 0: everything addressable now
     const float w_max = d.scal[1];
     const float inv_n = 1.0f / (float)N;   // N is a power of two: x / N == x * inv_n exactly
     TreeEntry te{};
-    if (half == 0) te = tree_entry_loads(d, i_ref);
-    float uref[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) uref[r] = r < d.du ? up[(size_t)r * N + i_ref] : 0.0f;
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const float u3 = __uint_as_float(kt[4]);
+    if (half == 0) te = tree_entry_loads(d);
+    gibbs_step_entry_rows<DMAX>(d, s, g);
     float xi[DMAX];
 #pragma unroll
     for (int r = 0; r < DMAX; ++r)
-        xi[r] = r < d.du ? normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)(live ? m : 0) * d.du + r) : 0.0f;
+        xi[r] = r < d.du ? normal_at(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)(live ? m : 0) * d.du + r) : 0.0f;
     float last, rootW;
     int J;
     if (HALVES == 1) {
-        J = tree_build(d, te, L, i_ref, u3, w_max, inv_n, last, rootW);
+        J = tree_build(d, te, L, g.i_ref, g.u3, w_max, inv_n, last, rootW);
     } else {
-        if (half == 0) {
-            J = tree_build(d, te, L, i_ref, u3, w_max, inv_n, last, rootW);
-            if (tid == 0) {
-                Jsh = J;
-                lastsh = last;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kTreeBuildBarriers; ++k) __syncthreads();   // the barriers of tree_build
-        }
-        __syncthreads();
-        J = Jsh;
-        last = lastsh;
+        J = tree_build_shared(d, te, L, half == 0, g.i_ref, g.u3, w_max, inv_n, last);
         rootW = last;    // (several tiles per workgroup: powers of two only)
     }
-    int shift = (j_ref - J) % N;   // roll by j - J (:85)
-    if (shift < 0) shift += N;
-    int src = m - shift;
-    if (src < 0) src += N;
-    if (!live) src = 0;
+    const int src = live ? roll_source(m, roll_shift(g.j_ref, J, N), N) : 0;
     // ---- round 2
     const float ws = d.w[src];
     float u[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * N + src] : 0.0f;
-    const float u1 = uniform_at(a0, a1, (uint64_t)N, (uint64_t)src);
-    const float u2 = uniform_at(b0, b1, (uint64_t)N, (uint64_t)src);
-    const float qK[1] = {last * (1.0f - u2)};                               // resamplings.py:73-74
-    float P[1] = {0.0f}, E[1] = {rootW};
-    int tile[1], h[1], hi[1] = {0};
-    tree_search_lds(L, d.nb - d.plus1, qK[0], P[0], E[0], tile[0], h[0]);
-    const bool killed[1] = {live && u1 * w_max >= ws};                      // :71
-    // ---- rounds 3, 4 (killed slots only)
-    // The ancestor is one of the last four leaves or the slot behind them: for narrow states its row is fetched together
-    // with those leaves (one dependent round trip less).
-    constexpr bool kEarlyRow = DMAX <= 2;
+    load_row<DMAX>(d, g.up, src, u);
+    const float u1 = uniform_at(g.a0, g.a1, (uint64_t)N, (uint64_t)src);
+    const float u2 = uniform_at(g.b0, g.b1, (uint64_t)N, (uint64_t)src);
+    const float q = last * (1.0f - u2);                                     // resamplings.py:73-74
+    float P = 0.0f, E = rootW;
+    int tile, h, red = 0;
+    tree_search_lds(L, d.nb - d.plus1, q, P, E, tile, h);
+    const bool killed = live && u1 * w_max >= ws;                           // :71
+    // ---- rounds 3, 4 (killed slots only), round 5
     float ucand[DMAX];
-    if (killed[0]) {
-        const TreeRound rd = tree_round_load(d, tile[0], h[0]);
-        const int lo = tree_round_walk(rd, tile[0], h[0], qK[0], P[0], E[0]);
-        const float4 w4 = *reinterpret_cast<const float4*>(d.w + lo);
-        float4 ug[DMAX];
-        float ue[DMAX];
-        if (kEarlyRow) {
-            const int e = lo + 4 < N ? lo + 4 : N - 1;
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) {
-                ug[r] = r < d.du ? *reinterpret_cast<const float4*>(up + (size_t)r * N + lo) : make_float4(0.f, 0.f, 0.f, 0.f);
-                ue[r] = r < d.du ? up[(size_t)r * N + e] : 0.0f;
-            }
-        }
-        hi[0] = tree_leaves_walk(w4, lo, qK[0], P[0], E[0]);
-        if (kEarlyRow) {
-            const int k = hi[0] - lo;
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) {
-                const float lo2 = (k & 1) ? ug[r].y : ug[r].x, hi2 = (k & 1) ? ug[r].w : ug[r].z;
-                ucand[r] = k >= 4 ? ue[r] : ((k & 2) ? hi2 : lo2);
-            }
-        }
-    }
-    const bool pinned = m == j_ref;
-    const int a = pinned ? i_ref : (killed[0] ? hi[0] : src);               // :86
-    // ---- round 5
-    if (killed[0] && !pinned) {
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) u[r] = kEarlyRow ? ucand[r] : up[(size_t)r * N + a];
-    }
-    if (pinned) {
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) u[r] = uref[r];
-    }
-    float lv[1];
-    if (d.As && live) d.As[(size_t)s * N + m] = a;
-    // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) {
-        if (r < d.du) {
-            const float dr = drift_row<DMAX>(t, r, u, v_prev);
-            float x = (u[r] + dr * t.dt) + t.sd * xi[r];
-            if (pinned) x = ustar[r];
-            if (live) {
-                un[(size_t)r * N + m] = x;
-                if (d.uss) d.uss[((size_t)(s + 1) * N + m) * d.du + r] = x;
-            }
-        }
-    }
-    const float l = live ? lg_loglik<DMAX>(t, u, v, v_prev) : -__builtin_inff();   // likelihood_logpdf on the gathered particle (csmc.py:145)
-    if (live) d.lw[m] = l;
-    lv[0] = l;
+    if (killed) red = tree_redraw<DMAX>(d, g.up, tile, h, q, P, E, ucand);
+    gibbs_slot_gather<DMAX, kEarlyRow<DMAX>>(d, g, s, m, src, killed, red, u, ucand, live);
+    const float l = gibbs_slot_finish<DMAX>(d, g, s, m, u, xi, live);
     float mx, sx;
-    {   // the tile's (max, sumexp): block_lse_partial per half
-        const int lane = threadIdx.x & 63, wv = (threadIdx.x >> 6) & 3, h4 = half * 4;
-        const float mw = wave_max(lv[0]);
-        if (lane == 0) part[0][h4 + wv] = mw;
-        __syncthreads();
-        mx = fmaxf(fmaxf(part[0][h4], part[0][h4 + 1]), fmaxf(part[0][h4 + 2], part[0][h4 + 3]));
-        TreePath pth;
-        const float sw_ = wave_upsweep(fbsmi_expf(lv[0] - finite_or_zero_f(mx)), pth);
-        if (lane == 0) part[1][h4 + wv] = sw_;
-        __syncthreads();
-        sx = (part[1][h4] + part[1][h4 + 1]) + (part[1][h4 + 2] + part[1][h4 + 3]);
-    }
+    block_lse_partial_tiles(l, part[0], part[1], mx, sx);
     if (tid == 0) {
         d.bmax[tileb] = mx;
         d.bsumexp[tileb] = sx;
@@ -1681,177 +1727,85 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1t(LgDev dd, int s) 
 // k_lg_prop1tp, HALVES = 2, 4: a workgroup of 512 / 1024 threads owns tiles N/2 APART -- HALVES / 2 adjacent tiles from blockIdx.x * HALVES / 2
 // on (the lower side) and the tiles nb / 2 further on (the upper side) -- so thread p of the lower side and thread p of the
 // upper side hold the slots m and m + N/2: the two elements that jax's random_bits puts on the two output words of ONE Threefry
-// call of the noise draw.  The first 256 threads build the trees and find J (the other waves wait at the barriers instead
-// of repeating ~450 instructions each); meanwhile the upper side draws the noise of BOTH slots of its pairs and hands the
-// lower side's through LDS (kPairNoise), so the tree-building waves draw no noise and the workgroup makes one noise call
-// per pair.  Then every thread does its slot.  Every output is written per tile / per slot exactly as by the one-tile
-// workgroups: only the owner changes.
+// call of the noise draw.  The first 256 threads build the trees and find J (tree_build_shared); meanwhile the upper side
+// draws the noise of BOTH slots of its pairs and hands the lower side's through LDS (kPairNoise), so the tree-building waves
+// draw no noise and the workgroup makes one noise call per pair.  Then every thread does its slot, with its own kill-test and
+// redraw draws.  Every output is written per tile / per slot exactly as by the one-tile workgroups: only the owner changes.
 // The kill-test and redraw uniforms are source-indexed and pair up the same way (the rotation keeps the two sources N/2
 // apart), and the redraw searches of the ~7 % killed slots can be dealt out from an LDS queue as in k_lg_propQ: both were
 // built and measured on top of this kernel and left out -- the two workgroup barriers they need after J (exchange /
 // queue, results) cost more than the ~270 instructions per wave they save.  k_lg_prop1th (below) pairs the
 // uniforms without a barrier by putting both slots of a pair in one wave; this kernel stays under FBSMI_PROP_HALFWAVE=0.
+//
+// The partner's noise goes through LDS, 4 * DMAX * NP bytes here and twice that in k_lg_prop1th (both normals): up to 8 / 16 KB
+// for the instantiations up to DMAX = 4.  DMAX = 16 would take up to 64 KB next to the 22 KB of trees, so there every slot
+// draws its own noise (same bits: random_bits_at is the same call with the other word kept).
+template <int DMAX>
+constexpr bool kPairNoise = DMAX <= 4;
+
 template <int DMAX, int HALVES>
 __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1tp(LgDev dd, int s) {
     static_assert(HALVES == 2 || HALVES == 4, "two sides of HALVES / 2 tiles");
     constexpr int HP = HALVES / 2, NP = kBlock * HP;   // tiles per side; pairs
-    // The partner's noise goes through LDS, 4 * DMAX * NP bytes: up to 8 KB for the instantiations up to DMAX = 4.  DMAX = 16
-    // would take 16 / 32 KB next to the 22 KB of trees, so there every slot draws its own noise (same bits: random_bits_at
-    // is the same call with the other word kept).
-    constexpr bool kPairNoise = DMAX <= 4;
-    // The ancestor is one of the last four leaves or the slot behind them: for narrow states its row is fetched together
-    // with those leaves (one dependent round trip less).
-    constexpr bool kEarlyRow = DMAX <= 2;
     const LgDev d = chain_view(dd, blockIdx.y);
     __shared__ TreeLds L;
     __shared__ float part[2][4 * HALVES];
-    __shared__ int Jsh;
-    __shared__ float lastsh;
-    __shared__ float xish[kPairNoise ? DMAX : 1][NP];   // noise of the lower slots, drawn by their partners
-    const int N = d.N, tid = threadIdx.x & (kBlock - 1), half = threadIdx.x / kBlock, lane = threadIdx.x & 63;
+    __shared__ float xish[kPairNoise<DMAX> ? DMAX : 1][NP];   // noise of the lower slots, drawn by their partners
+    const int N = d.N, tid = threadIdx.x & (kBlock - 1), half = threadIdx.x / kBlock;
     const bool upper = half >= HP;                       // (wave-uniform)
     const int pr = (int)threadIdx.x - (upper ? NP : 0);  // the pair
     const int mL = blockIdx.x * NP + pr;                 // its lower slot, < N/2
     const int m = upper ? mL + (N >> 1) : mL;
     const int tileb = m / kBlock;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
     // ---- round 0: everything addressable now
     const float w_max = d.scal[1];
     const float inv_n = 1.0f / (float)N;   // N is a power of two: x / N == x * inv_n exactly
     TreeEntry te{};
-    if (half == 0) te = tree_entry_loads(d, i_ref);
-    float uref[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) uref[r] = r < d.du ? up[(size_t)r * N + i_ref] : 0.0f;
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const float u3 = __uint_as_float(kt[4]);
-    float xi[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) xi[r] = 0.0f;
-    if (!kPairNoise) {
+    if (half == 0) te = tree_entry_loads(d);
+    gibbs_step_entry_rows<DMAX>(d, s, g);
+    float xi[DMAX] = {};
+    if (!kPairNoise<DMAX>) {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) xi[r] = normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
+            if (r < d.du) xi[r] = normal_at(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
     } else if (upper) {   // element mL * du + r is in the first half of the draw, its partner belongs to slot mL + N/2
 #pragma unroll
         for (int r = 0; r < DMAX; ++r) {
             if (r < d.du) {
                 uint32_t lo_, hi_;
-                random_bits_pair(t0, t1, (uint64_t)N * d.du, (uint64_t)mL * d.du + r, lo_, hi_);
+                random_bits_pair(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)mL * d.du + r, lo_, hi_);
                 xish[r][pr] = normal_from_bits(lo_);
                 xi[r] = normal_from_bits(hi_);
             }
         }
     }
     float last;
-    int J;
-    if (half == 0) {
-        float rootW;
-        J = tree_build(d, te, L, i_ref, u3, w_max, inv_n, last, rootW);
-        if (tid == 0) {
-            Jsh = J;
-            lastsh = last;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kTreeBuildBarriers; ++k) __syncthreads();   // the barriers of tree_build
-    }
-    __syncthreads();
-    J = Jsh;
-    last = lastsh;   // == the root of the w tree (powers of two only)
-    int shift = (j_ref - J) % N;   // roll by j - J (:85)
-    if (shift < 0) shift += N;
-    int src = m - shift;
-    if (src < 0) src += N;
+    const int J = tree_build_shared(d, te, L, half == 0, g.i_ref, g.u3, w_max, inv_n, last);
+    const int src = roll_source(m, roll_shift(g.j_ref, J, N), N);
     // ---- round 2
     const float ws = d.w[src];
     float u[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * N + src] : 0.0f;
-    if (kPairNoise && !upper) {
+    load_row<DMAX>(d, g.up, src, u);
+    if (kPairNoise<DMAX> && !upper) {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r)
             if (r < d.du) xi[r] = xish[r][pr];
     }
-    const float u1 = uniform_at(a0, a1, (uint64_t)N, (uint64_t)src);
-    const float u2 = uniform_at(b0, b1, (uint64_t)N, (uint64_t)src);
+    const float u1 = uniform_at(g.a0, g.a1, (uint64_t)N, (uint64_t)src);
+    const float u2 = uniform_at(g.b0, g.b1, (uint64_t)N, (uint64_t)src);
     const float q = last * (1.0f - u2);                                     // resamplings.py:73-74
     float P = 0.0f, E = last;
     int tile, h, red = 0;
     tree_search_lds(L, d.nb, q, P, E, tile, h);
     const bool killed = u1 * w_max >= ws;                                   // :71
-    // ---- rounds 3, 4 (killed slots only)
+    // ---- rounds 3, 4 (killed slots only), round 5
     float ucand[DMAX];
-    if (killed) {
-        const TreeRound rd = tree_round_load(d, tile, h);
-        const int lo = tree_round_walk(rd, tile, h, q, P, E);
-        const float4 w4 = *reinterpret_cast<const float4*>(d.w + lo);
-        float4 ug[DMAX];
-        float ue[DMAX];
-        if (kEarlyRow) {
-            const int en = lo + 4 < N ? lo + 4 : N - 1;
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) {
-                ug[r] = r < d.du ? *reinterpret_cast<const float4*>(up + (size_t)r * N + lo) : make_float4(0.f, 0.f, 0.f, 0.f);
-                ue[r] = r < d.du ? up[(size_t)r * N + en] : 0.0f;
-            }
-        }
-        red = tree_leaves_walk(w4, lo, q, P, E);
-        if (kEarlyRow) {
-            const int k = red - lo;
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) {
-                const float lo2 = (k & 1) ? ug[r].y : ug[r].x, hi2 = (k & 1) ? ug[r].w : ug[r].z;
-                ucand[r] = k >= 4 ? ue[r] : ((k & 2) ? hi2 : lo2);
-            }
-        }
-    }
-    const bool pinned = m == j_ref;
-    const int a = pinned ? i_ref : (killed ? red : src);                    // :86
-    // ---- round 5
-    if (killed && !pinned) {
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) u[r] = kEarlyRow ? ucand[r] : up[(size_t)r * N + a];
-    }
-    if (pinned) {
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) u[r] = uref[r];
-    }
-    if (d.As) d.As[(size_t)s * N + m] = a;
-    // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) {
-        if (r < d.du) {
-            const float dr = drift_row<DMAX>(t, r, u, v_prev);
-            float x = (u[r] + dr * t.dt) + t.sd * xi[r];
-            if (pinned) x = ustar[r];
-            un[(size_t)r * N + m] = x;
-            if (d.uss) d.uss[((size_t)(s + 1) * N + m) * d.du + r] = x;
-        }
-    }
-    const float l = lg_loglik<DMAX>(t, u, v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
-    d.lw[m] = l;
+    if (killed) red = tree_redraw<DMAX>(d, g.up, tile, h, q, P, E, ucand);
+    gibbs_slot_gather<DMAX, kEarlyRow<DMAX>>(d, g, s, m, src, killed, red, u, ucand);
+    const float l = gibbs_slot_finish<DMAX>(d, g, s, m, u, xi);
     float mx, sx;
-    {   // the tile's (max, sumexp): block_lse_partial per tile
-        const int wv = (threadIdx.x >> 6) & 3, h4 = half * 4;
-        const float mw = wave_max(l);
-        if (lane == 0) part[0][h4 + wv] = mw;
-        __syncthreads();
-        mx = fmaxf(fmaxf(part[0][h4], part[0][h4 + 1]), fmaxf(part[0][h4 + 2], part[0][h4 + 3]));
-        TreePath pth;
-        const float sw_ = wave_upsweep(fbsmi_expf(l - finite_or_zero_f(mx)), pth);
-        if (lane == 0) part[1][h4 + wv] = sw_;
-        __syncthreads();
-        sx = (part[1][h4] + part[1][h4 + 1]) + (part[1][h4 + 2] + part[1][h4 + 3]);
-    }
+    block_lse_partial_tiles(l, part[0], part[1], mx, sx);
     if (tid == 0) {
         d.bmax[tileb] = mx;
         d.bsumexp[tileb] = sx;
@@ -1905,19 +1859,10 @@ template <int DMAX, int HALVES>
 __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s) {
     static_assert(HALVES == 2 || HALVES == 4, "two sides of HALVES / 2 tiles");
     constexpr int HP = HALVES / 2, NP = kBlock * HP;   // tiles per side; pairs
-    // Both normals of a pair go through LDS, 8 * DMAX * NP bytes: up to 16 KB for the instantiations up to DMAX = 4.  DMAX = 16
-    // would take 32 / 64 KB next to the 22 KB of trees, so there every slot draws its own noise (same bits: random_bits_at
-    // is the same call with the other word kept).
-    constexpr bool kPairNoise = DMAX <= 4;
-    // The ancestor is one of the last four leaves or the slot behind them: for narrow states its row is fetched together
-    // with those leaves (one dependent round trip less).
-    constexpr bool kEarlyRow = DMAX <= 2;
     const LgDev d = chain_view(dd, blockIdx.y);
     __shared__ TreeLds L;
     __shared__ __attribute__((aligned(16))) float part[2][2][HP][8];   // [max | sumexp][side][tile of the side][block of 32 slots]
-    __shared__ int Jsh;
-    __shared__ float lastsh;
-    __shared__ float xish[kPairNoise ? DMAX : 1][2 * NP];   // noise of every slot, at the index of the thread that owns it
+    __shared__ float xish[kPairNoise<DMAX> ? DMAX : 1][2 * NP];   // noise of every slot, at the index of the thread that owns it
     const int N = d.N, hN = N >> 1, tid = threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int hw = lane >> 5;                            // 0: a lower slot, 1: its partner N/2 above
     const bool builder = tid < kBlock;                   // (wave-uniform) the threads of tree_build
@@ -1926,31 +1871,18 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
     const int m = mL + (hw ? hN : 0);
     const int ts = wv >> 3, bk = wv & 7;                 // the tile of the side, and this half-wave's block of 32 slots in it
     const int tileb = blockIdx.x * HP + ts + (hw ? d.nb >> 1 : 0);   // == m / kBlock
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
     // ---- round 0: everything addressable now
     const float w_max = d.scal[1];
     const float inv_n = 1.0f / (float)N;   // N is a power of two: x / N == x * inv_n exactly
     TreeEntry te{};
-    if (builder) te = tree_entry_loads(d, i_ref);
-    float uref[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) uref[r] = r < d.du ? up[(size_t)r * N + i_ref] : 0.0f;
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const float u3 = __uint_as_float(kt[4]);
-    float xi[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) xi[r] = 0.0f;
-    if (!kPairNoise) {
+    if (builder) te = tree_entry_loads(d);
+    gibbs_step_entry_rows<DMAX>(d, s, g);
+    float xi[DMAX] = {};
+    if (!kPairNoise<DMAX>) {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) xi[r] = normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
+            if (r < d.du) xi[r] = normal_at(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
     } else if (tid >= NP) {   // pair p: element (slot p of the lower side) * du + r is in the first half of the draw, its
                               // partner belongs to the slot N/2 above; the owners are lanes l and l + 32 of wave p / 32
         const int p = tid - NP, own = (p >> 5) * 64 + (p & 31);
@@ -1959,38 +1891,20 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
         for (int r = 0; r < DMAX; ++r) {
             if (r < d.du) {
                 uint32_t lo_, hi_;
-                random_bits_pair(t0, t1, (uint64_t)N * d.du, (uint64_t)mp * d.du + r, lo_, hi_);
+                random_bits_pair(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)mp * d.du + r, lo_, hi_);
                 xish[r][own] = normal_from_bits(lo_);
                 xish[r][own + 32] = normal_from_bits(hi_);
             }
         }
     }
     float last;
-    int J;
-    if (builder) {
-        float rootW;
-        J = tree_build(d, te, L, i_ref, u3, w_max, inv_n, last, rootW);
-        if (tid == 0) {
-            Jsh = J;
-            lastsh = last;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kTreeBuildBarriers; ++k) __syncthreads();   // the barriers of tree_build
-    }
-    __syncthreads();
-    J = Jsh;
-    last = lastsh;   // == the root of the w tree (powers of two only)
-    int shift = (j_ref - J) % N;   // roll by j - J (:85)
-    if (shift < 0) shift += N;
-    int src = m - shift;
-    if (src < 0) src += N;
+    const int J = tree_build_shared(d, te, L, builder, g.i_ref, g.u3, w_max, inv_n, last);
+    const int src = roll_source(m, roll_shift(g.j_ref, J, N), N);
     // ---- round 2
     const float ws = d.w[src];
     float u[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * N + src] : 0.0f;
-    if (kPairNoise) {
+    load_row<DMAX>(d, g.up, src, u);
+    if (kPairNoise<DMAX>) {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r)
             if (r < d.du) xi[r] = xish[r][tid];
@@ -2003,7 +1917,7 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
     const int c = src & (hN - 1);
     const bool swp = (src >= hN) != (hw != 0);
     uint32_t o0, o1;
-    threefry2x32(hw ? b0 : a0, hw ? b1 : a1, (uint32_t)c, (uint32_t)(c + hN), o0, o1);
+    threefry2x32(hw ? g.b0 : g.a0, hw ? g.b1 : g.a1, (uint32_t)c, (uint32_t)(c + hN), o0, o1);
     const auto xw = __builtin_amdgcn_permlane32_swap(swp ? o1 : o0, swp ? o0 : o1, false, false);
     const float u1 = fbsmi_bits_to_unit(xw[0]);
     const float u2 = fbsmi_bits_to_unit(xw[1]);
@@ -2012,58 +1926,11 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
     int tile, h, red = 0;
     tree_search_lds(L, d.nb, q, P, E, tile, h);
     const bool killed = u1 * w_max >= ws;                                   // :71
-    // ---- rounds 3, 4 (killed slots only)
+    // ---- rounds 3, 4 (killed slots only), round 5
     float ucand[DMAX];
-    if (killed) {
-        const TreeRound rd = tree_round_load(d, tile, h);
-        const int lo = tree_round_walk(rd, tile, h, q, P, E);
-        const float4 w4 = *reinterpret_cast<const float4*>(d.w + lo);
-        float4 ug[DMAX];
-        float ue[DMAX];
-        if (kEarlyRow) {
-            const int en = lo + 4 < N ? lo + 4 : N - 1;
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) {
-                ug[r] = r < d.du ? *reinterpret_cast<const float4*>(up + (size_t)r * N + lo) : make_float4(0.f, 0.f, 0.f, 0.f);
-                ue[r] = r < d.du ? up[(size_t)r * N + en] : 0.0f;
-            }
-        }
-        red = tree_leaves_walk(w4, lo, q, P, E);
-        if (kEarlyRow) {
-            const int k = red - lo;
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) {
-                const float lo2 = (k & 1) ? ug[r].y : ug[r].x, hi2 = (k & 1) ? ug[r].w : ug[r].z;
-                ucand[r] = k >= 4 ? ue[r] : ((k & 2) ? hi2 : lo2);
-            }
-        }
-    }
-    const bool pinned = m == j_ref;
-    const int a = pinned ? i_ref : (killed ? red : src);                    // :86
-    // ---- round 5
-    if (killed && !pinned) {
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) u[r] = kEarlyRow ? ucand[r] : up[(size_t)r * N + a];
-    }
-    if (pinned) {
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) u[r] = uref[r];
-    }
-    if (d.As) d.As[(size_t)s * N + m] = a;
-    // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) {
-        if (r < d.du) {
-            const float dr = drift_row<DMAX>(t, r, u, v_prev);
-            float x = (u[r] + dr * t.dt) + t.sd * xi[r];
-            if (pinned) x = ustar[r];
-            un[(size_t)r * N + m] = x;
-            if (d.uss) d.uss[((size_t)(s + 1) * N + m) * d.du + r] = x;
-        }
-    }
-    const float l = lg_loglik<DMAX>(t, u, v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
-    d.lw[m] = l;
+    if (killed) red = tree_redraw<DMAX>(d, g.up, tile, h, q, P, E, ucand);
+    gibbs_slot_gather<DMAX, kEarlyRow<DMAX>>(d, g, s, m, src, killed, red, u, ucand);
+    const float l = gibbs_slot_finish<DMAX>(d, g, s, m, u, xi);
     float mx, sx;
     {   // the tile's (max, sumexp): block_lse_partial per tile, with the tile's 256 slots held as eight blocks of 32 by the
         // lower (upper) half-waves of eight waves.  Levels 0-4 of the canonical tree stay inside a half-wave; levels 5-7
@@ -2088,68 +1955,39 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
 }
 
 // The two-launch step with TWO slots per thread (see k_lg_prop2 below for the pairing): the trees, J and the
-// staging are built once per 512 slots.
+// staging are built once per 512 slots.  The two Cat(w) searches run in lockstep, so it has its own walk below the LDS levels
+// (not tree_redraw) and fetches the killed slots' rows afterwards.
 template <int DMAX>
 __global__ void __launch_bounds__(kBlock) k_lg_prop2t(LgDev dd, int s) {
     const LgDev d = chain_view(dd, blockIdx.y);
     __shared__ TreeLds L;
     __shared__ float xch2[2][8];
-    const int N = d.N, half = N >> 1, tid = threadIdx.x;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
+    const int N = d.N, tid = threadIdx.x;
     const int mA = blockIdx.x * kBlock + tid;   // < N/2
-    const int m[2] = {mA, mA + half};
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    const int m[2] = {mA, mA + (N >> 1)};
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
     // ---- round 0
     const float w_max = d.scal[1];
     const float inv_n = 1.0f / (float)N;
-    const TreeEntry te = tree_entry_loads(d, i_ref);
-    float uref[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) uref[r] = r < d.du ? up[(size_t)r * N + i_ref] : 0.0f;
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const float u3 = __uint_as_float(kt[4]);
+    const TreeEntry te = tree_entry_loads(d);
+    gibbs_step_entry_rows<DMAX>(d, s, g);
     float xi[2][DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) {
-        xi[0][r] = 0.0f;
-        xi[1][r] = 0.0f;
-        if (r < d.du) {   // element mA * du + r is in the first half of the draw, its partner belongs to slot mA + N/2
-            uint32_t lo_, hi_;
-            random_bits_pair(t0, t1, (uint64_t)N * d.du, (uint64_t)mA * d.du + r, lo_, hi_);
-            xi[0][r] = normal_from_bits(lo_);
-            xi[1][r] = normal_from_bits(hi_);
-        }
-    }
+    pair_noise<DMAX>(d, g, mA, xi[0], xi[1]);
     float last;
     float rootW_unused;
-    const int J = tree_build(d, te, L, i_ref, u3, w_max, inv_n, last, rootW_unused);
-    int shift = (j_ref - J) % N;
-    if (shift < 0) shift += N;
+    const int J = tree_build(d, te, L, g.i_ref, g.u3, w_max, inv_n, last, rootW_unused);
     int src[2];
-    src[0] = mA - shift;
-    if (src[0] < 0) src[0] += N;
-    const bool a_low = src[0] < half;          // the two sources are N/2 apart too
-    src[1] = a_low ? src[0] + half : src[0] - half;
-    const int pbase = a_low ? src[0] : src[1];
+    pair_sources(mA, g.j_ref, J, N, src);
     // ---- round 2
     float ws[2], u[2][DMAX];
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
         ws[h2] = d.w[src[h2]];
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) u[h2][r] = r < d.du ? up[(size_t)r * N + src[h2]] : 0.0f;
+#pragma unroll   // (not load_row: through it k_lg_prop2<4> takes 73 VGPRs instead of 71 and loses a wave per SIMD)
+        for (int r = 0; r < DMAX; ++r) u[h2][r] = r < d.du ? g.up[(size_t)r * N + src[h2]] : 0.0f;
     }
-    uint32_t k_lo, k_hi, r_lo, r_hi;
-    random_bits_pair(a0, a1, (uint64_t)N, (uint64_t)pbase, k_lo, k_hi);
-    random_bits_pair(b0, b1, (uint64_t)N, (uint64_t)pbase, r_lo, r_hi);
-    const float u1[2] = {fbsmi_bits_to_unit(a_low ? k_lo : k_hi), fbsmi_bits_to_unit(a_low ? k_hi : k_lo)};
-    const float u2[2] = {fbsmi_bits_to_unit(a_low ? r_lo : r_hi), fbsmi_bits_to_unit(a_low ? r_hi : r_lo)};
+    float u1[2], u2[2];
+    pair_uniforms<DMAX>(g, N, src, u1, u2);
     const float qK[2] = {last * (1.0f - u2[0]), last * (1.0f - u2[1])};    // resamplings.py:73-74
     float P[2] = {0.0f, 0.0f}, E[2] = {last, last};
     int tile[2], h[2], hi[2] = {0, 0};
@@ -2202,35 +2040,12 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop2t(LgDev dd, int s) {
         if (killed[0]) hi[0] = tree_leaves_walk(w40, lo0, qK[0], P[0], E[0]);
         if (killed[1]) hi[1] = tree_leaves_walk(w41, lo1, qK[1], P[1], E[1]);
     }
+    // ---- round 5
     float lnew[2];
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
-        const bool pinned = m[h2] == j_ref;
-        const int a = pinned ? i_ref : (killed[h2] ? hi[h2] : src[h2]);     // :86
-        // ---- round 5
-        if (killed[h2] && !pinned) {
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r)
-                if (r < d.du) u[h2][r] = up[(size_t)r * N + a];
-        }
-        if (pinned) {
-#pragma unroll
-            for (int r = 0; r < DMAX; ++r) u[h2][r] = uref[r];
-        }
-        if (d.As) d.As[(size_t)s * N + m[h2]] = a;
-        // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) {
-            if (r < d.du) {
-                const float dr = drift_row<DMAX>(t, r, u[h2], v_prev);
-                float x = (u[h2][r] + dr * t.dt) + t.sd * xi[h2][r];
-                if (pinned) x = ustar[r];
-                un[(size_t)r * N + m[h2]] = x;
-                if (d.uss) d.uss[((size_t)(s + 1) * N + m[h2]) * d.du + r] = x;
-            }
-        }
-        lnew[h2] = lg_loglik<DMAX>(t, u[h2], v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
-        d.lw[m[h2]] = lnew[h2];
+        gibbs_slot_gather<DMAX, false>(d, g, s, m[h2], src[h2], killed[h2], hi[h2], u[h2]);
+        lnew[h2] = gibbs_slot_finish<DMAX>(d, g, s, m[h2], u[h2], xi[h2]);
     }
     float mxA, sxA, mxB, sxB;
     block_lse_partial2(lnew[0], lnew[1], xch2[0], xch2[1], mxA, sxA, mxB, sxB);
@@ -2257,14 +2072,9 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop2(LgDev dd, int s) {
     __shared__ __attribute__((aligned(16))) float heapW[kHeapSizeW];
     __shared__ float heapJ[kHeapSizeJ];
     __shared__ float win[kBlock];
-    const int N = d.N, half = N >> 1;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t a0 = kt[0], a1 = kt[1], b0 = kt[2], b1 = kt[3], t0 = kt[6], t1 = kt[7];
-    const int i_ref = d.bs[s], j_ref = d.bs[s + 1];
+    const int N = d.N;
     const int mA = blockIdx.x * kBlock + threadIdx.x;   // < N/2
-    const int m[2] = {mA, mA + half};
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
+    const int m[2] = {mA, mA + (N >> 1)};
     // ---- round 0
     const float lastJ = d.cdfJ[N - 1];
     const float last = d.cdf[N - 1];
@@ -2274,14 +2084,8 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop2(LgDev dd, int s) {
     const float4 hw0 = reinterpret_cast<const float4*>(d.hpW)[2 * threadIdx.x];
     const float4 hw1 = reinterpret_cast<const float4*>(d.hpW)[2 * threadIdx.x + 1];
     const float hj = d.hpJ[threadIdx.x];
-    float uref[DMAX];
-#pragma unroll
-    for (int r = 0; r < DMAX; ++r) uref[r] = r < d.du ? up[(size_t)r * N + i_ref] : 0.0f;
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
-    const float u3 = __uint_as_float(kt[4]);
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);   // (behind the heap loads here; in front of them the registers are the same)
+    gibbs_step_entry_rows<DMAX>(d, s, g);
     float xi[2][DMAX];
 #pragma unroll
     for (int r = 0; r < DMAX; ++r) {
@@ -2289,7 +2093,7 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop2(LgDev dd, int s) {
         xi[1][r] = 0.0f;
         if (r < d.du) {   // element mA * du + r is in the first half of the draw, its partner belongs to slot mA + N/2
             uint32_t lo_, hi_;
-            random_bits_pair(t0, t1, (uint64_t)N * d.du, (uint64_t)mA * d.du + r, lo_, hi_);
+            random_bits_pair(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)mA * d.du + r, lo_, hi_);
             xi[0][r] = normal_from_bits(lo_);
             xi[1][r] = normal_from_bits(hi_);
         }
@@ -2299,8 +2103,9 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop2(LgDev dd, int s) {
     heapJ[threadIdx.x] = hj;
     __syncthreads();
     // ---- round 1: J (resamplings.py:84), the rotation j - J (:85)
-    const int J = bisect_uniform(d.cdfJ, N, d.levels, d.lh_j, heapJ, win, lastJ * (1.0f - u3));
-    int shift = (j_ref - J) % N;
+    const int J = bisect_uniform(d.cdfJ, N, d.levels, d.lh_j, heapJ, win, lastJ * (1.0f - g.u3));
+    const int half = N >> 1;
+    int shift = (g.j_ref - J) % N;
     if (shift < 0) shift += N;
     int src[2];
     src[0] = mA - shift;
@@ -2313,12 +2118,12 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop2(LgDev dd, int s) {
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
         ws[h2] = d.w[src[h2]];
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) u[h2][r] = r < d.du ? up[(size_t)r * N + src[h2]] : 0.0f;
+#pragma unroll   // (not load_row: through it k_lg_prop2<4> takes 73 VGPRs instead of 71 and loses a wave per SIMD)
+        for (int r = 0; r < DMAX; ++r) u[h2][r] = r < d.du ? g.up[(size_t)r * N + src[h2]] : 0.0f;
     }
     uint32_t k_lo, k_hi, r_lo, r_hi;
-    random_bits_pair(a0, a1, (uint64_t)N, (uint64_t)pbase, k_lo, k_hi);
-    random_bits_pair(b0, b1, (uint64_t)N, (uint64_t)pbase, r_lo, r_hi);
+    random_bits_pair(g.a0, g.a1, (uint64_t)N, (uint64_t)pbase, k_lo, k_hi);
+    random_bits_pair(g.b0, g.b1, (uint64_t)N, (uint64_t)pbase, r_lo, r_hi);
     const float u1[2] = {fbsmi_bits_to_unit(a_low ? k_lo : k_hi), fbsmi_bits_to_unit(a_low ? k_hi : k_lo)};
     const float u2[2] = {fbsmi_bits_to_unit(a_low ? r_lo : r_hi), fbsmi_bits_to_unit(a_low ? r_hi : r_lo)};
     const float qK[2] = {last * (1.0f - u2[0]), last * (1.0f - u2[1])};    // resamplings.py:73-74
@@ -2328,34 +2133,35 @@ __global__ void __launch_bounds__(kBlock) k_lg_prop2(LgDev dd, int s) {
     // ---- rounds 3, 4
 #pragma unroll 1
     for (int rem = d.levels - d.lh_w; rem > 0; rem -= 3) bisect_round3_x2(d.cdf, lo, hi, qK, killed);
+    // ---- round 5.  The pair draws and the slot tail are this kernel's own text, not pair_noise / pair_sources / pair_uniforms /
+    // gibbs_slot_gather / gibbs_slot_finish as in k_lg_prop2t: through them <4> ran 2.8 % slower
     float lnew[2];
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
-        const bool pinned = m[h2] == j_ref;
-        const int a = pinned ? i_ref : (killed[h2] ? hi[h2] : src[h2]);     // :86
-        // ---- round 5
+        const bool pinned = m[h2] == g.j_ref;
+        const int a = pinned ? g.i_ref : (killed[h2] ? hi[h2] : src[h2]);     // :86
         if (killed[h2] && !pinned) {
 #pragma unroll
             for (int r = 0; r < DMAX; ++r)
-                if (r < d.du) u[h2][r] = up[(size_t)r * N + a];
+                if (r < d.du) u[h2][r] = g.up[(size_t)r * N + a];
         }
         if (pinned) {
 #pragma unroll
-            for (int r = 0; r < DMAX; ++r) u[h2][r] = uref[r];
+            for (int r = 0; r < DMAX; ++r) u[h2][r] = g.uref[r];
         }
         if (d.As) d.As[(size_t)s * N + m[h2]] = a;
         // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
 #pragma unroll
         for (int r = 0; r < DMAX; ++r) {
             if (r < d.du) {
-                const float dr = drift_row<DMAX>(t, r, u[h2], v_prev);
-                float x = (u[h2][r] + dr * t.dt) + t.sd * xi[h2][r];
-                if (pinned) x = ustar[r];
-                un[(size_t)r * N + m[h2]] = x;
+                const float dr = drift_row<DMAX>(g.t, r, u[h2], g.v_prev);
+                float x = (u[h2][r] + dr * g.t.dt) + g.t.sd * xi[h2][r];
+                if (pinned) x = g.ustar[r];
+                g.un[(size_t)r * N + m[h2]] = x;
                 if (d.uss) d.uss[((size_t)(s + 1) * N + m[h2]) * d.du + r] = x;
             }
         }
-        lnew[h2] = lg_loglik<DMAX>(t, u[h2], v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
+        lnew[h2] = lg_loglik<DMAX>(g.t, u[h2], g.v, g.v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
         d.lw[m[h2]] = lnew[h2];
     }
     float mxA, sxA, mxB, sxB;
@@ -3330,40 +3136,20 @@ template <int DMAX>
 __device__ __forceinline__ void lg_step1_body(const LgDev& d, int s, LgwPreLds& pre) {
     const int N = d.N, m = threadIdx.x;
     const bool live = m < N;
-    const uint32_t* kt = d.keytab + 8 * s;
-    const uint32_t t0 = kt[6], t1 = kt[7];
-    const int j_ref = d.bs[s + 1];
-    const float* __restrict__ up = (s & 1) ? d.u1 : d.u0;
-    float* __restrict__ un = (s & 1) ? d.u0 : d.u1;
-    const StepTables<DMAX> t = step_tables<DMAX>(d, s);
-    const float* v_prev = d.vs + (size_t)s * d.dv;
-    const float* v = d.vs + (size_t)(s + 1) * d.dv;
-    const float* ustar = d.us_star + (size_t)(s + 1) * d.du;
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
+    gibbs_step_entry_rows<DMAX>(d, s, g);
     float xi[DMAX];
     auto draw_noise = [&]() {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r)
-            xi[r] = (r < d.du && live) ? normal_at(t0, t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r) : 0.0f;
+            xi[r] = (r < d.du && live) ? normal_at(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r) : 0.0f;
     };
-    lgw_pre_body<false>(d, s, true, pre, draw_noise);
+    lgw_pre_body<false>(d, s, true, pre, draw_noise);   // J, the kill tests and the redraws, in LDS: ancestors in pre.ancS (stored there)
     if (live) {
         const int a = pre.ancS[m];
-        const bool pinned = m == j_ref;
         float u[DMAX];
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * N + a] : 0.0f;
-        // transition_sampler (gp_gibbs.py:120-122) and the pin of csmc.py:143
-#pragma unroll
-        for (int r = 0; r < DMAX; ++r) {
-            if (r < d.du) {
-                const float dr = drift_row<DMAX>(t, r, u, v_prev);
-                float x = (u[r] + dr * t.dt) + t.sd * xi[r];
-                if (pinned) x = ustar[r];
-                un[(size_t)r * N + m] = x;
-                if (d.uss) d.uss[((size_t)(s + 1) * N + m) * d.du + r] = x;
-            }
-        }
-        d.lw[m] = lg_loglik<DMAX>(t, u, v, v_prev);   // likelihood_logpdf on the gathered particle (csmc.py:145)
+        load_row<DMAX>(d, g.up, a, u);
+        gibbs_slot_finish<DMAX>(d, g, s, m, u, xi);
     }
 }
 
