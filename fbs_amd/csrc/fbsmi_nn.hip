@@ -843,9 +843,11 @@ extern "C" int fbsmi_nn_groupnorm_silu(const void* x, void* y, int dtype, int64_
                                        const float* gamma, const float* beta, float eps, const float* scale,
                                        const float* shift, const float* xbias, const void* residual, const float* rbias,
                                        void* stream) {
-    if (!x || !y || !gamma || !beta || B < 0 || n < 1 || C < 8 || groups < 1 || groups > 32 || (dtype != 0 && dtype != 1) ||
+    if (!x || !y || !gamma || !beta || B < 0 || n < 1 || C < 8 || groups < 1 || (dtype != 0 && dtype != 1) ||
         (scale == nullptr) != (shift == nullptr))
         return fail(FBSMI_ERR_ARG, "nn_groupnorm_silu: bad arguments");
+    // more than 32 groups is a valid GroupNorm this kernel has no room for (gMean / gRstd): the caller keeps the library's
+    if (groups > 32) return fail(FBSMI_ERR_UNSUPPORTED, "nn_groupnorm_silu: at most 32 groups");
     const int slots = C / 8;
     if (C % (8 * groups) != 0 || slots > 256 || 256 % slots != 0)
         return fail(FBSMI_ERR_UNSUPPORTED, "nn_groupnorm_silu: C must be a multiple of 8 * groups and C / 8 must divide 256");
@@ -975,14 +977,15 @@ extern "C" int fbsmi_nn_conv3x3(const void* x, int32_t xstride, const void* w, i
         return fail(FBSMI_ERR_ARG, "nn_conv3x3: bad arguments");
     if ((Cin != 64 && Cin != 128) || Cout < 64 || Cout % 64 != 0)
         return fail(FBSMI_ERR_UNSUPPORTED, "nn_conv3x3: Cin must be 64 or 128 and Cout a multiple of 64");
-    if (B == 0) return FBSMI_OK;
     const long long npix = (long long)B * H * W;
     if (npix > 0x3fffffff) return fail(FBSMI_ERR_UNSUPPORTED, "nn_conv3x3: more than 2^30 pixels per call");
     const int ck = Cin / 16;
     const int nco = ck == 4 ? 64 : 32;
     ConvShape sh;
+    // before the empty batch: the answer for a shape is the one fbsmi_nn_conv3x3_supported gives, whatever B is
     if (!conv3x3_shape(W, Cin, sh))
         return fail(FBSMI_ERR_UNSUPPORTED, "nn_conv3x3: image rows too wide for the staged range (ask fbsmi_nn_conv3x3_supported first)");
+    if (B == 0) return FBSMI_OK;
     const int nw = sh.nw, mb = sh.mb;
     const size_t lds = sh.lds;
     const int tile = 32 * mb * nw;

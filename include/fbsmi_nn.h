@@ -39,7 +39,8 @@ int fbsmi_nn_conv3x3(const void* x, int32_t xstride, const void* w, int32_t wstr
 
 /* 1 when fbsmi_nn_conv3x3 has a tile shape for rows of W pixels and slices of Cin channels (the staged pixel range must fit
  * 160 KB of LDS beside the weights: W < 248 at Cin = 64, W <= 100 at Cin = 128), else 0: the caller then keeps the library
- * convolution.  No GPU work. */
+ * convolution.  No GPU work.  fbsmi_nn_conv3x3 answers FBSMI_ERR_UNSUPPORTED for exactly the shapes this says 0 for, also
+ * when B = 0 (a supported shape with B = 0 is FBSMI_OK and launches nothing). */
 int fbsmi_nn_conv3x3_supported(int32_t H, int32_t W, int32_t Cin, int32_t Cout);
 
 /* 1x1 projection to 64 channels, bfloat16 on the matrix cores, with its consumer folded in:
@@ -59,7 +60,9 @@ int fbsmi_nn_proj64(const void* a, int32_t Ca, const void* b, int32_t Cb, const 
  * convolution that produced it): (B, n, C) token-major
  * (channels_last); C a multiple of 8 * groups; gamma, beta, xbias: (C) float32;
  * scale, shift: (B, C) float32 or NULL (no modulation).  dtype: 0 float32, 1 bfloat16 (statistics in float32,
- * Welford / Chan merging). */
+ * Welford / Chan merging).  At most 32 groups, C / 8 a divisor of 256: a GroupNorm outside that (33 groups, C = 384) is
+ * FBSMI_ERR_UNSUPPORTED, like every shape the kernels have no path for -- the caller then keeps the library's; groups < 1,
+ * n < 1, a NULL array or only one of scale / shift is FBSMI_ERR_ARG. */
 int fbsmi_nn_groupnorm_silu(const void* x, void* y, int dtype, int64_t B, int32_t n, int32_t C, int32_t groups,
                             const float* gamma, const float* beta, float eps, const float* scale, const float* shift,
                             const float* xbias, const void* residual, const float* rbias, void* stream);
