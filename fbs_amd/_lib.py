@@ -12,7 +12,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip",
-                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip", "fbsmi_bs.hip")]
+                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip", "fbsmi_bs.hip", "fbsmi_kf.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", "fbsmi_device.h"), os.path.join(_HERE, "csrc", "fbsmi_host.h"),
                 os.path.join(_HERE, "csrc", "fbsmi_em_path.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi.h"), os.path.join(_HERE, "..", "include", "fbsmi_math.h"),
@@ -164,6 +164,13 @@ class CSGMModelStruct(C.Structure):
                 ("s", C.c_void_p), ("m_ref", C.c_void_p), ("S_ref", C.c_void_p)]
 
 
+class KFModelStruct(C.Structure):
+    _fields_ = [("du", C.c_int32), ("dv", C.c_int32), ("T", C.c_int32),
+                ("H", C.c_void_p), ("e", C.c_void_p), ("Pm", C.c_void_p), ("c", C.c_void_p), ("AK", C.c_void_p),
+                ("W", C.c_void_p), ("lconst", C.c_void_p), ("Lt", C.c_void_p), ("F", C.c_void_p), ("sqQ", C.c_void_p),
+                ("m_u", C.c_void_p), ("m_v", C.c_void_p), ("gain", C.c_void_p)]
+
+
 class EMMaskStruct(C.Structure):
     _fields_ = [("du", C.c_int32), ("dv", C.c_int32), ("u_off", C.c_void_p), ("v_off", C.c_void_p),
                 ("role", C.c_void_p)]
@@ -238,6 +245,11 @@ SIGNATURES = {
     "fbsmi_csgm_destroy": (None, [_vp]),
     "fbsmi_csgm_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "fbsmi_csgm_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
+    "fbsmi_kf_create": (C.c_int, [C.POINTER(KFModelStruct), _i32, C.POINTER(_vp)]),
+    "fbsmi_kf_destroy": (None, [_vp]),
+    "fbsmi_kf_sample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fbsmi_kf_filter": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "fbsmi_kf_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
     "fbsmi_lg_sweep_profile": (C.c_int, [_vp, C.c_int]),
     "fbsmi_lg_sweep_kernel_us": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "fbsmi_em_concat": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),

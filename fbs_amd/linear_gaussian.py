@@ -327,6 +327,11 @@ class LinearGaussianBridge:
         keyt = ("fsamp", int(nparticles), resampling, int(nsamples))
         return self._cached(keyt, lambda: LGFilterSampler(self, int(nparticles), resampling, int(nsamples)))
 
+    def kalman_handle(self, nsamples: int = 1):
+        """The fused Kalman-filter conditional sampler (fbs_amd/lg_kalman.py, LGKalman) for `nsamples` samples per call."""
+        from .lg_kalman import LGKalman
+        return self._cached(("kalman", int(nsamples)), lambda: LGKalman(self, int(nsamples)))
+
     def gibbs_kernel(self, key, x0, y0, bs_star, nparticles, explicit_backward=True, explicit_final=False,
                      use_graph=True, marg_y=False):
         """One fused sweep; same returns as fbs.samplers.gibbs_kernel: (x0, us_star, bs_star, acc)."""

@@ -501,6 +501,75 @@ int fbsmi_csgm_run(fbsmi_csgm* h, const uint32_t* keys, const float* u0, float* 
  * path (T+1, B, d) (store_path only). */
 int fbsmi_csgm_view(fbsmi_csgm* h, int which, void* dst, int64_t* count, void* stream);
 
+/* ---- batched, device-resident Kalman-filter conditional sampler for the analytic model ------------
+ * The exact counterpart of fbsmi_lg_fsamp: the discretised model that bootstrap_filter targets is linear-Gaussian,
+ *   u_0 | v_0 ~ N(m_0, Sigma_0)  (ref_sampler),   (u_{k+1}; v_{k+1}) | u_k, v_k ~ N(M_k (u_k; v_k) + dt g[k], sd[k]^2 I),
+ * with the likelihood of v_{k+1} given the PREVIOUS state and the state then propagated, so its filtering law
+ * p(u_T | v_0..v_T) = N(m_T, cov_T) and its marginal likelihood p(v_1..v_T | v_0) are closed-form: the N -> infinity limit
+ * of fbsmi_lg_fsamp's sample and the exact value of the -nell it estimates.  (experiments/toy/gp_kf.py differentiates the
+ * observation mean with respect to v_prev and passes sqrt(dt) b where a covariance is expected; this is the exact
+ * filter, not that recursion.  Flags, key schedule and output of the driver are gp_kf.py's.)
+ * Tables (fbs_amd/lg_kalman.py, lg_kalman_tables; float64 on the host, rounded once to float32).  Step k leaves
+ * t_prev = ts[k]; M_k = I + dt G[k] = [[A, B], [C, D]] with the u rows first, (c; e) = dt g[k], q = sd[k]^2, Sigma_0 the
+ * conditional covariance of ref_sampler; the covariance recursion does not depend on the data:
+ *   S = C Sigma C^T + q I,  K = Sigma C^T inv(S),  Sigma+ = Sigma - K S K^T,  Sigma <- A Sigma+ A^T + q I (symmetrised)
+ *   H[k] = [C D] (dv, D),  e[k] (dv),  Pm[k] = [A B] (du, D),  c[k] (du),  AK[k] = A K (du, dv),
+ *   W[k] = inv(lower Cholesky factor of S) (dv, dv),  lconst[k] = -(log det S + dv log 2 pi) / 2,
+ *   Lt = transposed lower Cholesky factor of cov_T = Sigma after step T-1.
+ * Numeric specification (float32, no contraction beyond the chains named; tests/kf_restate.py restates it in numpy),
+ * sample b with key = keys[b]:
+ *   keys          key_fwd, key_bwd, key_kf = split(key, 3)            (gp_kf.py:151; key_bwd is unused, as there)
+ *   forward path  exactly the "forward path" line of fbsmi_lg_fsamp: r[0] = y0, r[k+1] = F[k] * r[k] + sqQ[k] * xi[k],
+ *                 xi = normal(key_fwd, (T, dv)); vs[k] = r[T - k]
+ *   m_0           exactly the float64 conditional mean of the ref_sampler block of fbsmi_lg_pmcmc with yT = vs[0],
+ *                 rounded to float32
+ *   step k        z = (m, vs[k])  (D values)
+ *                 pred_i: acc = e[k][i], then acc = fbsmi_fmaf(H[k][i][c], z[c], acc), c ascending;
+ *                 r_i = vs[k+1][i] - pred_i
+ *                 m'_j : acc = c[k][j], then acc = fbsmi_fmaf(Pm[k][j][c], z[c], acc), c ascending, then continued with
+ *                        acc = fbsmi_fmaf(AK[k][j][c], r[c], acc), c ascending
+ *                 qv_i : acc = 0, then acc = fbsmi_fmaf(W[k][i][c], r[c], acc), c ascending
+ *                 ss   : acc = 0, then acc = fbsmi_fmaf(qv_i, qv_i, acc), i ascending
+ *                 ll <- ll + ((-0.5f * ss) + lconst[k]),  ll = 0 before step 0
+ *   sample        zz = normal(key_kf, (du,));  x_j: acc = m_T[j], then acc = fbsmi_fmaf(Lt[c][j], zz[c], acc), c ascending
+ *                 (mean + zz @ chol)
+ *   outputs       samples[b] = x, means[b] = m_T, loglik[b] = ll.
+ * A call is two plain launches on the caller's stream (the front: keys, path, m_0; the recursion and the draw), nothing
+ * on the host inside it. */
+typedef struct fbsmi_kf_model {
+    int32_t du, dv, T;
+    const float* H;      /* (T, dv, du + dv) */
+    const float* e;      /* (T, dv) */
+    const float* Pm;     /* (T, du, du + dv) */
+    const float* c;      /* (T, du) */
+    const float* AK;     /* (T, du, dv) */
+    const float* W;      /* (T, dv, dv) */
+    const float* lconst; /* (T) */
+    const float* Lt;     /* (du, du) */
+    const float* F;      /* (T) the front: fbsmi_lg_model's F, sqQ and fbsmi_lg_pmcmc_tables' m_u, m_v, gain */
+    const float* sqQ;    /* (T) */
+    const double* m_u;   /* (du) */
+    const double* m_v;   /* (dv) */
+    const double* gain;  /* (du, dv) */
+} fbsmi_kf_model;
+typedef struct fbsmi_kf fbsmi_kf; /* opaque: the tables in the kernel's operand order, the vs and m_0 buffers */
+/* B = nsamples samples per call.  The tables are device arrays, read here, once (the handle keeps its own copies).
+ * FBSMI_ERR_ARG for a null model, T < 1 or a null table; FBSMI_ERR_UNSUPPORTED for du or dv outside [1, 128] or nsamples
+ * outside [1, 65535]; all of this is answered before any device call. */
+int fbsmi_kf_create(const fbsmi_kf_model* model, int32_t nsamples, fbsmi_kf** out);
+void fbsmi_kf_destroy(fbsmi_kf* h);
+/* keys (B, 2) and y0 (dv) are device inputs; samples (B, du), means (B, du) (nullable) and loglik (B) (nullable) device
+ * outputs.  FBSMI_ERR_UNSUPPORTED for a model without an exact forward transition (F and sqQ all-zero placeholders), as
+ * fbsmi_lg_fsamp_create answers. */
+int fbsmi_kf_sample(fbsmi_kf* h, const uint32_t* keys, const float* y0, float* samples, float* means, float* loglik,
+                    void* stream);
+/* The filter alone on the caller's observation paths vs (B, T+1, dv), read in place: m_0 from vs[b][0], the T steps,
+ * means (B, du) and loglik (B) (each nullable); nothing is drawn. */
+int fbsmi_kf_filter(fbsmi_kf* h, const float* vs, float* means, float* loglik, void* stream);
+/* State of the last call, copied to dst (nullable: only *count is set): which 0 vs (B, T+1, dv), the observation paths
+ * of the last fbsmi_kf_sample; 1 m_ (B, du), the initial means m_0 of the last call of either kind. */
+int fbsmi_kf_view(fbsmi_kf* h, int which, void* dst, int64_t* count, void* stream);
+
 /* ---- fused SMC step for score-network models (image experiments) --------------------------------
  * The three closures of experiments/imgs/inpainting.py:102-147 (and supr.py; sb_imgs/supr.py:80-127)
  * wrap ONE network evaluation on the joint image concat(u, v) per SMC step (csmc.py:142,145 evaluate it
