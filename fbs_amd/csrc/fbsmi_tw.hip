@@ -422,6 +422,8 @@ int fbsmi_tw_create(const fbsmi_tw_model* m, int32_t nparticles, int resampling,
         return fail(FBSMI_ERR_ARG, "tw_create: need a model, T >= 1, nruns >= 1 and resampling 0 (stratified) | 1 (systematic)");
     if (!m->R || !m->r || !m->C || !m->c || !m->sd || !m->lognorm || !m->m_ref || !m->Lt || !m->y)
         return fail(FBSMI_ERR_ARG, "tw_create: null table");
+    if (nruns > 65535)   // run b of the batch is blockIdx.y of every launch
+        return fail(FBSMI_ERR_UNSUPPORTED, "tw_create: the fused twisted SMC takes 1 <= nruns <= 65535 (one grid row per run)");
     if (m->d < 1 || m->d > 128 || nparticles < 1 || nparticles > 131072)
         return fail(FBSMI_ERR_UNSUPPORTED, "tw_create: the fused twisted SMC takes 1 <= d <= 128 and 1 <= nparticles <= 131072");
     fbsmi_tw* h = new (std::nothrow) fbsmi_tw();

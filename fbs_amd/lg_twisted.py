@@ -23,6 +23,7 @@ from .linear_gaussian import _Closure, _LGHandle
 from .sdes.linear import LinearSDE, discretise_linear_sde_np
 
 MAX_D, MAX_PARTICLES = 128, 131072   # the wide family's limits (fbsmi_tw_create)
+MAX_RUNS = 65535                     # nruns of a handle: a run is one grid row of every launch (fbsmi_tw_create)
 
 
 def lg_twisted_tables(mean, cov, sde: LinearSDE, ts, obs_var, y) -> dict:
@@ -183,6 +184,8 @@ class TwistedHandle(_LGHandle):
     def __init__(self, model: GaussianTwisted, nparticles, resampling, nruns=1, store_ancestors=False):
         if not model.fused_supported(nparticles):
             raise NotImplementedError(f"the fused twisted SMC takes 1 <= d <= {MAX_D} and 1 <= nparticles <= {MAX_PARTICLES}")
+        if not 1 <= int(nruns) <= MAX_RUNS:
+            raise NotImplementedError(f"the fused twisted SMC takes 1 <= nruns <= {MAX_RUNS}")
         self.model, self.n, self.C, self.store = model, int(nparticles), int(nruns), bool(store_ancestors)
         h = C.c_void_p()
         with torch.cuda.device(model.device):

@@ -444,7 +444,8 @@ typedef struct fbsmi_tw_model {
 } fbsmi_tw_model;
 typedef struct fbsmi_tw fbsmi_tw; /* opaque: device buffers for nruns runs, a stream and the captured graphs */
 /* resampling 0 stratified | 1 systematic.  The tables stay the caller's and must outlive the handle.  d outside
- * [1, 128] or nparticles outside [1, 131072]: FBSMI_ERR_UNSUPPORTED.  store_ancestors: keep every step's ancestors. */
+ * [1, 128], nparticles outside [1, 131072] or nruns > 65535 (a run is one grid row of every launch):
+ * FBSMI_ERR_UNSUPPORTED.  store_ancestors: keep every step's ancestors. */
 int fbsmi_tw_create(const fbsmi_tw_model* model, int32_t nparticles, int resampling, int32_t nruns, int store_ancestors,
                     fbsmi_tw** out);
 void fbsmi_tw_destroy(fbsmi_tw* h);

@@ -56,3 +56,18 @@ class Restate:
         key_init, key_sde = self.O.split(np.asarray(key, np.uint32), 2)
         u0 = self.u0(key_init)
         return u0, self.integrate(key_sde, u0, return_path=True)
+
+    def sample_batch(self, keys):
+        """sample() for a batch of keys at once: the same chains and the same roundings in the same order (drift is per
+        row already), the draws per key; what a batch of thousands can afford.  -> (u0 (B, d), path (T+1, B, d))"""
+        O, h, d, T = self.O, self.h, self.d, self.T
+        ks = [O.split(np.asarray(k, np.uint32), 2) for k in np.asarray(keys, np.uint32).reshape(-1, 2)]
+        x = drift(h["S_ref"], h["m_ref"], np.stack([O.normal(k2[0], (d,)) for k2 in ks]))
+        xi = np.stack([np.stack([O.normal(kk, (1, d))[0] for kk in O.split(k2[1], T)]) for k2 in ks], axis=1)   # (T, B, d)
+        path = [x]
+        for k in range(T):
+            f = drift(h["A"][k], h["cvec"][k], x)
+            x = ((x + (f * h["ddt"][k]).astype(f32)).astype(f32) + (h["s"][k] * xi[k]).astype(f32)).astype(f32)
+            path.append(x)
+        return path[0], np.stack(path)
+

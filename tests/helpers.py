@@ -35,6 +35,21 @@ def toy_gp(d, dv=None, seed=5):
     return dict(m0=np.zeros(d + dv), cov0=joint, y0=rng.normal(size=dv).astype(np.float32), du=d)
 
 
+# both sides of every 16-row tile of the matrix-core engines, and of their 32- and 64-column edges
+WIDTHS = [15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 79, 80, 81, 95, 96, 97, 111, 112, 113, 127, 128]
+
+
+def toy_rand(du, dv, seed=7):
+    """A dense joint Gaussian of du + dv coordinates with a non-zero mean; dv may exceed du (toy_gp observes coordinates
+    of u, so it cannot)."""
+    D = du + dv
+    rng = np.random.default_rng(seed)
+    A = rng.normal(size=(D, D))
+    cov0 = A @ A.T / D + 0.5 * np.eye(D)
+    m0 = 0.3 * rng.normal(size=D)
+    return dict(m0=m0, cov0=cov0, y0=rng.normal(size=dv).astype(np.float32), du=du)
+
+
 def oracle_model_from(O, bridge):
     """An oracle LGModel fed with the PRODUCT's float32 tables (parity then isolates the kernels)."""
     h = bridge.host

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import WIDTHS
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("fbsmi_csgm_create", "fbsmi_csgm_destroy", "fbsmi_csgm_run", "fbsmi_csgm_view")
 OBS_VAR = 0.7
@@ -130,6 +132,59 @@ def test_restatement_against_float64(oracle):
         worst = max(worst, float(np.abs(path.astype(np.float64) - want).max() / np.abs(want).max()))
     print(f"restatement against float64: {worst:.3g}")
     assert worst <= 1e-5
+
+
+@pytest.mark.parametrize("sde_name", ["const", "lin"])
+@pytest.mark.parametrize("d", WIDTHS)
+def test_restatement_against_float64_across_the_width_ladder(d, sde_name, oracle):
+    """The same comparison at every width of helpers.WIDTHS (both sides of every 16-row tile), T = 6: bit equality of the
+    kernel with the restatement says nothing about accuracy at a width where the restatement was never held to float64.
+    Largest figure measured over the ladder: 4.9e-7 (d = 128, lin)."""
+    from csgm_restate import Restate
+    m = _model(d=d, T=6, sde_name=sde_name)
+    rs = Restate(oracle, m)
+    worst = 0.0
+    for seed in (5, 6, 7):
+        u0, path = rs.sample(oracle.PRNGKey(seed))
+        want = float64_recursion(oracle, m, oracle.PRNGKey(seed))
+        assert path.shape == (7, d) and path.dtype == np.float32 and np.array_equal(path[0], u0)
+        worst = max(worst, float(np.abs(path.astype(np.float64) - want).max() / np.abs(want).max()))
+    print(f"d = {d}, {sde_name}: restatement against float64 {worst:.3g}")
+    assert worst <= 1e-5
+
+
+@pytest.mark.parametrize("d,T,sde_name", [(3, 2, "const"), (17, 3, "lin"), (80, 4, "const")])
+def test_batched_restatement_is_the_per_key_one(d, T, sde_name, oracle):
+    """Restate.sample_batch (what the GPU tests of wide or large batches compare with) against Restate.sample, bit for bit."""
+    from csgm_restate import Restate
+    rs = Restate(oracle, _model(d=d, T=T, sde_name=sde_name))
+    keys = np.stack([oracle.PRNGKey(11 + b) for b in range(5)])
+    u0, path = rs.sample_batch(keys)
+    assert u0.shape == (5, d) and path.shape == (T + 1, 5, d) and u0.dtype == path.dtype == np.float32
+    for b in range(5):
+        u0_1, path_1 = rs.sample(keys[b])
+        assert np.array_equal(u0[b].view(np.uint32), u0_1.view(np.uint32))
+        assert np.array_equal(path[:, b].view(np.uint32), path_1.view(np.uint32))
+
+
+def test_restatement_feels_one_ulp_past_row_and_column_64(oracle):
+    """d = 80: one ulp on A[1][79][79] (the last row and column, both past 64) changes the restated path, so a comparison
+    with the restatement reaches the rows and columns the wide GPU cases exist for.  A drift that moves by one ulp is
+    scaled by ddt = 1/3 before it meets x, so most single entries' ulps are rounded away there (of the diagonal entries
+    tried, 79 at step 1 and 70 at step 2 survive); the entry is one that survives, and the change is where it must be."""
+    from csgm_restate import Restate
+    m = _model(d=80, T=3)
+    u0, path = Restate(oracle, m).sample(oracle.PRNGKey(5))
+    A = m.host["A"].copy()
+    A[1, 79, 79] = np.nextafter(A[1, 79, 79], np.float32(np.inf))
+    assert A[1, 79, 79] != m.host["A"][1, 79, 79]
+    bumped = Restate(oracle, m)
+    bumped.h = dict(m.host, A=A)
+    u0_b, path_b = bumped.sample(oracle.PRNGKey(5))
+    assert np.array_equal(u0_b.view(np.uint32), u0.view(np.uint32))                     # u0 does not read A
+    changed = np.argwhere(path_b.view(np.uint32) != path.view(np.uint32))
+    print(f"one ulp on A[1][79][79]: {len(changed)} of {path.size} path entries change, first {changed[:1].tolist()}")
+    assert len(changed) >= 1 and changed[0].tolist() == [2, 79]                         # first in row 79, behind step 1
 
 
 def test_restatement_stays_finite_at_the_gpu_shapes(oracle):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from csgm_restate import Restate
+from helpers import WIDTHS
 from test_csgm_tables import float64_recursion
 from test_gpu_tw_fused import _eq, _np, _sde
 
@@ -51,11 +52,17 @@ SHAPES = [(1, 8, 1, "const"), (2, 5, 3, "const"), (3, 8, 33, "lin"), (5, 6, 70, 
           (24, 6, 65, "lin"), (33, 4, 31, "const"), (100, 3, 64, "const"), (128, 3, 33, "lin"), (100, 37, 8, "const")]
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=["d{}-T{}-B{}-{}".format(*s) for s in SHAPES])
-def test_sample_mode(shape, oracle, dev):
+# Every width of the ladder: both sides of every 16-row tile, so every k_csgm<NQ>, NQ = 1..8, is launched below, on and
+# above its last full tile (no zero padding at the multiples of 16); NQ = 5 and 6 are the widths at which only some waves
+# own a second row tile.  T alternates 3 and 4 (both parities of the LDS ping-pong and of k + 1 == T), the SDE changes
+# every second width (so both run at both T), B cycles through one sample, either side of a workgroup's 16, and 33.
+LADDER = [(d, (3, 4)[i % 2], (1, 15, 16, 17, 33)[i % 5], ("const", "lin")[(i // 2) % 2]) for i, d in enumerate(WIDTHS)]
+
+
+def _sample_mode(shape, want=_want_batch):
     d, T, B, sde_name = shape
     m = _model(d, T, sde_name)
-    u0_w, path_w = _want_batch(d, T, sde_name, B)
+    u0_w, path_w = want(d, T, sde_name, B)
     assert np.isfinite(u0_w).all() and np.isfinite(path_w).all()
     h = m.handle(B, store_path=True)
     out = h.sample(_keys(B))
@@ -66,10 +73,51 @@ def test_sample_mode(shape, oracle, dev):
     _eq(_np(out), path_w[-1], "samples")
 
 
-@pytest.mark.parametrize("store_path", [True, False])
-def test_integrate_mode(store_path, oracle, dev):
-    d, T, B = 24, 6, 19
+@pytest.mark.parametrize("shape", SHAPES, ids=["d{}-T{}-B{}-{}".format(*s) for s in SHAPES])
+def test_sample_mode(shape, oracle, dev):
+    _sample_mode(shape)
+
+
+@pytest.mark.parametrize("shape", LADDER, ids=["d{}-T{}-B{}-{}".format(*s) for s in LADDER])
+def test_sample_mode_across_the_width_ladder(shape, oracle, dev):
+    d, T, B, sde_name = shape
+    u0_1, path_1 = _want(d, T, sde_name, 11)                       # the first key through the per-key restatement
+    u0_w, path_w = _want_batched(d, T, sde_name, B)
+    _eq(u0_w[0], u0_1, "batched restatement: u0")
+    _eq(path_w[:, 0], path_1, "batched restatement: path")
+    _sample_mode(shape, _want_batched)
+
+
+@functools.lru_cache(maxsize=None)
+def _want_batched(d, T, sde_name, B, seed0=11):
+    """_want_batch through the restatement's batched form (tests/test_csgm_tables.py holds it to the per-key one bit for
+    bit): the wide cases in a fraction of a second.  -> (u0 (B, d), path (T+1, B, d))"""
+    import oracle as O
+    return Restate(O, _model(d, T, sde_name)).sample_batch(_keys(B, seed0))
+
+
+def test_large_batch(oracle, dev):
+    """B = 4113: 257 workgroups and one sample over, more workgroups than the device has compute units.  The restatement
+    is batched over the samples (Restate.sample_batch), and held to the per-key one on the first 40 keys."""
+    d, T, B = 3, 2, 4113
     m = _model(d, T, "const")
+    keys = _keys(B)
+    u0_w, path_w = _want_batched(d, T, "const", B)
+    u0_1, path_1 = _want_batch(d, T, "const", 40)
+    _eq(u0_w[:40], u0_1, "batched restatement: u0")
+    _eq(path_w[:, :40], path_1, "batched restatement: path")
+    assert np.isfinite(path_w).all()
+    h = m.handle(B, store_path=True)
+    out = h.sample(keys)
+    v = h.views()
+    _eq(_np(v["u0"]), u0_w, "u0")
+    _eq(_np(v["path"]), path_w, "path")
+    _eq(_np(out), path_w[-1], "samples")
+
+
+def _integrate_mode(d, T, sde_name, store_path, oracle, dev):
+    B = 19
+    m = _model(d, T, sde_name)
     rs = Restate(oracle, m)
     u0 = np.random.default_rng(3).normal(size=(B, d)).astype(f32)
     keys = _keys(B, 40)
@@ -84,6 +132,20 @@ def test_integrate_mode(store_path, oracle, dev):
         _eq(_np(v["path"]), want, "path")
     else:
         assert "path" not in v
+
+
+@pytest.mark.parametrize("store_path", [True, False])
+def test_integrate_mode(store_path, oracle, dev):
+    _integrate_mode(24, 6, "const", store_path, oracle, dev)
+
+
+# integrate mode (u0 from the caller: the clamped load of rows >= d, the table fetch from table 1) at an exact tile count
+# (16, 48, 96), just past one (65, 113) and at NQ = 5, where wave 0 alone owns a second row tile
+@pytest.mark.parametrize("store_path", [True, False])
+@pytest.mark.parametrize("d,T,sde_name", [(16, 3, "const"), (48, 4, "lin"), (65, 3, "lin"), (80, 4, "const"), (96, 3, "const"),
+                                          (113, 4, "lin")])
+def test_integrate_mode_across_widths(d, T, sde_name, store_path, oracle, dev):
+    _integrate_mode(d, T, sde_name, store_path, oracle, dev)
 
 
 def test_without_store_path(oracle, dev):

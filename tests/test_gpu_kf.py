@@ -11,6 +11,7 @@ import torch
 
 from helpers import toy_gp, toy_2d, toy_4d, toy_31, oracle_model_from
 import kf_restate as R
+from test_kf_tables import LADDER
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +34,7 @@ def _eq(a, b, what):
 
 MODELS = {"2d": (toy_2d, 30), "4d": (toy_4d, 30), "31": (toy_31, 30), "gp17": (lambda: toy_gp(17), 10),
           "gp20v7": (lambda: toy_gp(20, dv=7), 10), "gp128": (lambda: toy_gp(128), 4), "gp100": (lambda: toy_gp(100), 200)}
+MODELS.update({name: (make, 6) for name, make in LADDER.items()})      # the width ladder of tests/test_kf_tables.py
 _BRIDGES, _WANT = {}, {}
 NKEYS = 33
 
@@ -93,6 +95,10 @@ def _sample_guarded(h, br, keys, y0, dev):
 
 # ---- 1. bit equality ----------------------------------------------------------------------------------------------------
 PARITY = [(m, B) for m in ("2d", "4d", "31", "gp17", "gp20v7", "gp128") for B in (1, 15, 16, 17, 33)] + [("gp100", 17)]
+# NQu = NQv = 1, 3, 4 (63, 64), 5 (65, 80), 6, 7 and the pairs (8, 1), (5, 3), (1, 3), (3, 5), (2, 6), (1, 8): every count
+# 3..6 on either side, both "second row tile on some waves only" flags mixed, dv > du, the fallback loads (row tile 0, the
+# last column group again) with NQu != NQv; one workgroup with one live sample, and two
+PARITY += [(m, B) for m in LADDER for B in (1, 17)]
 
 
 @pytest.mark.parametrize("name,B", PARITY, ids=[f"{m}-B{B}" for m, B in PARITY])
@@ -108,7 +114,7 @@ def test_bit_equality_with_the_restatement(name, B, oracle, dev):
 
 
 # ---- 2. filter(vs) against sample, the Python layer, ragged batches -----------------------------------------------------------
-@pytest.mark.parametrize("name", ["4d", "gp20v7"])
+@pytest.mark.parametrize("name", ["4d", "gp20v7", "gp80v33", "rand33v80"])
 def test_filter_on_the_sampled_paths_and_ragged_batches(name, oracle, dev):
     from fbs_amd import _lib, ops
     toy, ts, br = _setup(name, dev)

@@ -36,39 +36,37 @@ def _sde(name):
 
 
 @functools.lru_cache(maxsize=None)
-def _model(d, T, sde_name):
+def _model(d, T, sde_name, obs_var=OBS_VAR, device="cuda:0"):
     """The Gaussian-process toy of gp_twisted.py:30-58 at width d with a non-zero prior mean, on T steps of [0, 1]."""
     import fbs_amd
     zs = np.linspace(0., 5., d)
     cov = np.exp(-np.abs(zs[None, :] - zs[:, None]))
     rng = np.random.default_rng(100 + d)
     mean, y = 0.3 * rng.normal(size=d), rng.normal(size=d).astype(f32)
-    return fbs_amd.GaussianTwisted(mean, cov, _sde(sde_name), np.linspace(0., 1., T + 1), OBS_VAR, y, device="cuda:0")
+    return fbs_amd.GaussianTwisted(mean, cov, _sde(sde_name), np.linspace(0., 1., T + 1), obs_var, y, device=device)
 
 
 @functools.lru_cache(maxsize=None)
-def _want(d, T, N, sde_name, resampling, seed):
+def _want(d, T, N, sde_name, resampling, seed, obs_var=OBS_VAR, device="cuda:0"):
     """The restated run under PRNGKey(seed): computed once, shared by the tests that need it."""
     import oracle as O
-    return Restate(O, _model(d, T, sde_name)).run(O.PRNGKey(seed), N, resampling)
+    return Restate(O, _model(d, T, sde_name, obs_var, device)).run(O.PRNGKey(seed), N, resampling)
 
 
 @functools.lru_cache(maxsize=None)
-def _want_sample(d, T, N, sde_name, seed):
+def _want_sample(d, T, N, sde_name, seed, obs_var=OBS_VAR):
     import oracle as O
-    return Restate(O, _model(d, T, sde_name)).sample(O.PRNGKey(seed), N)
+    return Restate(O, _model(d, T, sde_name, obs_var)).sample(O.PRNGKey(seed), N)
 
 
 SHAPES = [(1, 8, 1, "const"), (2, 5, 2, "const"), (3, 8, 16, "const"), (3, 8, 100, "lin"), (10, 6, 257, "const"),
           (10, 6, 1000, "const"), (24, 6, 48, "const"), (24, 4, 300, "lin"), (100, 3, 64, "const"), (128, 3, 33, "lin")]
 
 
-@pytest.mark.parametrize("resampling", ["stratified", "systematic"])
-@pytest.mark.parametrize("shape", SHAPES, ids=["d{}-T{}-N{}-{}".format(*s) for s in SHAPES])
-def test_single_run(shape, resampling, oracle, dev):
+def _single_run(shape, resampling, oracle, obs_var=OBS_VAR):
     d, T, N, sde_name = shape
-    m = _model(d, T, sde_name)
-    xs_w, lws_w, inds_w = _want(d, T, N, sde_name, resampling, 11)
+    m = _model(d, T, sde_name, obs_var)
+    xs_w, lws_w, inds_w = _want(d, T, N, sde_name, resampling, 11, obs_var)
     assert np.isfinite(xs_w).all() and np.isfinite(lws_w).all()
     h = m.handle(N, resampling, nruns=1, store_ancestors=True)
     xs, lws = h.run(oracle.PRNGKey(11))
@@ -76,6 +74,70 @@ def test_single_run(shape, resampling, oracle, dev):
     _eq(_np(h.views()["ancestors"])[0], inds_w, "ancestors")
     _eq(_np(xs)[0], xs_w, "particles")
     _eq(_np(lws)[0], lws_w, "log-weights")
+
+
+@pytest.mark.parametrize("resampling", ["stratified", "systematic"])
+@pytest.mark.parametrize("shape", SHAPES, ids=["d{}-T{}-N{}-{}".format(*s) for s in SHAPES])
+def test_single_run(shape, resampling, oracle, dev):
+    _single_run(shape, resampling, oracle)
+
+
+# The widths of k_tw_gemm: nq = Kp / 16 = 1..7 column groups through the two-at-a-time operand pipeline (odd and even
+# counts), exact row tiles (2 d = 32, 64, ...), the first width whose columns need the second staging half (65), against
+# ensemble sizes on either side of the 32-slot tile (31 / 32 / 33) and of the one-tile boundary (255 / 256 / 257: three
+# launches a step up to 256, five above), and nb = 2 and 3 tiles.  obs_var = 5: with 0.7 these wide models collapse (d = 64,
+# N = 255 keeps 3 distinct ancestors in step 0) and the gather would read a handful of rows; tests/test_tw_tables.py
+# asserts that every step of every case here keeps at least N / 4 distinct ancestors.
+WIDE_OBS_VAR = 5.0
+WIDE = [(16, 4, 32, "const"), (32, 3, 31, "lin"), (32, 3, 33, "lin"), (48, 3, 256, "const"), (64, 3, 255, "const"),
+        (65, 4, 64, "lin"), (80, 3, 257, "const"), (96, 4, 33, "const"), (112, 3, 100, "lin"), (17, 3, 512, "const"),
+        (33, 3, 513, "const")]
+# The ensemble sizes of k_tw_norm / k_tw_cdf / lse_from_partials: nb = 5, 17 (the top tree past thread 0), 256 (the last
+# size with one tile pair per thread), 274 (four per thread), 512 (capacity: two waves of the top tree); (d, T, N), const
+# SDE, obs_var = 0.7 but for the one model of width 16, which at 0.7 keeps 150 of 1025 ancestors in step 0.
+LARGE = [(16, 2, 1025), (3, 3, 4097), (2, 3, 65536), (3, 2, 70001), (1, 2, 131072)]
+
+
+def ladder_obs_var(d):
+    return WIDE_OBS_VAR if d >= 16 else OBS_VAR
+
+
+@pytest.mark.parametrize("resampling", ["stratified", "systematic"])
+@pytest.mark.parametrize("shape", WIDE, ids=["d{}-T{}-N{}-{}".format(*s) for s in WIDE])
+def test_single_run_across_the_widths(shape, resampling, oracle, dev):
+    _single_run(shape, resampling, oracle, WIDE_OBS_VAR)
+
+
+@pytest.mark.parametrize("shape", [(48, 3, 256, "const"), (80, 3, 257, "const")], ids=["d48-N256", "d80-N257"])
+def test_sample_across_the_one_tile_boundary(shape, oracle, dev):
+    """sample() (the select graph: the last normalisation, its cdf above one tile, the choice) at wide models."""
+    d, T, N, sde_name = shape
+    h = _model(d, T, sde_name, WIDE_OBS_VAR).handle(N, "stratified", nruns=1)
+    for seed in (11, 12):
+        smp = h.sample(oracle.PRNGKey(seed)[None])
+        assert smp.shape == (1, d)
+        _eq(_np(smp)[0], _want_sample(d, T, N, sde_name, seed, WIDE_OBS_VAR), f"seed {seed} sample")
+
+
+@pytest.mark.parametrize("resampling", ["stratified", "systematic"])
+@pytest.mark.parametrize("shape", LARGE, ids=["d{}-T{}-N{}".format(*s) for s in LARGE])
+def test_single_run_at_large_ensembles(shape, resampling, oracle, dev):
+    _single_run(shape + ("const",), resampling, oracle, ladder_obs_var(shape[0]))
+
+
+def test_batched_runs_at_a_large_ensemble(oracle, dev):
+    """nruns = 3 at N = 4097 (nb = 17): the per-run offsets of the tile partials with more tiles than one thread holds."""
+    d, T, N = 3, 3, 4097
+    seeds = [11, 12, 13]
+    h = _model(d, T, "const").handle(N, "stratified", nruns=3, store_ancestors=True)
+    xs, lws = h.run(np.stack([oracle.PRNGKey(s) for s in seeds]))
+    anc = _np(h.views()["ancestors"])
+    assert xs.shape == (3, N, d) and lws.shape == (3, N) and anc.shape == (3, T, N)
+    for b, s in enumerate(seeds):
+        xs_w, lws_w, inds_w = _want(d, T, N, "const", "stratified", s)
+        _eq(anc[b], inds_w, f"run {b} ancestors")
+        _eq(_np(xs)[b], xs_w, f"run {b} particles")
+        _eq(_np(lws)[b], lws_w, f"run {b} log-weights")
 
 
 @pytest.mark.parametrize("shape", [(10, 6, 257, "const"), (24, 6, 48, "const")], ids=["d10-N257", "d24-N48"])

@@ -7,13 +7,28 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import toy_2d, toy_31, toy_4d, toy_gp
+from helpers import toy_2d, toy_31, toy_4d, toy_gp, toy_rand
 import fsamp_restate as FR
 import kf_restate as R
 
 f32 = np.float32
 OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -3
 TOYS = {"2d": toy_2d, "4d": toy_4d, "31": toy_31}
+# the width ladder of k_kf, on ts = linspace(0, 2, 7): square models on either side of the 16-row tiles and of the
+# 64-column edge, and rectangular ones whose (NQu, NQv) differ, dv > du among them
+SQUARE = {f"gp{d}": (lambda d=d: toy_gp(d)) for d in (16, 48, 63, 64, 65, 80, 96, 112)}
+RECT = {"gp128v1": lambda: toy_gp(128, dv=1), "gp80v33": lambda: toy_gp(80, dv=33), "rand5v40": lambda: toy_rand(5, 40),
+        "rand33v80": lambda: toy_rand(33, 80), "rand17v96": lambda: toy_rand(17, 96), "rand5v128": lambda: toy_rand(5, 128)}
+LADDER = {**SQUARE, **RECT}
+LADDER_TILES = {"gp128v1": (8, 1), "gp80v33": (5, 3), "rand5v40": (1, 3), "rand33v80": (3, 5), "rand17v96": (2, 6),
+                "rand5v128": (1, 8)}
+LADDER_TS = np.linspace(0, 2, 7)
+DENSE = {**TOYS, **RECT, "gp48": SQUARE["gp48"]}
+
+
+def ladder_keys(O, n=17):
+    """The keys of the ladder's samples (those of tests/test_gpu_kf.py)."""
+    return O.split(O.PRNGKey(51), 33)[:n]
 
 
 def _tables(toy, ts):
@@ -67,10 +82,10 @@ def _dense(tab, m0, Sig0, vs):
     return post_mean[-du:], post_cov[-du:, -du:], loglik
 
 
-@pytest.mark.parametrize("name", sorted(TOYS))
+@pytest.mark.parametrize("name", sorted(TOYS) + sorted(set(DENSE) - set(TOYS)))
 def test_tables_against_dense_conditioning(name):
     from fbs_amd.lg_kalman import kalman_filter_np
-    toy, ts = TOYS[name](), np.linspace(0, 2, 7)
+    toy, ts = DENSE[name](), np.linspace(0, 2, 7)
     tab, pm, kt = _tables(toy, ts)
     assert kt["T"] == 6 and kt["H"].shape == (6, kt["dv"], kt["du"] + kt["dv"]) and kt["AK"].shape == (6, kt["du"], kt["dv"])
     assert np.array_equal(np.linalg.cholesky(kt["cov_0"]).astype(f32), pm["chol"])     # the matrix chol is rounded from
@@ -106,6 +121,45 @@ def test_restatement_against_float64_at_the_drivers_shape(oracle):
         zz = oracle.normal(oracle.split(keys[b], 3)[2], (100,)).astype(np.float64)
         x64 = m64 + zz @ kt["Lt"]
         assert np.abs(w["samples"][b] - x64).max() <= 1e-5 * np.abs(x64).max()
+
+
+@pytest.mark.parametrize("name", list(LADDER))
+def test_restatement_against_float64_across_the_width_ladder(name, oracle):
+    """Means to 1e-5 of max |m|, loglik to 1e-5 relative, 17 keys, T = 6, at every model of the ladder.  (No du = 1 here:
+    max |m| is then one coordinate, which can sit near zero.)  Largest figures measured: means 1.4e-6 (rand5v128), loglik 1.6e-7 (rand33v80)."""
+    from fbs_amd.lg_kalman import kalman_filter_np
+    toy = LADDER[name]()
+    tab, pm, kt = _tables(toy, LADDER_TS)
+    du, dv = kt["du"], kt["dv"]
+    if name in LADDER_TILES:
+        assert ((du + 15) // 16, (dv + 15) // 16) == LADDER_TILES[name]
+    w = R.want(oracle, _oracle_model(oracle, tab), _host32(kt), kt, ladder_keys(oracle), toy["y0"])
+    assert w["vs"].shape == (17, 7, dv) and w["samples"].shape == w["means"].shape == (17, du)
+    worst_m = worst_l = 0.0
+    for b in range(17):
+        m64, ll64 = kalman_filter_np(kt, w["vs"][b].astype(np.float64))
+        worst_m = max(worst_m, float(np.abs(w["means"][b] - m64).max() / np.abs(m64).max()))
+        worst_l = max(worst_l, abs(float(w["loglik"][b]) - ll64) / abs(ll64))
+    print(f"{name} (du {du}, dv {dv}): means {worst_m:.2e} of max |m|, loglik {worst_l:.2e} relative")
+    assert np.isfinite(w["samples"]).all() and worst_m <= 1e-5 and worst_l <= 1e-5
+
+
+def test_restatement_feels_one_ulp_in_the_last_row_and_column_of_the_u_block(oracle):
+    """toy_gp(80, dv=33): one ulp on Pm[5][79][79] (row tile 4 -- the second tile of wave 0 alone -- and column group 4, in
+    the last step, whose row 79 feeds mean 79 and nothing else) changes the restated means in coordinate 79 only, so a
+    comparison with the restatement reaches that row and column.  Measured: 4 of the 17 samples change."""
+    toy = LADDER["gp80v33"]()
+    tab, pm, kt = _tables(toy, LADDER_TS)
+    om, host, keys = _oracle_model(oracle, tab), _host32(kt), ladder_keys(oracle)
+    w = R.want(oracle, om, host, kt, keys, toy["y0"])
+    Pm = host["Pm"].copy()
+    Pm[5, 79, 79] = np.nextafter(Pm[5, 79, 79], f32(np.inf))
+    assert Pm[5, 79, 79] != host["Pm"][5, 79, 79]
+    wb = R.want(oracle, om, dict(host, Pm=Pm), kt, keys, toy["y0"])
+    assert np.array_equal(wb["vs"].view(np.uint32), w["vs"].view(np.uint32))            # the path does not read Pm
+    changed = np.argwhere(wb["means"].view(np.uint32) != w["means"].view(np.uint32))
+    print(f"one ulp on Pm[5][79][79]: means changed at (sample, coordinate) {changed.tolist()}")
+    assert len(changed) >= 1 and np.all(changed[:, 1] == 79)
 
 
 def test_restated_front_is_the_filter_samplers(oracle):

@@ -155,3 +155,72 @@ def test_restatement_stays_finite_at_the_gpu_shapes(oracle):
         m = _model(d=d, T=T, sde_name=sde_name)
         xs, lws, inds = Restate(oracle, m).run(oracle.PRNGKey(5), N)
         assert xs.shape == (N, d) and inds.shape == (T, N) and np.isfinite(xs).all() and np.isfinite(lws).all()
+
+
+def _gpu_cases():
+    from test_gpu_tw_fused import LARGE, WIDE, ladder_obs_var
+    return [(s, ladder_obs_var(s[0])) for s in WIDE] + [(s + ("const",), ladder_obs_var(s[0])) for s in LARGE]
+
+
+@pytest.mark.parametrize("resampling", ["stratified", "systematic"])
+@pytest.mark.parametrize("case", _gpu_cases(), ids=lambda c: "d{}-T{}-N{}-{}".format(*c[0]))
+def test_restatement_keeps_a_diverse_ensemble_at_the_gpu_ladder(case, resampling, oracle):
+    """The restated runs the GPU ladder is compared with (tests/test_gpu_tw_fused.py: obs_var = 5 from width 16 on, 0.7 below, the
+    same models, key and resamplers) are finite, and every step keeps at least N / 4 distinct ancestors: a collapsed
+    ensemble would gather a handful of rows over and over and test little of the search, the gather or the product."""
+    from test_gpu_tw_fused import _want
+    (d, T, N, sde_name), obs_var = case
+    xs, lws, inds = _want(d, T, N, sde_name, resampling, 11, obs_var, "cpu")
+    assert xs.shape == (N, d) and lws.shape == (N,) and inds.shape == (T, N)
+    assert np.isfinite(xs).all() and np.isfinite(lws).all() and inds.min() >= 0 and inds.max() < N
+    distinct = [int(np.unique(row).size) for row in inds]
+    print(f"d = {d}, T = {T}, N = {N}, {sde_name}, {resampling}, obs_var = {obs_var}: distinct ancestors per step {distinct}")
+    assert min(distinct) >= N / 4
+
+
+# ---- argument checks of fbsmi_tw_create: answered before any device call ---------------------------------------------------------
+def test_tw_create_validation():
+    import ctypes as C
+    from fbs_amd import _lib
+    from fbs_amd.lg_twisted import MAX_RUNS, TwistedHandle
+    OK, ERR_ARG, ERR_UNSUPPORTED = 0, -1, -3
+    L = _lib.lib()
+    buf = C.create_string_buffer(64)                       # a non-NULL pointer; never dereferenced
+    p = C.addressof(buf)
+
+    def create(d=4, T=3, nparticles=8, resampling=0, nruns=1, null=None, model=True):
+        tabs = [None if n == null else p for n in ("R", "r", "C", "c", "sd", "lognorm", "m_ref", "Lt", "y")]
+        st = _lib.TWModelStruct(d, T, 0.25, *tabs, 0.7, 1.0)
+        h = C.c_void_p()
+        rc = L.fbsmi_tw_create(C.byref(st) if model else None, nparticles, resampling, nruns, 0, C.byref(h))
+        assert not h.value
+        return rc, L.fbsmi_last_error()
+
+    for kw in (dict(model=False), dict(T=0), dict(nruns=0), dict(nruns=-1), dict(resampling=2), dict(null="R"), dict(null="y")):
+        rc, msg = create(**kw)
+        assert rc == ERR_ARG and b"tw_create" in msg, (kw, rc, msg)
+    for kw in (dict(d=0), dict(d=129), dict(nparticles=0), dict(nparticles=131073)):
+        rc, msg = create(**kw)
+        assert rc == ERR_UNSUPPORTED and b"tw_create" in msg and b"128" in msg and b"131072" in msg, (kw, rc, msg)
+    rc, msg = create(nruns=65536)
+    assert rc == ERR_UNSUPPORTED and b"tw_create" in msg and b"nruns" in msg and b"65535" in msg, (rc, msg)
+    rc, msg = create(nruns=1 << 30)
+    assert rc == ERR_UNSUPPORTED and b"65535" in msg, (rc, msg)
+    # nruns = 65535 passes the bound: with a width that is refused next, the refusal is the width's (nothing is allocated)
+    rc, msg = create(nruns=65535, d=129)
+    assert rc == ERR_UNSUPPORTED and b"65535" not in msg and b"128" in msg, (rc, msg)
+    rc, msg = create(nruns=65536, d=129)
+    assert rc == ERR_UNSUPPORTED and b"65535" in msg, (rc, msg)
+    with pytest.raises(NotImplementedError, match="65535"):        # what fbs_amd._lib.call makes of it
+        tabs = [p] * 9
+        _lib.call("fbsmi_tw_create", C.byref(_lib.TWModelStruct(4, 3, 0.25, *tabs, 0.7, 1.0)), 8, 0, 65536, 0, C.byref(C.c_void_p()))
+    # the Python layer refuses it before the library is asked
+    assert MAX_RUNS == 65535
+    m = _model()
+    for nruns in (65536, 0):
+        with pytest.raises(NotImplementedError, match="65535"):
+            m.handle(8, "stratified", nruns=nruns)
+        with pytest.raises(NotImplementedError, match="65535"):
+            TwistedHandle(m, 8, "stratified", nruns=nruns)
+    assert not m._handles or all(k[2] not in (0, 65536) for k in m._handles)
+
