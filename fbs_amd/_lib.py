@@ -176,6 +176,13 @@ class EMMaskStruct(C.Structure):
                 ("role", C.c_void_p)]
 
 
+class EMPlanStruct(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("kernel", "pair", "vec", "ku", "nU", "nV", "vfirst", "nseg", "lnet_bytes",
+                                         "lds_bytes", "grid")]
+
+
+EM_KERNELS = ("none", "finish", "rows", "translp", "concat")    # FBSMI_EM_KERNEL_*
+
 # name -> (restype, argtypes); every int-returning entry is status-checked by call()
 _vp, _i32, _i64, _u32, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
 SIGNATURES = {
@@ -257,6 +264,11 @@ SIGNATURES = {
                                   _u32, _u32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "fbsmi_em_transition_logpdf": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, C.c_int, C.c_int, _f, _f, _f, _f, _vp,
                                              _i64, _vp, _vp]),
+    "fbsmi_em_concat_plan": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, _i64, C.c_int, _vp, C.POINTER(EMPlanStruct)]),
+    "fbsmi_em_finish_plan": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _i64, _i64, _i64,
+                                       _i64, _vp, _vp, _vp, C.POINTER(EMPlanStruct)]),
+    "fbsmi_em_transition_logpdf_plan": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, C.c_int, C.c_int, _vp, _i64, _vp,
+                                                  C.POINTER(EMPlanStruct)]),
     # include/fbsmi_nn.h
     "fbsmi_nn_linear_attention": (C.c_int, [_vp, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp]),
     "fbsmi_nn_qkv_linear_attention": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),

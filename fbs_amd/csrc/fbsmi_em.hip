@@ -427,9 +427,8 @@ __global__ void __launch_bounds__(kBlock, FBSMI_EM_WAVES) k_em_finish(const EmAr
 // output goes to LDS by LDS-DMA (global_load_lds_dwordx4: full-width coalesced, no registers, all of it in flight at
 // once) while the workgroup computes its share of the row's normals; after one barrier both parts of the row are served
 // from LDS through the offset tables -- proposal (4 elements per thread and group of 1024), then the log-density
-// segments (pipelined as in em_row_logpdf, the table / target / base from L2).  PAIR2: the launch covers the whole draw
-// with an even number of rows; the workgroup then takes rows r and r + n/2 one after the other and keeps the second
-// words of its Threefry calls in registers for the second row (the pairing of jax's random_bits).
+// segments (pipelined as in em_row_logpdf, the table / target / base from L2).  Row slices only: a launch that covers
+// the whole draw pairs the Threefry words in k_em_finish.
 // Requirements (else k_em_finish): du % 4 == 0, du <= 4096, row bytes a multiple of 16 that fit the LDS budget.
 // ------------------------------------------------------------------------------------------------
 template <int NETDT>
@@ -582,20 +581,17 @@ __device__ __forceinline__ float em_row_logpdf_lds(const EmArgs& a, const void* 
     return root;
 }
 
-template <int KU, bool PAIR2, int NETDT, int MODE>
+template <int KU, int NETDT, int MODE>
 __global__ void __launch_bounds__(kBlock, 3) k_em_rows(const EmArgs a, int lnet_bytes) {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     void* lnet = (void*)lds_raw;
     float* seg = (float*)(lds_raw + lnet_bytes);
     const uint32_t du = (uint32_t)a.du;
-    const int32_t r0 = blockIdx.x;                      // first (or only) row of this workgroup
-    const int nrows = PAIR2 ? 2 : 1;
-    const int32_t half_rows = a.n >> 1;
+    const int32_t r0 = blockIdx.x;                      // the row of this workgroup
 
     em_stage_row<NETDT>(a, r0, lnet);
     // this thread's proposal groups: p = 4 * (tid + 256 k)
     int4 o4[KU];
-    uint32_t hi[KU][4];
     float z[KU][4];
     float4 x4[KU];
     {
@@ -614,15 +610,16 @@ __global__ void __launch_bounds__(kBlock, 3) k_em_rows(const EmArgs a, int lnet_
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 uint32_t lo;
-                if (FBSMI_EM_PROBE == 2) { lo = e0 + j; hi[k][j] = lo; }
-                else if (PAIR2) threefry2x32(a.k0, a.k1, e0 + j, e0 + j + a.half, lo, hi[k][j]);
+                if (FBSMI_EM_PROBE == 2) lo = e0 + j;
                 else lo = random_bits_at(a.k0, a.k1, a.ntot_el, (uint64_t)e0 + j);
                 z[k][j] = (FBSMI_EM_PROBE == 1 || FBSMI_EM_PROBE == 2) ? fbsmi_u2f(lo >> 9) : normal_from_bits(lo);
             }
         }
     }
-    for (int rr = 0; rr < nrows; ++rr) {
-        const int32_t r = rr == 0 ? r0 : r0 + half_rows;
+    // One trip.  Written as a loop because the compiler allocates registers and schedules the kernel differently without
+    // it: this form keeps the machine code every timing of this kernel in DESIGN.md was taken with.
+    for (int once = 0; once < 1; ++once) {
+        const int32_t r = r0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LDS-DMA of this row (and the operand loads) have landed
         __syncthreads();
         // ---- proposal for row r ----
@@ -653,23 +650,6 @@ __global__ void __launch_bounds__(kBlock, 3) k_em_rows(const EmArgs a, int lnet_
         // ---- log-density of row r ----
         const float root = FBSMI_EM_PROBE == 5 ? 0.0f : em_row_logpdf_lds<NETDT, MODE>(a, lnet, seg);
         if (threadIdx.x == 0) a.lw[r] = root;
-        if (PAIR2 && rr == 0) {
-            __syncthreads();                                 // everyone is done with the staged row and the segment sums
-            const int32_t r2 = r0 + half_rows;
-            em_stage_row<NETDT>(a, r2, lnet);
-            const int64_t src = a.A ? (int64_t)a.A[r2] : (int64_t)r2;
-#pragma unroll
-            for (int k = 0; k < KU; ++k) {
-                const uint32_t p = 4u * (threadIdx.x + 256u * k);
-                const uint32_t pl = p < du ? p : du - 4;
-                x4[k] = *(const float4*)(a.us + src * du + pl);
-            }
-#pragma unroll
-            for (int k = 0; k < KU; ++k)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    z[k][j] = (FBSMI_EM_PROBE == 1 || FBSMI_EM_PROBE == 2) ? fbsmi_u2f(hi[k][j] >> 9) : normal_from_bits(hi[k][j]);
-        }
     }
 }
 
@@ -775,24 +755,23 @@ int launch_finish(const EmArgs& a, int net_dtype, int mode, size_t lds, hipStrea
     return FBSMI_OK;
 }
 
-template <int KU, bool PAIR2>
+template <int KU>
 int launch_rows(const EmArgs& a, int net_dtype, int mode, int lnet_bytes, size_t lds, hipStream_t st) {
-    const dim3 grid((unsigned)(PAIR2 ? a.n / 2 : a.n));
-    if (net_dtype == 0 && mode == 0) k_em_rows<KU, PAIR2, 0, 0><<<grid, kBlock, lds, st>>>(a, lnet_bytes);
-    else if (net_dtype == 0) k_em_rows<KU, PAIR2, 0, 1><<<grid, kBlock, lds, st>>>(a, lnet_bytes);
-    else if (mode == 0) k_em_rows<KU, PAIR2, 1, 0><<<grid, kBlock, lds, st>>>(a, lnet_bytes);
-    else k_em_rows<KU, PAIR2, 1, 1><<<grid, kBlock, lds, st>>>(a, lnet_bytes);
+    const dim3 grid((unsigned)a.n);
+    if (net_dtype == 0 && mode == 0) k_em_rows<KU, 0, 0><<<grid, kBlock, lds, st>>>(a, lnet_bytes);
+    else if (net_dtype == 0) k_em_rows<KU, 0, 1><<<grid, kBlock, lds, st>>>(a, lnet_bytes);
+    else if (mode == 0) k_em_rows<KU, 1, 0><<<grid, kBlock, lds, st>>>(a, lnet_bytes);
+    else k_em_rows<KU, 1, 1><<<grid, kBlock, lds, st>>>(a, lnet_bytes);
     FBSMI_LAUNCH_CHECK();
     return FBSMI_OK;
 }
 
-template <bool PAIR2>
 int launch_rows_ku(int ku, const EmArgs& a, int net_dtype, int mode, int lnet_bytes, size_t lds, hipStream_t st) {
     switch (ku) {
-        case 1: return launch_rows<1, PAIR2>(a, net_dtype, mode, lnet_bytes, lds, st);
-        case 2: return launch_rows<2, PAIR2>(a, net_dtype, mode, lnet_bytes, lds, st);
-        case 3: return launch_rows<3, PAIR2>(a, net_dtype, mode, lnet_bytes, lds, st);
-        default: return launch_rows<4, PAIR2>(a, net_dtype, mode, lnet_bytes, lds, st);
+        case 1: return launch_rows<1>(a, net_dtype, mode, lnet_bytes, lds, st);
+        case 2: return launch_rows<2>(a, net_dtype, mode, lnet_bytes, lds, st);
+        case 3: return launch_rows<3>(a, net_dtype, mode, lnet_bytes, lds, st);
+        default: return launch_rows<4>(a, net_dtype, mode, lnet_bytes, lds, st);
     }
 }
 
@@ -805,6 +784,111 @@ bool mask_ok(const fbsmi_em_mask* m) {
     return m && m->du >= 1 && m->dv >= 0 && m->u_off && (m->dv == 0 || m->v_off) && m->role;
 }
 
+// The flat draw of a call: n_total * du normals, of which rows [row0, row0 + n) are this call's.
+struct EmDraw {
+    uint32_t ntot_el, half, first_el, nloc_el;
+};
+
+EmDraw em_draw(const fbsmi_em_mask* mask, int64_t n_total, int64_t row0, int64_t n) {
+    EmDraw d;
+    d.ntot_el = (uint32_t)(n_total * mask->du);
+    d.half = (uint32_t)(((uint64_t)d.ntot_el + 1) >> 1);
+    d.first_el = (uint32_t)(row0 * mask->du);
+    d.nloc_el = (uint32_t)(n * mask->du);
+    return d;
+}
+
+// The largest flat draw: a thread of the element-wise proposal walk tests e0 + k < lim with e0 + k up to lim + 2 in 32 bits.
+constexpr int64_t kEmMaxDraw = ((int64_t)1 << 32) - 4;
+
+// Every argument check and every dispatch decision of fbsmi_em_finish, on the host and from the VALUES of the pointers
+// alone: what fbsmi_em_finish launches is what this fills in.  kernel == FBSMI_EM_KERNEL_NONE: the call does nothing.
+int plan_finish(const fbsmi_em_mask* mask, const void* us, const void* net, int net_dtype, int mode, const void* v,
+                const void* v_prev, int64_t n_total, int64_t row0, int64_t n, int64_t pin_row, const void* pin_value,
+                const void* us_new, const void* lw, fbsmi_em_plan& p) {
+    p = fbsmi_em_plan{};
+    FBSMI_NEED(mask_ok(mask) && n >= 0 && row0 >= 0 && row0 + n <= n_total && (net_dtype == 0 || net_dtype == 1) &&
+                   (mode == 0 || mode == 1), "em_finish: bad arguments");
+    if (n == 0 || (!us_new && !lw)) return FBSMI_OK;
+    FBSMI_NEED(net && n < ((int64_t)1 << 31), "em_finish: null network output or too many rows");
+    FBSMI_NEED(mask->du + mask->dv >= 4, "em_finish: images of fewer than 4 floats are not supported");
+    FBSMI_NEED(!us_new || (us && us_new != us), "em_finish: the proposal needs us, and us_new must not alias it");
+    FBSMI_NEED(!lw || mask->dv == 0 || (v && v_prev), "em_finish: the weights need v and v_prev");
+    FBSMI_NEED(pin_row < 0 || (pin_row < n && pin_value), "em_finish: bad pin");
+    FBSMI_NEED(n_total * (int64_t)mask->du <= kEmMaxDraw, "em_finish: the noise draw exceeds 2^32 - 4 elements");
+    const EmDraw d = em_draw(mask, n_total, row0, n);
+    const bool pair = row0 == 0 && n == n_total;
+    const uint32_t groups = pair ? (d.half + 3) / 4 : (d.nloc_el + 3) / 4;
+    p.pair = pair;
+    p.nU = us_new ? (int32_t)((groups + kBlock - 1) / kBlock) : 0;
+    p.nV = lw ? (int32_t)n : 0;
+    p.vfirst = (p.nU > 0 && p.nV > 0 && p.nU + p.nV <= 8192) ? 1 : 0;   // up to ~4 workgroups per CU slot: rows first
+    // 16-byte accesses on particle rows: whole rows of 4-float groups, aligned bases, and in the paired
+    // walk a second half that starts on a group boundary
+    const bool vec = mask->du % 4 == 0 && (!pair || d.half % 4 == 0) && (d.first_el % 4 == 0) &&
+                     ((((uintptr_t)us | (uintptr_t)us_new) & 15) == 0);
+    p.vec = vec;
+    FBSMI_NEED((((uintptr_t)mask->u_off | (uintptr_t)mask->v_off) & 15) == 0,
+               "em_finish: the mask tables must be 16-byte aligned");
+    const size_t lds = seg_lds_bytes(mask->dv);
+    p.nseg = (mask->dv + 255) >> 8;
+    // A rank's row slice of a sharded ensemble cannot pair the Threefry words, and its proposal groups then cost the
+    // two-role kernel 96 us at the config-5 share; one pass over whole rows (k_em_rows) does it in 56.  The whole draw
+    // stays on the two-role kernel (49 us against 62).  FBSMI_EM_ROWS=0 forces the two-role kernel (diagnostics).
+    static const int rows_on = [] { const char* e = getenv("FBSMI_EM_ROWS"); return e ? atoi(e) : 1; }();
+    const int esz = net_dtype == 0 ? 4 : 2;
+    const int64_t rowbytes = (int64_t)(mask->du + mask->dv) * esz;
+    const int lnet_bytes = (int)((rowbytes + 1023) / 1024 * 1024);
+    const bool rows_ok = rows_on && !pair && us_new && lw && vec && mask->dv >= 1 && mask->du <= 4096 && rowbytes % 16 == 0 &&
+                         lnet_bytes + (int64_t)lds <= 52 * 1024 && (((uintptr_t)net) & 15) == 0 && n >= 64;
+    if (rows_ok) {
+        p.kernel = FBSMI_EM_KERNEL_ROWS;
+        p.ku = (mask->du + 1023) / 1024;
+        p.lnet_bytes = lnet_bytes;
+        p.lds_bytes = (int32_t)((size_t)lnet_bytes + lds);
+        p.grid = (int32_t)n;
+    } else {
+        p.kernel = FBSMI_EM_KERNEL_FINISH;
+        p.lds_bytes = (int32_t)lds;
+        p.grid = p.nU + p.nV;
+    }
+    return FBSMI_OK;
+}
+
+int plan_concat(const fbsmi_em_mask* mask, const void* us, const void* v_prev, int64_t n, int out_dtype, const void* img,
+                fbsmi_em_plan& p) {
+    p = fbsmi_em_plan{};
+    FBSMI_NEED(mask_ok(mask) && n >= 0 && (out_dtype == 0 || out_dtype == 1), "em_concat: bad arguments");
+    if (n == 0) return FBSMI_OK;
+    FBSMI_NEED(us && img && (mask->dv == 0 || v_prev), "em_concat: null pointer");
+    const int32_t D = mask->du + mask->dv;
+    const int32_t chunks = (D + 1024 * kCatGroups - 1) / (1024 * kCatGroups);
+    FBSMI_NEED(n * chunks < (int64_t)1 << 31, "em_concat: too many rows");
+    p.kernel = FBSMI_EM_KERNEL_CONCAT;
+    p.vec = D % 4 == 0 && mask->du >= 4 && mask->dv >= 4 && ((uintptr_t)img & 15) == 0 &&
+            ((uintptr_t)mask->role & 15) == 0;
+    p.ku = chunks;
+    p.grid = (int32_t)(n * chunks);
+    return FBSMI_OK;
+}
+
+int plan_translp(const fbsmi_em_mask* mask, const void* us, const void* net, int net_dtype, int mode, const void* u,
+                 int64_t n, const void* lw, fbsmi_em_plan& p) {
+    p = fbsmi_em_plan{};
+    FBSMI_NEED(mask_ok(mask) && n >= 0 && (net_dtype == 0 || net_dtype == 1) && (mode == 0 || mode == 1),
+               "em_transition_logpdf: bad arguments");
+    if (n == 0) return FBSMI_OK;
+    FBSMI_NEED(us && net && u && lw && n < ((int64_t)1 << 31), "em_transition_logpdf: null pointer");
+    FBSMI_NEED(mask->du + mask->dv >= 4, "em_transition_logpdf: images of fewer than 4 floats are not supported");
+    FBSMI_NEED(((uintptr_t)mask->u_off & 15) == 0, "em_transition_logpdf: the mask tables must be 16-byte aligned");
+    p.kernel = FBSMI_EM_KERNEL_TRANSLP;
+    p.nV = (int32_t)n;
+    p.nseg = (mask->du + 255) >> 8;
+    p.lds_bytes = (int32_t)seg_lds_bytes(mask->du);
+    p.grid = (int32_t)n;
+    return FBSMI_OK;
+}
+
 }  // namespace
 
 }  // namespace fbsmi
@@ -813,22 +897,38 @@ using namespace fbsmi;
 
 extern "C" {
 
+int fbsmi_em_concat_plan(const fbsmi_em_mask* mask, const void* us, const void* v_prev, int64_t n, int out_dtype,
+                         const void* img, fbsmi_em_plan* plan) {
+    FBSMI_NEED(plan, "em_concat_plan: null plan");
+    return plan_concat(mask, us, v_prev, n, out_dtype, img, *plan);
+}
+
+int fbsmi_em_finish_plan(const fbsmi_em_mask* mask, const void* us, const void* net, int net_dtype, int mode, const void* v,
+                         const void* v_prev, int64_t n_total, int64_t row0, int64_t n, int64_t pin_row,
+                         const void* pin_value, const void* us_new, const void* lw, fbsmi_em_plan* plan) {
+    FBSMI_NEED(plan, "em_finish_plan: null plan");
+    return plan_finish(mask, us, net, net_dtype, mode, v, v_prev, n_total, row0, n, pin_row, pin_value, us_new, lw, *plan);
+}
+
+int fbsmi_em_transition_logpdf_plan(const fbsmi_em_mask* mask, const void* us, const void* net, int net_dtype, int mode,
+                                    const void* u, int64_t n, const void* lw, fbsmi_em_plan* plan) {
+    FBSMI_NEED(plan, "em_transition_logpdf_plan: null plan");
+    return plan_translp(mask, us, net, net_dtype, mode, u, n, lw, *plan);
+}
+
 int fbsmi_em_concat(const fbsmi_em_mask* mask, const float* us, const int32_t* A, const float* v_prev, int64_t n,
                     int out_dtype, void* img, void* stream) {
-    FBSMI_NEED(mask_ok(mask) && n >= 0 && (out_dtype == 0 || out_dtype == 1), "em_concat: bad arguments");
-    if (n == 0) return FBSMI_OK;
-    FBSMI_NEED(us && img && (mask->dv == 0 || v_prev), "em_concat: null pointer");
+    fbsmi_em_plan p;
+    const int rc = plan_concat(mask, us, v_prev, n, out_dtype, img, p);
+    if (rc != FBSMI_OK || p.kernel == FBSMI_EM_KERNEL_NONE) return rc;
     const int32_t D = mask->du + mask->dv;
-    const int32_t chunks = (D + 1024 * kCatGroups - 1) / (1024 * kCatGroups);
-    FBSMI_NEED(n * chunks < (int64_t)1 << 31, "em_concat: too many rows");
-    const bool vec = D % 4 == 0 && mask->du >= 4 && mask->dv >= 4 && ((uintptr_t)img & 15) == 0 &&
-                     ((uintptr_t)mask->role & 15) == 0;
+    const int32_t chunks = p.ku;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)(n * chunks));
+    const dim3 grid((unsigned)p.grid);
 #define FBSMI_CC(OD, V) \
     k_em_concat<OD, V><<<grid, kBlock, 0, st>>>(us, A, v_prev, mask->role, mask->du, D, chunks, img)
-    if (out_dtype == 0) { if (vec) FBSMI_CC(0, true); else FBSMI_CC(0, false); }
-    else { if (vec) FBSMI_CC(1, true); else FBSMI_CC(1, false); }
+    if (out_dtype == 0) { if (p.vec) FBSMI_CC(0, true); else FBSMI_CC(0, false); }
+    else { if (p.vec) FBSMI_CC(1, true); else FBSMI_CC(1, false); }
 #undef FBSMI_CC
     FBSMI_LAUNCH_CHECK();
     return FBSMI_OK;
@@ -838,77 +938,41 @@ int fbsmi_em_finish(const fbsmi_em_mask* mask, const float* us, const int32_t* A
                     const int32_t* net_A, int net_dtype, int mode, float cx, float cs, float dt, float sd, const float* v, const float* v_prev, uint32_t k0,
                     uint32_t k1, int64_t n_total, int64_t row0, int64_t n, int64_t pin_row, const float* pin_value,
                     float* us_new, float* lw, void* stream) {
-    FBSMI_NEED(mask_ok(mask) && n >= 0 && row0 >= 0 && row0 + n <= n_total && (net_dtype == 0 || net_dtype == 1) &&
-                   (mode == 0 || mode == 1), "em_finish: bad arguments");
-    if (n == 0 || (!us_new && !lw)) return FBSMI_OK;
-    FBSMI_NEED(net && n < ((int64_t)1 << 31), "em_finish: null network output or too many rows");
-    FBSMI_NEED(mask->du + mask->dv >= 4, "em_finish: images of fewer than 4 floats are not supported");
-    FBSMI_NEED(!us_new || (us && us_new != us), "em_finish: the proposal needs us, and us_new must not alias it");
-    FBSMI_NEED(!lw || mask->dv == 0 || (v && v_prev), "em_finish: the weights need v and v_prev");
-    FBSMI_NEED(pin_row < 0 || (pin_row < n && pin_value), "em_finish: bad pin");
-    FBSMI_NEED(n_total * (int64_t)mask->du < ((int64_t)1 << 32), "em_finish: the noise draw exceeds 2^32 elements");
+    fbsmi_em_plan p;
+    const int rc = plan_finish(mask, us, net, net_dtype, mode, v, v_prev, n_total, row0, n, pin_row, pin_value, us_new, lw, p);
+    if (rc != FBSMI_OK || p.kernel == FBSMI_EM_KERNEL_NONE) return rc;
+    const EmDraw d = em_draw(mask, n_total, row0, n);
     EmArgs a;
     a.us = us; a.A = A; a.net_A = net_A; a.net = net; a.v = v; a.v_prev = v_prev; a.pin_value = pin_value;
     a.us_new = us_new; a.lw = lw; a.u_off = mask->u_off; a.v_off = mask->v_off;
     a.du = mask->du; a.dv = mask->dv; a.D = mask->du + mask->dv;
     a.cx = cx; a.cs = cs; a.dt = dt; a.sd = sd; a.k0 = k0; a.k1 = k1;
-    a.ntot_el = (uint32_t)(n_total * mask->du);
-    a.half = (uint32_t)(((uint64_t)a.ntot_el + 1) >> 1);
-    a.first_el = (uint32_t)(row0 * mask->du);
-    a.nloc_el = (uint32_t)(n * mask->du);
+    a.ntot_el = d.ntot_el; a.half = d.half; a.first_el = d.first_el; a.nloc_el = d.nloc_el;
     a.n = (int32_t)n;
     a.pin_row = us_new && pin_row >= 0 ? (int32_t)pin_row : -1;
-    const bool pair = row0 == 0 && n == n_total;
-    const uint32_t groups = pair ? (a.half + 3) / 4 : (a.nloc_el + 3) / 4;
-    a.nU = us_new ? (int32_t)((groups + kBlock - 1) / kBlock) : 0;
-    a.nV = lw ? (int32_t)n : 0;
-    a.vfirst = (a.nU > 0 && a.nV > 0 && a.nU + a.nV <= 8192) ? 1 : 0;   // up to ~4 workgroups per CU slot: rows first
-    // 16-byte accesses on particle rows: whole rows of 4-float groups, aligned bases, and in the paired
-    // walk a second half that starts on a group boundary
-    const bool vec = mask->du % 4 == 0 && (!pair || a.half % 4 == 0) && (a.first_el % 4 == 0) &&
-                     ((((uintptr_t)us | (uintptr_t)us_new) & 15) == 0);
-    FBSMI_NEED((((uintptr_t)mask->u_off | (uintptr_t)mask->v_off) & 15) == 0,
-               "em_finish: the mask tables must be 16-byte aligned");
-    const size_t lds = seg_lds_bytes(mask->dv);
+    a.nU = p.nU; a.nV = p.nV; a.vfirst = p.vfirst;
     hipStream_t st = (hipStream_t)stream;
-    // A rank's row slice of a sharded ensemble cannot pair the Threefry words, and its proposal groups then cost the
-    // two-role kernel 96 us at the config-5 share; one pass over whole rows (k_em_rows) does it in 56.  The whole draw
-    // stays on the two-role kernel (49 us against 62).  FBSMI_EM_ROWS=0 forces the two-role kernel (diagnostics).
-    {
-        static const int rows_on = [] { const char* e = getenv("FBSMI_EM_ROWS"); return e ? atoi(e) : 1; }();
-        const int esz = net_dtype == 0 ? 4 : 2;
-        const int64_t rowbytes = (int64_t)a.D * esz;
-        const int lnet_bytes = (int)((rowbytes + 1023) / 1024 * 1024);
-        const bool rows_ok = rows_on && !pair && us_new && lw && vec && mask->dv >= 1 && mask->du <= 4096 && rowbytes % 16 == 0 &&
-                             lnet_bytes + (int64_t)lds <= 52 * 1024 && (((uintptr_t)net) & 15) == 0 && n >= 64;
-        if (rows_ok) {
-            const int ku = (mask->du + 1023) / 1024;
-            const size_t tot = (size_t)lnet_bytes + lds;
-            return launch_rows_ku<false>(ku, a, net_dtype, mode, lnet_bytes, tot, st);
-        }
-    }
-    if (pair) return vec ? launch_finish<true, true>(a, net_dtype, mode, lds, st)
-                         : launch_finish<true, false>(a, net_dtype, mode, lds, st);
-    return vec ? launch_finish<false, true>(a, net_dtype, mode, lds, st)
-               : launch_finish<false, false>(a, net_dtype, mode, lds, st);
+    const size_t lds = (size_t)p.lds_bytes;
+    if (p.kernel == FBSMI_EM_KERNEL_ROWS) return launch_rows_ku(p.ku, a, net_dtype, mode, p.lnet_bytes, lds, st);
+    if (p.pair) return p.vec ? launch_finish<true, true>(a, net_dtype, mode, lds, st)
+                             : launch_finish<true, false>(a, net_dtype, mode, lds, st);
+    return p.vec ? launch_finish<false, true>(a, net_dtype, mode, lds, st)
+                 : launch_finish<false, false>(a, net_dtype, mode, lds, st);
 }
 
 int fbsmi_em_transition_logpdf(const fbsmi_em_mask* mask, const float* us, const void* net, int net_dtype, int mode,
                                float cx, float cs, float dt, float sd, const float* u, int64_t n, float* lw,
                                void* stream) {
-    FBSMI_NEED(mask_ok(mask) && n >= 0 && (net_dtype == 0 || net_dtype == 1) && (mode == 0 || mode == 1),
-               "em_transition_logpdf: bad arguments");
-    if (n == 0) return FBSMI_OK;
-    FBSMI_NEED(us && net && u && lw && n < ((int64_t)1 << 31), "em_transition_logpdf: null pointer");
-    FBSMI_NEED(mask->du + mask->dv >= 4, "em_transition_logpdf: images of fewer than 4 floats are not supported");
-    FBSMI_NEED(((uintptr_t)mask->u_off & 15) == 0, "em_transition_logpdf: the mask tables must be 16-byte aligned");
+    fbsmi_em_plan p;
+    const int rc = plan_translp(mask, us, net, net_dtype, mode, u, n, lw, p);
+    if (rc != FBSMI_OK || p.kernel == FBSMI_EM_KERNEL_NONE) return rc;
     EmArgs a = {};
     a.us = us; a.net = net; a.v = u; a.lw = lw; a.u_off = mask->u_off; a.v_off = mask->v_off;
     a.du = mask->du; a.dv = mask->dv; a.D = mask->du + mask->dv;
     a.cx = cx; a.cs = cs; a.dt = dt; a.sd = sd; a.n = (int32_t)n; a.pin_row = -1;
-    const size_t lds = seg_lds_bytes(mask->du);
+    const size_t lds = (size_t)p.lds_bytes;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)n);
+    const dim3 grid((unsigned)p.grid);
     if (net_dtype == 0 && mode == 0) k_em_translp<0, 0><<<grid, kBlock, lds, st>>>(a);
     else if (net_dtype == 0) k_em_translp<0, 1><<<grid, kBlock, lds, st>>>(a);
     else if (mode == 0) k_em_translp<1, 0><<<grid, kBlock, lds, st>>>(a);

@@ -608,7 +608,8 @@ int fbsmi_em_concat(const fbsmi_em_mask* mask, const float* us, const int32_t* A
  *   us_new[r] = (x + drift_u * dt) + sd * z;   us_new[pin_row] = pin_value (pin_row < 0: no pin);
  *   lw[r] = tree-sum_j ( log(2 pi sd^2) + (v[j] - (v_prev[j] + drift_v[j] * dt))^2 / sd^2 ) / -2
  * (jax.scipy.stats.norm.logpdf summed in the canonical pairwise order of include/fbsmi_math.h).
- * us_new (n, du) nullable (no proposal), lw (n) nullable (no weights); us_new must not alias us. */
+ * us_new (n, du) nullable (no proposal), lw (n) nullable (no weights); us_new must not alias us.
+ * n_total * du <= 2^32 - 4 (FBSMI_ERR_ARG beyond: the flat index of the draw is 32 bits wide). */
 int fbsmi_em_finish(const fbsmi_em_mask* mask, const float* us, const int32_t* A, const void* net,
                     const int32_t* net_A, int net_dtype, int mode, float cx, float cs, float dt, float sd, const float* v, const float* v_prev, uint32_t k0,
                     uint32_t k1, int64_t n_total, int64_t row0, int64_t n, int64_t pin_row, const float* pin_value,
@@ -619,6 +620,36 @@ int fbsmi_em_finish(const fbsmi_em_mask* mask, const float* us, const int32_t* A
 int fbsmi_em_transition_logpdf(const fbsmi_em_mask* mask, const float* us, const void* net, int net_dtype, int mode,
                                float cx, float cs, float dt, float sd, const float* u, int64_t n, float* lw,
                                void* stream);
+
+/* What a call of the three entry points above would launch, decided on the host from the mask's sizes and the VALUES of
+ * the pointers (nothing is dereferenced, no HIP call is made: these run without a GPU).  Each *_plan function takes the
+ * arguments of its entry point that the decision or an argument check reads, returns what the entry point would return
+ * for them (FBSMI_ERR_ARG with the same message for a refused call), and fills *plan; the entry points themselves launch
+ * from the same plan.  kernel NONE: the call returns FBSMI_OK without a launch (n == 0, or nothing asked for). */
+#define FBSMI_EM_KERNEL_NONE 0
+#define FBSMI_EM_KERNEL_FINISH 1   /* k_em_finish: proposal and log-density workgroups in one grid */
+#define FBSMI_EM_KERNEL_ROWS 2     /* k_em_rows: one workgroup per row, the network row staged in LDS */
+#define FBSMI_EM_KERNEL_TRANSLP 3  /* k_em_translp */
+#define FBSMI_EM_KERNEL_CONCAT 4   /* k_em_concat */
+typedef struct fbsmi_em_plan {
+    int32_t kernel;      /* FBSMI_EM_KERNEL_* */
+    int32_t pair;        /* finish: the call covers the whole draw, a thread takes both words of a Threefry call */
+    int32_t vec;         /* finish, concat: the 16-byte variant (0: element by element) */
+    int32_t ku;          /* rows: proposal groups per thread, 1..4; concat: chunks of 4096 elements per row */
+    int32_t nU, nV;      /* finish: proposal / log-density workgroups; transition_logpdf: nV rows */
+    int32_t vfirst;      /* finish: 1 log-density workgroups first, 0 the two roles interleaved over the grid */
+    int32_t nseg;        /* 256-element segments of the summed part; above 64 the segment sums meet in an LDS tree */
+    int32_t lnet_bytes;  /* rows: LDS bytes of the staged network row */
+    int32_t lds_bytes;   /* dynamic LDS of the launch */
+    int32_t grid;        /* workgroups of the launch */
+} fbsmi_em_plan;
+int fbsmi_em_concat_plan(const fbsmi_em_mask* mask, const void* us, const void* v_prev, int64_t n, int out_dtype,
+                         const void* img, fbsmi_em_plan* plan);
+int fbsmi_em_finish_plan(const fbsmi_em_mask* mask, const void* us, const void* net, int net_dtype, int mode, const void* v,
+                         const void* v_prev, int64_t n_total, int64_t row0, int64_t n, int64_t pin_row,
+                         const void* pin_value, const void* us_new, const void* lw, fbsmi_em_plan* plan);
+int fbsmi_em_transition_logpdf_plan(const fbsmi_em_mask* mask, const void* us, const void* net, int net_dtype, int mode,
+                                    const void* u, int64_t n, const void* lw, fbsmi_em_plan* plan);
 
 /* HIP-event timing hooks: average duration in microseconds of the propagate ("Euler") kernel
  * over the launches since the last reset; 0 launches -> returns 0. Only measured when

@@ -34,9 +34,11 @@ def element_tables(unobs_pix, obs_pix, channels):
 
 
 def to_bf16_bits(x):
-    """float32 -> bfloat16 bit patterns, round to nearest even."""
+    """float32 -> bfloat16 bit patterns, round to nearest even; NaN stays NaN (its upper 16 bits with the quiet bit set:
+    the rounding increment would carry a small payload into the exponent, or out of the word)."""
     u = np.ascontiguousarray(x, F).view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    rne = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    return np.where((u & 0x7FFFFFFF) > 0x7F800000, (u >> 16) | 0x40, rne).astype(np.uint16)
 
 
 def from_bf16_bits(h):
@@ -83,9 +85,11 @@ def _logpdf_terms(target, base, drift, dt, sd):
 
 
 def finish(us, A, net, mode, cx, cs, dt, sd, v, v_prev, key, n_total, row0, pin_row, pin_value, u_off, v_off,
-           want_us=True, want_lw=True):
+           want_us=True, want_lw=True, z=None):
     """-> (us_new (n, du) or None, lw (n,) or None) for the n rows [row0, row0 + n) of an ensemble of
-    n_total rows; net (n, D) float32 (a bfloat16 network output is passed already widened)."""
+    n_total rows; net (n, D) float32 (a bfloat16 network output is passed already widened).
+    z (n, du), optional: rows [row0, row0 + n) of normal(key, (n_total, du)) computed by the caller, for a slice of a
+    draw too large to materialise (key and n_total are then not used)."""
     net = np.asarray(net, F)
     n = net.shape[0]
     du = u_off.size
@@ -93,7 +97,7 @@ def finish(us, A, net, mode, cx, cs, dt, sd, v, v_prev, key, n_total, row0, pin_
     us_new = lw = None
     if want_us:
         x = us2 if A is None else us2[np.asarray(A, np.int64)]
-        z = _normal(key, (int(n_total), du))[row0:row0 + n]
+        z = _normal(key, (int(n_total), du))[row0:row0 + n] if z is None else np.asarray(z, F).reshape(n, du)
         d = _drift(mode, cx, cs, x, net[:, u_off])
         us_new = ((x + (d * F(dt)).astype(F)).astype(F) + (F(sd) * z).astype(F)).astype(F)
         if pin_row is not None and pin_row >= 0:

@@ -80,7 +80,8 @@ def test_concat_matches_oracle(task, shape, n, out_dtype, oracle, dev):
 
 
 def _finish(emk, us, A, net, mode, cx, cs, dt, sd, v, vp, key, n_total, row0, pin_row, pin_val, dev, want_us=True,
-            want_lw=True, net_A=None):
+            want_lw=True, net_A=None, kernel=None):
+    """kernel: the kernel fbsmi_em_finish_plan must name for these very pointers, asserted before the launch."""
     from fbs_amd import _lib
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a is not None else None
     ust, At, vt, vpt, pt, nAt = t(us), t(A), t(v), t(vp), t(pin_val), t(net_A)
@@ -92,6 +93,12 @@ def _finish(emk, us, A, net, mode, cx, cs, dt, sd, v, vp, key, n_total, row0, pi
     out = torch.full((n, emk.du), np.nan, dtype=torch.float32, device=dev) if want_us else None
     lw = torch.full((n,), np.nan, dtype=torch.float32, device=dev) if want_lw else None
     p = lambda x: x.data_ptr() if x is not None else None
+    if kernel is not None:
+        plan = _lib.EMPlanStruct()
+        _lib.call("fbsmi_em_finish_plan", emk.ref, p(ust), nt.data_ptr(), 0 if nt.dtype == torch.float32 else 1, mode, p(vt),
+                  p(vpt), n_total, row0, n, pin_row, p(pt), p(out), p(lw), C.byref(plan))
+        assert (_lib.EM_KERNELS[plan.kernel], plan.pair, plan.vec) == (kernel, 0, int(emk.du % 4 == 0 and (row0 * emk.du) % 4 == 0)), \
+            (_lib.EM_KERNELS[plan.kernel], plan.pair, plan.vec, plan.ku)
     _lib.call("fbsmi_em_finish", emk.ref, p(ust), p(At), nt.data_ptr(), p(nAt), 0 if nt.dtype == torch.float32 else 1,
               mode, cx, cs, dt, sd, p(vt), p(vpt), int(key[0]), int(key[1]), n_total, row0, n, pin_row, p(pt), p(out),
               p(lw), 0)
@@ -140,9 +147,11 @@ def test_finish_matches_oracle(task, shape, n, mode, oracle, dev):
 @pytest.mark.parametrize("task,shape,n_total,row0,n", [("inpaint-15", (28, 28, 1), 50, 13, 21),
                                                         ("inpaint-8", (16, 16, 3), 96, 48, 48),
                                                         ("inpaint-8", (16, 16, 3), 97, 0, 40),
-                                                        ("supr-4", (28, 28, 1), 33, 32, 1)])
+                                                        ("supr-4", (28, 28, 1), 33, 32, 1),
+                                                        ("inpaint-8", (16, 16, 3), 96, 32, 64)])
 def test_finish_row_slices_equal_the_whole_draw(task, shape, n_total, row0, n, oracle, dev):
-    """A rank of a sharded ensemble: rows [row0, row0+n) of the n_total-row draw."""
+    """A rank of a sharded ensemble: rows [row0, row0+n) of the n_total-row draw.  From 64 rows on a slice of a mask whose
+    rows the 16-byte walk can take runs the one-pass rows kernel, below that the two-role kernel: each case asserts which."""
     from oracle import em
     ds, mask, emk = _mask(task, shape, dev, oracle.PRNGKey(6))
     u_off, v_off, role = _tables(oracle, mask, shape[2])
@@ -154,7 +163,8 @@ def test_finish_row_slices_equal_the_whole_draw(task, shape, n_total, row0, n, o
     key = oracle.PRNGKey(78)
     pin_val = rng.normal(size=emk.du).astype(np.float32)
     want_us, want_lw = em.finish(us, None, net, 0, cx, cs, dt, sd, v, vp, key, n_total, row0, 0, pin_val, u_off, v_off)
-    got_us, got_lw = _finish(emk, us, None, net, 0, cx, cs, dt, sd, v, vp, key, n_total, row0, 0, pin_val, dev)
+    got_us, got_lw = _finish(emk, us, None, net, 0, cx, cs, dt, sd, v, vp, key, n_total, row0, 0, pin_val, dev,
+                             kernel={21: "finish", 48: "finish", 64: "rows", 40: "finish", 1: "finish"}[n])
     _eq(got_us, want_us, "us_new"); _eq(got_lw, want_lw, "lw")
 
 
