@@ -12,10 +12,10 @@ from .linear_gaussian import LinearGaussianBridge  # noqa: F401
 from .gaussian_sb import GaussianSBBridge  # noqa: F401
 from .lg_twisted import GaussianTwisted  # noqa: F401
 from .lg_csgm import GaussianCSGM  # noqa: F401
-from .lg_kalman import LGKalman, kalman_conditional_sampler  # noqa: F401
+from .lg_kalman import LGKalman, LGKalmanSmoother, kalman_conditional_sampler, kalman_path_sampler  # noqa: F401
 
 __all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "GaussianSBBridge", "GaussianTwisted", "GaussianCSGM", "LGKalman",
-           "kalman_conditional_sampler", "PRNGKey", "split", "build"]
+           "LGKalmanSmoother", "kalman_conditional_sampler", "kalman_path_sampler", "PRNGKey", "split", "build"]
 
 
 def build(force: bool = False) -> str:

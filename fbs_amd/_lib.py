@@ -171,6 +171,10 @@ class KFModelStruct(C.Structure):
                 ("m_u", C.c_void_p), ("m_v", C.c_void_p), ("gain", C.c_void_p)]
 
 
+class KFSModelStruct(C.Structure):
+    _fields_ = [("kf", C.POINTER(KFModelStruct)), ("K", C.c_void_p), ("J", C.c_void_p), ("Lb", C.c_void_p)]
+
+
 class EMMaskStruct(C.Structure):
     _fields_ = [("du", C.c_int32), ("dv", C.c_int32), ("u_off", C.c_void_p), ("v_off", C.c_void_p),
                 ("role", C.c_void_p)]
@@ -257,6 +261,12 @@ SIGNATURES = {
     "fbsmi_kf_sample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fbsmi_kf_filter": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "fbsmi_kf_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
+    "fbsmi_kfs_create": (C.c_int, [C.POINTER(KFSModelStruct), _i32, C.POINTER(_vp)]),
+    "fbsmi_kfs_destroy": (None, [_vp]),
+    "fbsmi_kfs_sample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "fbsmi_kfs_sample_on": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "fbsmi_kfs_smooth": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "fbsmi_kfs_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
     "fbsmi_lg_sweep_profile": (C.c_int, [_vp, C.c_int]),
     "fbsmi_lg_sweep_kernel_us": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(_i64)]),
     "fbsmi_em_concat": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, _vp, _i64, C.c_int, _vp, _vp]),

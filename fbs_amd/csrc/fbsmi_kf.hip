@@ -24,6 +24,9 @@
 //   * Sum of squares.  sum_i qv_i^2 is the diagonal of the 16 x 16 Gram matrix of the qv tile, one MFMA chain on wave 0
 //     under the next step's first phase: acc = 0, acc = fmaf(qv_i, qv_i, acc), i ascending.
 // LDS: 2 z tiles of 64 * 68 floats, r and qv tiles of 64 * 36 floats, 53 248 bytes, static.
+//
+// fbsmi_kfs_* (the smoother and path sampler, further down) is built on the same pieces: a storing instantiation of k_kf
+// that writes every m_k and r_k as it goes, and k_kfs_back, the backward recursion over them in the same layout.
 #include <new>
 #include <vector>
 
@@ -50,6 +53,15 @@ struct KfDev {
     const float* m0;                         // [B][du]
 };
 
+// the last argument of k_kf: nothing (fbsmi_kf_*), or where every m_k and r_k goes (fbsmi_kfs_*)
+struct KfNoStore {
+    static constexpr bool on = false;
+};
+struct KfStore {
+    static constexpr bool on = true;
+    float *ms, *rs;                          // [B][T+1][du] [B][T][dv]
+};
+
 // what the front launch reads and writes
 struct KfFront {
     int du, dv, T;
@@ -58,6 +70,13 @@ struct KfFront {
     float* vs;                               // [B][T+1][dv]
     float* m0;                               // [B][du]
 };
+
+// A row index the compiler takes as new at every use: a store predicate formed from it is a compare where it is used,
+// not a lane mask held in two scalar registers across the step loop (eight of them do not fit beside the loop's state).
+__device__ __forceinline__ int kf_fresh(int r) {
+    asm volatile("" : "+v"(r));
+    return r;
+}
 
 // wide_pos of fbsmi_lg.hip for a 16-row tile: element (sample i, column c), S floats per plane row
 __device__ __forceinline__ int kf_pos(int i, int c, int S) { return ((c & 3) * kKfTile + i) * S + (c >> 2); }
@@ -159,11 +178,14 @@ __global__ void __launch_bounds__(kKfMaxD) k_kf_front(KfFront d, const uint32_t*
     } while (0)
 
 // The mean recursion, the log-likelihood and (DRAW) the draw for the 16 samples of a workgroup.  vs: the handle's buffer
-// (sample mode) or the caller's paths (filter mode), (B, T+1, dv); m0 is the front's.
-template <bool DRAW>
+// (sample mode) or the caller's paths (filter mode), (B, T+1, dv); m0 is the front's.  STORE (fbsmi_kfs_*): every m_k
+// and r_k is written to st.ms and st.rs as the step produces it; the arithmetic is the same, and the instantiations
+// without stores keep the arguments they had and, with them, their code.
+template <bool DRAW, class Store = KfNoStore>
 __global__ void __launch_bounds__(kBlock) k_kf(KfDev d, const float* __restrict__ vs, const uint32_t* __restrict__ keys,
                                                float* __restrict__ samples, float* __restrict__ means,
-                                               float* __restrict__ loglik, int B) {
+                                               float* __restrict__ loglik, int B, Store st = Store()) {
+    constexpr bool STORE = Store::on;
     __shared__ __attribute__((aligned(16))) float zs[2][4 * kKfTile * kKfSz];
     __shared__ __attribute__((aligned(16))) float rs[4 * kKfTile * kKfS1];
     __shared__ __attribute__((aligned(16))) float qs[4 * kKfTile * kKfS1];
@@ -203,6 +225,16 @@ __global__ void __launch_bounds__(kBlock) k_kf(KfDev d, const float* __restrict_
     __syncthreads();
     for (int c = lc; c < du; c += 16) zs[0][kf_pos(ls, c, Sz)] = d.m0[(size_t)lb * du + c];
     for (int c = lc; c < dv; c += 16) zs[0][kf_pos(ls, Ku + c, Sz)] = vsl[c];
+    float *msl = nullptr, *rsl = nullptr;   // STORE: this lane's sample in st.ms and st.rs, advanced a step per step
+    int dul = 0, dvl = 0;                   // the rows this lane stores: du and dv, none for a slot past the batch
+    if constexpr (STORE) {
+        if (blockIdx.x * kKfTile + ls < B)
+            for (int c = lc; c < du; c += 16) st.ms[(size_t)lb * ((size_t)T + 1) * du + c] = d.m0[(size_t)lb * du + c];
+        msl = st.ms + (size_t)bc * ((size_t)T + 1) * du;
+        dul = live ? du : 0;
+        dvl = live ? dv : 0;
+        rsl = st.rs + (size_t)bc * (size_t)T * dv;
+    }
 
     // operands of column group q of step k: H and Pm (phase 1), AK and W (phase 2), for this wave's row tiles
     // this lane's element of column group 0 of its first row tile, per table; a row tile is NQc * 64 float4 on, a step
@@ -341,6 +373,13 @@ __global__ void __launch_bounds__(kBlock) k_kf(KfDev d, const float* __restrict_
             if (tv[s]) {
 #pragma unroll
                 for (int v = 0; v < 4; ++v) rs[kf_pos(smp, 16 * (wave + kWaves * s) + 4 * lg + v, Sv)] = vr[s][v] - accH[s][v];
+                if (STORE) {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const int r = kf_fresh(16 * (wave + kWaves * s) + 4 * lg + v);
+                        if (r < dvl) rsl[r] = vr[s][v] - accH[s][v];
+                    }
+                }
             }
         }
 #pragma unroll
@@ -372,7 +411,12 @@ __global__ void __launch_bounds__(kBlock) k_kf(KfDev d, const float* __restrict_
                 const int r = 16 * (wave + kWaves * s) + 4 * lg + v;
                 if (tu[s]) zs[p ^ 1][kf_pos(smp, r, Sz)] = accP[s][v];
                 if (tv[s]) qs[kf_pos(smp, r, Sv)] = accW[s][v];
+                if (STORE && tu[s] && kf_fresh(r) < dul) msl[du + r] = accP[s][v];
             }
+        }
+        if (STORE) {
+            msl += du;
+            rsl += dv;
         }
         __syncthreads();
         p ^= 1;
@@ -430,6 +474,156 @@ __global__ void __launch_bounds__(kBlock) k_kf(KfDev d, const float* __restrict_
             const int r = 16 * (wave + kWaves * s) + 4 * lg + v;
             if (tu[s] && live && r < du) samples[(size_t)b * du + r] = accP[s][v];
         }
+}
+
+// ---- the backward pass of the smoother and path sampler (fbsmi_kfs_*) ---------------------------------------------------
+// delta_k = K[k] r_k + Lb[k] xi_k + J[k] delta_{k+1}, paths[k] = m_k + delta_k, k = T-1 .. 0, in k_kf's layout: a workgroup
+// owns 16 samples (the MFMA columns) for all T steps, the u row tiles are dealt round-robin to the waves, the tables sit in
+// the A-operand order of k_kf_pack.  delta is ping-ponged through LDS in the plane layout; r_k (the forward launch's) and
+// xi[k] = normal(key_bwd, (T, du))[k] are staged into double-buffered operand tiles a step ahead, so the K r and Lb xi
+// chains of step k - 1 run behind the barrier of step k, off the serial J delta path, whose operands are asked for a
+// step ahead as well.  One barrier per step.  LDS: six tiles of 64 * 36 floats, 55 296 bytes, static.
+struct KfsDev {
+    int du, dv, T, NQu, NQv, Su, Sv;
+    const float4 *Kp, *Jp, *Lbp;             // [T][NQu][NQv][64] [T][NQu][NQu][64] [T][NQu][NQu][64]
+    const float *ms, *rs, *uT;               // [B][T+1][du] [B][T][dv] [B][du]
+};
+
+template <bool DRAW>
+__global__ void __launch_bounds__(kBlock) k_kfs_back(KfsDev d, const uint32_t* __restrict__ keys, float* __restrict__ paths,
+                                                     int B) {
+    __shared__ __attribute__((aligned(16))) float ds[2][4 * kKfTile * kKfS1];
+    __shared__ __attribute__((aligned(16))) float rl[2][4 * kKfTile * kKfS1];
+    __shared__ __attribute__((aligned(16))) float xl[2][4 * kKfTile * kKfS1];
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int du = d.du, dv = d.dv, T = d.T, NQu = d.NQu, NQv = d.NQv, Su = d.Su, Sv = d.Sv;
+    const int smp = lane & 15, lg = lane >> 4;
+    const int b = blockIdx.x * kKfTile + smp;
+    const bool live = b < B;
+    const int bc = live ? b : B - 1;   // the slots past the batch repeat its last sample and store nothing
+    const int dul = live ? du : 0;     // the rows this lane stores
+    const int ls = t >> 4, lc = t & 15;   // the loader's view of the tile: sample t / 16, columns t % 16 + 16 j
+    const bool llive = blockIdx.x * kKfTile + ls < B;
+    const int lb = llive ? blockIdx.x * kKfTile + ls : B - 1;
+    const bool tu[2] = {wave < NQu, wave + kWaves < NQu};
+    const int wu[2] = {tu[0] ? wave : 0, tu[1] ? wave + kWaves : 0};
+    const size_t T1 = (size_t)T + 1;
+    const float* msb = d.ms + (size_t)bc * T1 * du;
+    float* pb = paths + (size_t)bc * T1 * du;
+    int rcl[2][4];                        // this lane's output rows, clamped to du - 1 for the loads of m_k
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int r = 16 * (wave + kWaves * s) + 4 * lg + v;
+            rcl[s][v] = r < du ? r : du - 1;
+        }
+
+    for (int e = t; e < 2 * 4 * kKfTile * kKfS1; e += kBlock) {
+        (&ds[0][0])[e] = 0.0f;
+        (&rl[0][0])[e] = 0.0f;
+        (&xl[0][0])[e] = 0.0f;
+    }
+    __syncthreads();
+    // delta_T = u_T - m_T (DRAW; u_T is the forward launch's draw, stored as it is) or 0
+    for (int c = lc; c < du; c += 16) {
+        const float mT = d.ms[((size_t)lb * T1 + T) * du + c];
+        if (DRAW) {
+            const float uT = d.uT[(size_t)lb * du + c];
+            ds[0][kf_pos(ls, c, Su)] = uT - mT;
+            if (llive) paths[((size_t)lb * T1 + T) * du + c] = uT;
+        } else {
+            if (llive) paths[((size_t)lb * T1 + T) * du + c] = mT + 0.0f;
+        }
+    }
+    uint32_t kb0 = 0, kb1 = 0;
+    if (DRAW) split_at(keys[2 * lb], keys[2 * lb + 1], 3, 1, kb0, kb1);   // key_bwd of the loader's sample
+    const uint64_t nxi = (uint64_t)kf_fresh(T) * du;   // (and what the draw derives from it: in vector registers)
+    // r_k and xi[k] of the loader's sample into the operand tiles `buf`
+    auto stage = [&](int k, int buf) {
+        const float* rg = d.rs + ((size_t)lb * T + k) * dv;
+        for (int c = lc; c < dv; c += 16) rl[buf][kf_pos(ls, c, Sv)] = rg[c];
+        if (DRAW)
+            for (int c = lc; c < du; c += 16) xl[buf][kf_pos(ls, c, Su)] = normal_at(kb0, kb1, nxi, (uint64_t)k * du + c);
+    };
+    // this lane's float4 of column group 0 of this wave's row tiles within a step's K and within its J or Lb (kept in
+    // vector registers, like jo below)
+    const int ko[2] = {kf_fresh(wu[0] * NQv * 64 + lane), kf_fresh(wu[1] * NQv * 64 + lane)};
+    const int lo[2] = {kf_fresh(wu[0] * NQu * 64 + lane), kf_fresh(wu[1] * NQu * 64 + lane)};
+    // acc = 0, then the K r_k chain, then the Lb xi_k chain, for this wave's row tiles
+    mfma_f4 acc[2];
+    auto ahead = [&](int k, int buf) {
+        const float4* rb = reinterpret_cast<const float4*>(rl[buf] + lane * Sv);
+        const float4* xb = reinterpret_cast<const float4*>(xl[buf] + lane * Su);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            acc[s] = mfma_f4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (!tu[s]) continue;
+            const float4* Kl = d.Kp + (size_t)k * NQu * NQv * 64 + ko[s];
+            for (int q = 0; q < NQv; ++q) {
+                const float4 a = Kl[q * 64], x = rb[q];
+                KF_MFMA4(acc[s], a, x);
+            }
+            if (DRAW) {
+                const float4* Ll = d.Lbp + (size_t)k * NQu * NQu * 64 + lo[s];
+                for (int q = 0; q < NQu; ++q) {
+                    const float4 a = Ll[q * 64], x = xb[q];
+                    KF_MFMA4(acc[s], a, x);
+                }
+            }
+        }
+    };
+    // the J operands of a step, all of this wave's: asked for a step ahead.  No load is predicated: a row tile this wave
+    // does not have is row tile 0 again and a column group past the last is the last again, loaded and not used.
+    float4 jr[kKfMaxD / 16][2];
+    int jo[kKfMaxD / 16];   // this lane's float4 of column group q (clamped) within a row tile: kept in vector registers
+#pragma unroll
+    for (int q = 0; q < kKfMaxD / 16; ++q) jo[q] = kf_fresh((q < NQu ? q : NQu - 1) * 64 + lane);
+    auto loadJ = [&](int k) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float4* Jl = d.Jp + (size_t)k * NQu * NQu * 64 + (lo[s] - lane);
+#pragma unroll
+            for (int q = 0; q < kKfMaxD / 16; ++q) jr[q][s] = Jl[jo[q]];
+        }
+    };
+    loadJ(T - 1);
+    stage(T - 1, 0);
+    __syncthreads();
+    ahead(T - 1, 0);
+
+    int p = 0;
+    for (int k = T - 1; k >= 0; --k) {
+        const int bk = (T - 1 - k) & 1;
+        float mk[2][4];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) mk[s][v] = msb[(size_t)k * du + rcl[s][v]];
+        if (k > 0) stage(k - 1, bk ^ 1);
+        const float4* db = reinterpret_cast<const float4*>(ds[p] + lane * Su);
+#pragma unroll
+        for (int q = 0; q < kKfMaxD / 16; ++q) {
+            if (q < NQu) {
+                const float4 x = db[q];
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+                    if (tu[s]) KF_MFMA4(acc[s], jr[q][s], x);
+            }
+        }
+        loadJ(k > 0 ? k - 1 : 0);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int r = 16 * (wave + kWaves * s) + 4 * lg + v;
+                if (tu[s]) ds[p ^ 1][kf_pos(smp, r, Su)] = acc[s][v];
+                if (tu[s] && kf_fresh(r) < dul) pb[(size_t)k * du + r] = mk[s][v] + acc[s][v];
+            }
+        __syncthreads();
+        p ^= 1;
+        if (k > 0) ahead(k - 1, bk ^ 1);
+    }
 }
 
 }  // namespace
@@ -539,7 +733,7 @@ int fbsmi_kf_sample(fbsmi_kf* h, const uint32_t* keys, const float* y0, float* s
     const KfDev& d = h->d;
     const int B = h->nsamples;
     k_kf_front<true><<<B, h->front_block, 0, st>>>(h->f, keys, y0, nullptr);
-    k_kf<true><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(d, h->f.vs, keys, samples, means, loglik, B);
+    k_kf<true><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(d, h->f.vs, keys, samples, means, loglik, B, KfNoStore());
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("kf_sample launch: ") + hipGetErrorString(e));
     return FBSMI_OK;
@@ -551,7 +745,7 @@ int fbsmi_kf_filter(fbsmi_kf* h, const float* vs, float* means, float* loglik, v
     const KfDev& d = h->d;
     const int B = h->nsamples;
     k_kf_front<false><<<B, h->front_block, 0, st>>>(h->f, nullptr, nullptr, vs);
-    k_kf<false><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(d, vs, nullptr, nullptr, means, loglik, B);
+    k_kf<false><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(d, vs, nullptr, nullptr, means, loglik, B, KfNoStore());
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("kf_filter launch: ") + hipGetErrorString(e));
     return FBSMI_OK;
@@ -567,6 +761,147 @@ int fbsmi_kf_view(fbsmi_kf* h, int which, void* dst, int64_t* count, void* strea
         case 0: src = h->f.vs; n = B * ((size_t)d.T + 1) * d.dv; break;
         case 1: src = h->f.m0; n = B * d.du; break;
         default: return fail(FBSMI_ERR_ARG, "kf_view: which must be 0 (vs) or 1 (m_)");
+    }
+    if (count) *count = (int64_t)n;
+    if (!dst || n == 0) return FBSMI_OK;
+    FBSMI_HIP_TRY(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return FBSMI_OK;
+}
+
+}  // extern "C"
+
+// ---- fbsmi_kfs_*: the smoother and path sampler on top of a filter handle of its own ------------------------------------
+struct fbsmi_kfs {
+    fbsmi_kf* kf = nullptr;   // the front, the forward tables, vs and m_0
+    KfsDev bd{};
+    int nsamples = 0;
+    void* pool = nullptr;
+};
+
+namespace {
+
+// the forward launches of a call: the front, then the storing recursion (and the draw of u_T into the handle's buffer)
+template <bool DRAW>
+void kfs_forward(fbsmi_kfs* h, const float* vs, const uint32_t* keys, float* loglik, hipStream_t st) {
+    const int B = h->nsamples;
+    k_kf<DRAW, KfStore><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(
+        h->kf->d, vs, keys, const_cast<float*>(h->bd.uT), nullptr, loglik, B,
+        KfStore{const_cast<float*>(h->bd.ms), const_cast<float*>(h->bd.rs)});
+}
+
+}  // namespace
+
+extern "C" {
+
+int fbsmi_kfs_create(const fbsmi_kfs_model* m, int32_t nsamples, fbsmi_kfs** out) {
+    if (!out || !m || !m->kf || m->kf->T < 1) return fail(FBSMI_ERR_ARG, "kfs_create: need a model with T >= 1");
+    const fbsmi_kf_model* f = m->kf;
+    if (!f->H || !f->e || !f->Pm || !f->c || !f->AK || !f->W || !f->lconst || !f->Lt || !f->F || !f->sqQ || !f->m_u || !f->m_v ||
+        !f->gain || !m->K || !m->J || !m->Lb)
+        return fail(FBSMI_ERR_ARG, "kfs_create: null table");
+    if (f->du < 1 || f->du > kKfMaxD || f->dv < 1 || f->dv > kKfMaxD || nsamples < 1 || nsamples > 65535)
+        return fail(FBSMI_ERR_UNSUPPORTED,
+                    "kfs_create: the fused Kalman smoother takes 1 <= du, dv <= 128 and 1 <= nsamples <= 65535");
+    fbsmi_kfs* h = new (std::nothrow) fbsmi_kfs();
+    if (!h) return fail(FBSMI_ERR_ARG, "out of host memory");
+    int rc = fbsmi_kf_create(f, nsamples, &h->kf);
+    if (rc != FBSMI_OK) {
+        delete h;
+        return rc;
+    }
+    const size_t T = f->T, du = f->du, dv = f->dv, B = nsamples;
+    const int NQu = h->kf->d.NQu, NQv = h->kf->d.NQv;
+    h->nsamples = nsamples;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t nK = T * NQu * NQv * 256, nJ = T * NQu * NQu * 256;
+    const size_t o_K = take(nK * 4), o_J = take(nJ * 4), o_L = take(nJ * 4);
+    const size_t o_ms = take(B * (T + 1) * du * 4), o_rs = take(B * T * dv * 4), o_uT = take(B * du * 4);
+    auto bail = [&](hipError_t e, const char* what) {
+        const int r = fail(FBSMI_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        fbsmi_kfs_destroy(h);
+        return r;
+    };
+    hipError_t e;
+    if ((e = hipMalloc(&h->pool, off)) != hipSuccess) return bail(e, "kfs_create: hipMalloc");
+    if ((e = hipMemset(h->pool, 0, off)) != hipSuccess) return bail(e, "kfs_create: hipMemset");
+    char* p = (char*)h->pool;
+    KfsDev& bd = h->bd;
+    bd.du = f->du; bd.dv = f->dv; bd.T = f->T; bd.NQu = NQu; bd.NQv = NQv; bd.Su = h->kf->d.Su; bd.Sv = h->kf->d.Sv;
+    bd.Kp = (const float4*)(p + o_K); bd.Jp = (const float4*)(p + o_J); bd.Lbp = (const float4*)(p + o_L);
+    bd.ms = (const float*)(p + o_ms); bd.rs = (const float*)(p + o_rs); bd.uT = (const float*)(p + o_uT);
+    const KfPack jobs[3] = {
+        {m->K, (float*)(p + o_K), (int)T, (int)du, (int)dv, 0, NQv, NQu, NQv, (int)dv, 0, du * dv},
+        {m->J, (float*)(p + o_J), (int)T, (int)du, (int)du, 0, NQu, NQu, NQu, (int)du, 0, du * du},
+        {m->Lb, (float*)(p + o_L), (int)T, (int)du, (int)du, 0, NQu, NQu, NQu, (int)du, 0, du * du},
+    };
+    const size_t counts[3] = {nK, nJ, nJ};
+    for (int i = 0; i < 3; ++i) {
+        k_kf_pack<<<(unsigned)((counts[i] + kBlock - 1) / kBlock), kBlock, 0, nullptr>>>(jobs[i]);
+        if ((e = hipGetLastError()) != hipSuccess) return bail(e, "kfs_create: pack launch");
+    }
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return bail(e, "kfs_create: pack");
+    *out = h;
+    return FBSMI_OK;
+}
+
+void fbsmi_kfs_destroy(fbsmi_kfs* h) {
+    if (!h) return;
+    if (h->pool) {
+        (void)hipDeviceSynchronize();
+        (void)hipFree(h->pool);
+    }
+    fbsmi_kf_destroy(h->kf);
+    delete h;
+}
+
+static int kfs_launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    return FBSMI_OK;
+}
+
+int fbsmi_kfs_sample(fbsmi_kfs* h, const uint32_t* keys, const float* y0, float* paths, float* loglik, void* stream) {
+    if (!h || !keys || !y0 || !paths) return fail(FBSMI_ERR_ARG, "kfs_sample: null argument");
+    if (!h->kf->has_fwd) return fail(FBSMI_ERR_UNSUPPORTED, "kfs_sample: the model has no exact forward transition (F, sqQ)");
+    hipStream_t st = (hipStream_t)stream;
+    const int B = h->nsamples;
+    k_kf_front<true><<<B, h->kf->front_block, 0, st>>>(h->kf->f, keys, y0, nullptr);
+    kfs_forward<true>(h, h->kf->f.vs, keys, loglik, st);
+    k_kfs_back<true><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(h->bd, keys, paths, B);
+    return kfs_launched("kfs_sample");
+}
+
+int fbsmi_kfs_sample_on(fbsmi_kfs* h, const uint32_t* keys, const float* vs, float* paths, float* loglik, void* stream) {
+    if (!h || !keys || !vs || !paths) return fail(FBSMI_ERR_ARG, "kfs_sample_on: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int B = h->nsamples;
+    k_kf_front<false><<<B, h->kf->front_block, 0, st>>>(h->kf->f, nullptr, nullptr, vs);
+    kfs_forward<true>(h, vs, keys, loglik, st);
+    k_kfs_back<true><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(h->bd, keys, paths, B);
+    return kfs_launched("kfs_sample_on");
+}
+
+int fbsmi_kfs_smooth(fbsmi_kfs* h, const float* vs, float* smeans, float* loglik, void* stream) {
+    if (!h || !vs || !smeans) return fail(FBSMI_ERR_ARG, "kfs_smooth: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int B = h->nsamples;
+    k_kf_front<false><<<B, h->kf->front_block, 0, st>>>(h->kf->f, nullptr, nullptr, vs);
+    kfs_forward<false>(h, vs, nullptr, loglik, st);
+    k_kfs_back<false><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(h->bd, nullptr, smeans, B);
+    return kfs_launched("kfs_smooth");
+}
+
+int fbsmi_kfs_view(fbsmi_kfs* h, int which, void* dst, int64_t* count, void* stream) {
+    if (!h) return fail(FBSMI_ERR_ARG, "kfs_view: null handle");
+    const size_t B = h->nsamples, T = h->bd.T;
+    const void* src = nullptr;
+    size_t n = 0;
+    switch (which) {
+        case 0: src = h->kf->f.vs; n = B * (T + 1) * h->bd.dv; break;
+        case 1: src = h->bd.ms; n = B * (T + 1) * h->bd.du; break;
+        case 2: src = h->bd.rs; n = B * T * h->bd.dv; break;
+        default: return fail(FBSMI_ERR_ARG, "kfs_view: which must be 0 (vs), 1 (filter means) or 2 (innovations)");
     }
     if (count) *count = (int64_t)n;
     if (!dst || n == 0) return FBSMI_OK;

@@ -332,6 +332,12 @@ class LinearGaussianBridge:
         from .lg_kalman import LGKalman
         return self._cached(("kalman", int(nsamples)), lambda: LGKalman(self, int(nsamples)))
 
+    def kalman_smoother_handle(self, nsamples: int = 1):
+        """The fused Kalman smoother and path sampler (fbs_amd/lg_kalman.py, LGKalmanSmoother) for `nsamples` paths per
+        call."""
+        from .lg_kalman import LGKalmanSmoother
+        return self._cached(("kalman_smoother", int(nsamples)), lambda: LGKalmanSmoother(self, int(nsamples)))
+
     def gibbs_kernel(self, key, x0, y0, bs_star, nparticles, explicit_backward=True, explicit_final=False,
                      use_graph=True, marg_y=False):
         """One fused sweep; same returns as fbs.samplers.gibbs_kernel: (x0, us_star, bs_star, acc)."""

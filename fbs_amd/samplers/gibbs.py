@@ -29,6 +29,11 @@ def bridge_sampler(key, y0, yT, ts, sde):
 def gibbs_init(key, y0, x0_shape, ts, fwd_sampler, sde, unpack, transition_sampler, transition_logpdf,
                likelihood_logpdf, nparticles, method: str = 'smoother', marg_y: bool = True, x0=None, **kwargs):
     """Initialise the Gibbs sampler with a draw from a bootstrap filter/smoother (gibbs.py:23-65)."""
+    if method == 'kalman':                                                          # refused before anything is drawn
+        from ..linear_gaussian import LinearGaussianBridge
+        model = _lg_model_of(fwd_sampler, transition_sampler, likelihood_logpdf, unpack)
+        if type(model) is not LinearGaussianBridge or kwargs or not model.same_grid(ts):
+            raise NotImplementedError("method='kalman' needs the closures of one LinearGaussianBridge on its own grid")
     device = y0.device if isinstance(y0, torch.Tensor) else ops._default_device()
     if x0 is None:
         x0 = torch.zeros(x0_shape, dtype=torch.float32, device=device)
@@ -50,6 +55,10 @@ def gibbs_init(key, y0, x0_shape, ts, fwd_sampler, sde, unpack, transition_sampl
                                stratified, log=True, return_last=False, **kwargs)[0]
         approx_x0 = uss[-1, 0]
         approx_us_star = bootstrap_backward_smoother(key_bwd, uss, vs, ts, transition_logpdf, **kwargs)
+    elif method == 'kalman':
+        # an exact draw from p(u_0..u_T | vs) of the discretised model (fbs_amd/lg_kalman.py), keyed by key_bf
+        approx_us_star = model.kalman_smoother_handle(1).sample_on(key_bf, vs)[0]
+        approx_x0 = approx_us_star[-1]
     elif method == 'debug':
         approx_x0 = bootstrap_filter(transition_sampler, likelihood_logpdf, vs, ts, init_sampler, key_bf, nparticles,
                                      stratified, log=True, return_last=False, **kwargs)[0]

@@ -571,6 +571,54 @@ int fbsmi_kf_filter(fbsmi_kf* h, const float* vs, float* means, float* loglik, v
  * of the last fbsmi_kf_sample; 1 m_ (B, du), the initial means m_0 of the last call of either kind. */
 int fbsmi_kf_view(fbsmi_kf* h, int which, void* dst, int64_t* count, void* stream);
 
+/* ---- batched, device-resident Kalman smoother and path sampler for the analytic model ---------------
+ * The exact counterpart of fbsmi_lg_backsim, as fbsmi_kf is of fbsmi_lg_fsamp: the smoothing law
+ * p(u_0..u_T | v_0..v_T) of the model above is Gaussian, and a draw from it is the forward filter followed by a backward
+ * sampler (Rauch-Tung-Striebel with noise).  Given u_{k+1} and v_0..v_T, u_k depends on (u_{k+1}, v_0..v_{k+1}) only
+ * (u_{k+1} and v_{k+2} depend on (u_{k+1}, v_{k+1}) only and the u and v noises are independent), so with m_k, Sigma_k the
+ * filtering moments before step k, r_k its innovation and Sigma_k+ = Sigma_k - K S K^T:
+ *   u_T ~ N(m_T, cov_T),   u_k = m_k + K_k r_k + J_k (u_{k+1} - m_{k+1}) + Lb_k xi_k,   k = T-1 .. 0.
+ * Tables (fbs_amd/lg_kalman.py, lg_smoother_tables; float64 on the host, rounded once to float32), per step k:
+ *   K[k] = Sigma_k C^T inv(S) (du, dv),   J[k] = Sigma_k+ A^T inv(Sigma_{k+1}) (du, du),
+ *   Lb[k] = lower Cholesky factor of Sigma_k+ - J Sigma_{k+1} J^T (symmetrised) (du, du), its upper triangle stored as zero.
+ * Numeric specification (float32, no contraction beyond the chains named; tests/kfs_restate.py restates it in numpy),
+ * sample b with key = keys[b]; the deviation delta_k = u_k - m_k is carried, not u_k:
+ *   keys          key_fwd, key_bwd, key_kf = split(key, 3)
+ *   front, m_0    exactly those of fbsmi_kf_sample (fbsmi_kf_filter when vs is the caller's)
+ *   forward       exactly the step of fbsmi_kf, in the same chains; every m_k (k = 0..T) and r_k (k = 0..T-1) is kept;
+ *                 loglik is fbsmi_kf's
+ *   u_T           exactly the sample line of fbsmi_kf (zz = normal(key_kf, (du,)), the chain from m_T over Lt):
+ *                 paths[b][T] = u_T;  delta_T = u_T - m_T
+ *   noise         xi = normal(key_bwd, (T, du)); step k uses xi[k]
+ *   step k        k = T-1 .. 0, every j: acc = 0;
+ *                 acc = fbsmi_fmaf(K[k][j][c], r_k[c], acc), c ascending;
+ *                 acc = fbsmi_fmaf(Lb[k][j][c], xi[k][c], acc), c ascending over all of [0, du);
+ *                 acc = fbsmi_fmaf(J[k][j][c], delta_{k+1}[c], acc), c ascending;
+ *                 delta_k[j] = acc;  paths[b][k][j] = m_k[j] + delta_k[j]
+ *   smooth        delta_T = 0 (smeans[b][T][j] = m_T[j] + 0), the Lb line is left out, nothing is drawn.
+ * A call is three plain launches on the caller's stream (the front; the forward recursion with stores; the backward
+ * pass), nothing on the host inside it. */
+typedef struct fbsmi_kfs_model {
+    const fbsmi_kf_model* kf;
+    const float* K;  /* (T, du, dv) */
+    const float* J;  /* (T, du, du) */
+    const float* Lb; /* (T, du, du) */
+} fbsmi_kfs_model;
+typedef struct fbsmi_kfs fbsmi_kfs; /* opaque: a filter handle of its own, the packed K, J, Lb, the m_k, r_k and u_T buffers */
+/* Argument checks and limits are fbsmi_kf_create's, answered before any device call. */
+int fbsmi_kfs_create(const fbsmi_kfs_model* model, int32_t nsamples, fbsmi_kfs** out);
+void fbsmi_kfs_destroy(fbsmi_kfs* h);
+/* keys (B, 2), y0 (dv): the observation paths are the handle's own front's, as in fbsmi_kf_sample (and refused alike for a
+ * model without F, sqQ).  paths (B, T+1, du); loglik (B) nullable. */
+int fbsmi_kfs_sample(fbsmi_kfs* h, const uint32_t* keys, const float* y0, float* paths, float* loglik, void* stream);
+/* The same draw on the caller's observation paths vs (B, T+1, dv), read in place. */
+int fbsmi_kfs_sample_on(fbsmi_kfs* h, const uint32_t* keys, const float* vs, float* paths, float* loglik, void* stream);
+/* The smoothed means E[u_k | v_0..v_T] (B, T+1, du) on the caller's vs; nothing is drawn. */
+int fbsmi_kfs_smooth(fbsmi_kfs* h, const float* vs, float* smeans, float* loglik, void* stream);
+/* State of the last call, copied to dst (nullable: only *count is set): which 0 vs (B, T+1, dv), the observation paths of
+ * the last fbsmi_kfs_sample; 1 the filter means m_k (B, T+1, du); 2 the innovations r_k (B, T, dv). */
+int fbsmi_kfs_view(fbsmi_kfs* h, int which, void* dst, int64_t* count, void* stream);
+
 /* ---- fused SMC step for score-network models (image experiments) --------------------------------
  * The three closures of experiments/imgs/inpainting.py:102-147 (and supr.py; sb_imgs/supr.py:80-127)
  * wrap ONE network evaluation on the joint image concat(u, v) per SMC step (csmc.py:142,145 evaluate it
