@@ -9,13 +9,15 @@ from . import _lib  # noqa: F401
 from .ops import PRNGKey, split  # noqa: F401
 from . import ops, sdes, samplers  # noqa: F401
 from .linear_gaussian import LinearGaussianBridge  # noqa: F401
-from .gaussian_sb import GaussianSBBridge  # noqa: F401
+from .gaussian_sb import (GaussianSBBridge, SBKalman, SBKalmanSmoother, sb_kalman_conditional_sampler,  # noqa: F401
+                          sb_kalman_path_sampler)
 from .lg_twisted import GaussianTwisted  # noqa: F401
 from .lg_csgm import GaussianCSGM  # noqa: F401
 from .lg_kalman import LGKalman, LGKalmanSmoother, kalman_conditional_sampler, kalman_path_sampler  # noqa: F401
 
 __all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "GaussianSBBridge", "GaussianTwisted", "GaussianCSGM", "LGKalman",
-           "LGKalmanSmoother", "kalman_conditional_sampler", "kalman_path_sampler", "PRNGKey", "split", "build"]
+           "LGKalmanSmoother", "kalman_conditional_sampler", "kalman_path_sampler", "SBKalman", "SBKalmanSmoother",
+           "sb_kalman_conditional_sampler", "sb_kalman_path_sampler", "PRNGKey", "split", "build"]
 
 
 def build(force: bool = False) -> str:

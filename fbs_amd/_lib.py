@@ -12,9 +12,9 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip",
-                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip", "fbsmi_bs.hip", "fbsmi_kf.hip")]
+                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip", "fbsmi_bs.hip", "fbsmi_kf.hip", "fbsmi_kf_em.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", "fbsmi_device.h"), os.path.join(_HERE, "csrc", "fbsmi_host.h"),
-                os.path.join(_HERE, "csrc", "fbsmi_em_path.h"),
+                os.path.join(_HERE, "csrc", "fbsmi_em_path.h"), os.path.join(_HERE, "csrc", "fbsmi_kf_em.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi.h"), os.path.join(_HERE, "..", "include", "fbsmi_math.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi_nn.h")]
 LIB_PATH = os.path.join(_HERE, "lib", "libfbsmi.so")
@@ -46,7 +46,7 @@ def _stale() -> bool:
 
 def _compile_and_link(force: bool) -> None:
     """One object per source file (kept under lib/obj/, recompiled only when its source or a header is newer), compiled
-    side by side, then linked: a change to one kernel file costs one compilation, not six."""
+    side by side, then linked: a change to one kernel file costs one compilation, not ten."""
     os.makedirs(_OBJ_DIR, exist_ok=True)
     hip = _hipcc()
     th = max(os.path.getmtime(h) for h in _HEADERS)
@@ -261,6 +261,8 @@ SIGNATURES = {
     "fbsmi_kf_sample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fbsmi_kf_filter": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "fbsmi_kf_view": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_i64), _vp]),
+    "fbsmi_kf_set_em_forward": (C.c_int, [_vp, C.POINTER(EMForwardStruct), _vp, _vp]),
+    "fbsmi_kfs_set_em_forward": (C.c_int, [_vp, C.POINTER(EMForwardStruct), _vp, _vp]),
     "fbsmi_kfs_create": (C.c_int, [C.POINTER(KFSModelStruct), _i32, C.POINTER(_vp)]),
     "fbsmi_kfs_destroy": (None, [_vp]),
     "fbsmi_kfs_sample": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -25,6 +25,10 @@
 //     under the next step's first phase: acc = 0, acc = fmaf(qv_i, qv_i, acc), i ascending.
 // LDS: 2 z tiles of 64 * 68 floats, r and qv tiles of 64 * 36 floats, 53 248 bytes, static.
 //
+// A model whose forward process is Euler-Maruyama (the Gaussian Schrodinger bridge; fbsmi_kf_set_em_forward) takes
+// k_kf_front_em (fbsmi_kf_em.hip) for k_kf_front<true>: x0 and the joint path of fbsmi_em_path.h, its y half written
+// reversed into vs.  That kernel is a translation unit of its own so that the kernels here compile to the code they had.
+//
 // fbsmi_kfs_* (the smoother and path sampler, further down) is built on the same pieces: a storing instantiation of k_kf
 // that writes every m_k and r_k as it goes, and k_kfs_back, the backward recursion over them in the same layout.
 #include <new>
@@ -33,6 +37,7 @@
 #include "../../include/fbsmi.h"
 #include "fbsmi_device.h"
 #include "fbsmi_host.h"
+#include "fbsmi_kf_em.h"
 
 using namespace fbsmi;
 
@@ -635,7 +640,21 @@ struct fbsmi_kf {
     int front_block = 64;   // max(du, dv) rounded up to a wave
     bool has_fwd = false;   // F, sqQ are not all-zero placeholders
     void* pool = nullptr;
+    bool em = false;        // fbsmi_kf_set_em_forward: the front of a sample call is k_kf_front_em
+    KfEmFront e{};
+    void* em_pool = nullptr;   // the prior's floats and the key slab
 };
+
+namespace {
+
+// the front launch of a sample call
+void kf_launch_front(fbsmi_kf* h, const uint32_t* keys, const float* y0, hipStream_t st) {
+    const int B = h->nsamples;
+    if (!h->em) k_kf_front<true><<<B, h->front_block, 0, st>>>(h->f, keys, y0, nullptr);
+    else kf_front_em_launch(h->e, keys, y0, B, st);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -722,17 +741,60 @@ void fbsmi_kf_destroy(fbsmi_kf* h) {
         (void)hipDeviceSynchronize();
         (void)hipFree(h->pool);
     }
+    if (h->em_pool) (void)hipFree(h->em_pool);
     delete h;
+}
+
+int fbsmi_kf_set_em_forward(fbsmi_kf* h, const fbsmi_em_forward* f, const float* x0_mean, const float* x0_chol) {
+    if (!h || !f || f->nsub < 1 || !f->M || !f->c || !f->ddt || !f->s)
+        return fail(FBSMI_ERR_ARG, "kf_set_em_forward: need a handle and forward tables with nsub >= 1");
+    if ((x0_mean == nullptr) != (x0_chol == nullptr))
+        return fail(FBSMI_ERR_ARG, "kf_set_em_forward: x0_mean and x0_chol are both null or both set");
+    if (h->has_fwd)
+        return fail(FBSMI_ERR_UNSUPPORTED, "kf_set_em_forward: the model has an exact forward transition (F, sqQ)");
+    const size_t du = h->d.du, T = h->d.T, B = h->nsamples;   // (du + dv <= 256 = kEmPathMaxD by kf_create's limits)
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_mean = take(x0_mean ? du * 4 : 0), o_chol = take(x0_chol ? du * du * 4 : 0);
+    const size_t o_keys = take((int)T > kKfEmKeysLds ? B * T * 2 * 4 : 0);
+    void* pool = nullptr;
+    if (off) {
+        FBSMI_HIP_TRY(hipMalloc(&pool, off));
+        hipError_t e = hipSuccess;
+        if (x0_mean) {
+            e = hipMemcpy((char*)pool + o_mean, x0_mean, du * 4, hipMemcpyDeviceToDevice);
+            if (e == hipSuccess) e = hipMemcpy((char*)pool + o_chol, x0_chol, du * du * 4, hipMemcpyDeviceToDevice);
+        }
+        if (e != hipSuccess) {
+            (void)hipFree(pool);
+            return fail(FBSMI_ERR_HIP, std::string("kf_set_em_forward: hipMemcpy: ") + hipGetErrorString(e));
+        }
+    }
+    if (h->em_pool) {   // set again: the launches that read the old copies are behind us
+        (void)hipDeviceSynchronize();
+        (void)hipFree(h->em_pool);
+    }
+    h->em_pool = pool;
+    KfEmFront& e = h->e;
+    e.du = h->f.du; e.dv = h->f.dv; e.T = h->f.T;
+    e.nsub = f->nsub; e.M = f->M; e.c = f->c; e.ddt = f->ddt; e.s = f->s;
+    e.x0_mean = x0_mean ? (const float*)((char*)pool + o_mean) : nullptr;
+    e.x0_chol = x0_chol ? (const float*)((char*)pool + o_chol) : nullptr;
+    e.ekeys = (int)T > kKfEmKeysLds ? (uint32_t*)((char*)pool + o_keys) : nullptr;
+    e.m_u = h->f.m_u; e.m_v = h->f.m_v; e.gain = h->f.gain; e.vs = h->f.vs; e.m0 = h->f.m0;
+    h->em = true;
+    return FBSMI_OK;
 }
 
 int fbsmi_kf_sample(fbsmi_kf* h, const uint32_t* keys, const float* y0, float* samples, float* means, float* loglik,
                     void* stream) {
     if (!h || !keys || !y0 || !samples) return fail(FBSMI_ERR_ARG, "kf_sample: null argument");
-    if (!h->has_fwd) return fail(FBSMI_ERR_UNSUPPORTED, "kf_sample: the model has no exact forward transition (F, sqQ)");
+    if (!h->has_fwd && !h->em)
+        return fail(FBSMI_ERR_UNSUPPORTED, "kf_sample: the model has no exact forward transition (F, sqQ)");
     hipStream_t st = (hipStream_t)stream;
     const KfDev& d = h->d;
     const int B = h->nsamples;
-    k_kf_front<true><<<B, h->front_block, 0, st>>>(h->f, keys, y0, nullptr);
+    kf_launch_front(h, keys, y0, st);
     k_kf<true><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(d, h->f.vs, keys, samples, means, loglik, B, KfNoStore());
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(FBSMI_ERR_HIP, std::string("kf_sample launch: ") + hipGetErrorString(e));
@@ -861,12 +923,21 @@ static int kfs_launched(const char* what) {
     return FBSMI_OK;
 }
 
+int fbsmi_kfs_set_em_forward(fbsmi_kfs* h, const fbsmi_em_forward* f, const float* x0_mean, const float* x0_chol) {
+    if (!h || !f || f->nsub < 1 || !f->M || !f->c || !f->ddt || !f->s)
+        return fail(FBSMI_ERR_ARG, "kfs_set_em_forward: need a handle and forward tables with nsub >= 1");
+    if ((x0_mean == nullptr) != (x0_chol == nullptr))
+        return fail(FBSMI_ERR_ARG, "kfs_set_em_forward: x0_mean and x0_chol are both null or both set");
+    return fbsmi_kf_set_em_forward(h->kf, f, x0_mean, x0_chol);
+}
+
 int fbsmi_kfs_sample(fbsmi_kfs* h, const uint32_t* keys, const float* y0, float* paths, float* loglik, void* stream) {
     if (!h || !keys || !y0 || !paths) return fail(FBSMI_ERR_ARG, "kfs_sample: null argument");
-    if (!h->kf->has_fwd) return fail(FBSMI_ERR_UNSUPPORTED, "kfs_sample: the model has no exact forward transition (F, sqQ)");
+    if (!h->kf->has_fwd && !h->kf->em)
+        return fail(FBSMI_ERR_UNSUPPORTED, "kfs_sample: the model has no exact forward transition (F, sqQ)");
     hipStream_t st = (hipStream_t)stream;
     const int B = h->nsamples;
-    k_kf_front<true><<<B, h->kf->front_block, 0, st>>>(h->kf->f, keys, y0, nullptr);
+    kf_launch_front(h->kf, keys, y0, st);
     kfs_forward<true>(h, h->kf->f.vs, keys, loglik, st);
     k_kfs_back<true><<<(B + kKfTile - 1) / kKfTile, kBlock, 0, st>>>(h->bd, keys, paths, B);
     return kfs_launched("kfs_sample");

@@ -9,6 +9,12 @@ Euler-Maruyama with ``nsub`` sub-steps per interval (sb/gibbs.py:137-139).  The 
 
 so the CSMC part of a sweep and the particle filters run on the fused engine's affine tables unchanged; the forward
 paths take the Euler-Maruyama kernel (include/fbsmi.h, fbsmi_em_forward) on the tables of ``sb_tables``.
+
+The discretised reverse model is linear-Gaussian like the analytic one, so its filtering and smoothing laws and its marginal
+likelihood are closed-form on ``lg_kalman_tables`` of the same G, g, sd, dt: ``sb_kalman_model`` / ``SBKalman`` /
+``sb_kalman_conditional_sampler`` and ``sb_kalman_smoother_model`` / ``SBKalmanSmoother`` / ``sb_kalman_path_sampler`` are the
+exact yardsticks of the SB filter sampler, on the observation paths that sampler draws from the same keys
+(include/fbsmi.h, fbsmi_kf_set_em_forward).
 """
 from __future__ import annotations
 
@@ -18,6 +24,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .lg_kalman import (KF_PATH_ELEMS, LGKalman, LGKalmanSmoother, _conditional_chunks, _kf_struct, _kfs_struct,
+                        _path_chunks)
 from .linear_gaussian import LGFilter, LGFilterSampler, LinearGaussianBridge
 from .sdes.linear import make_gaussian_bw_sb
 
@@ -118,6 +126,26 @@ class GaussianSBBridge(LinearGaussianBridge):
                 None if prior is None else (prior[0].tobytes(), prior[1].tobytes()))
         return self._cached(keyt, lambda: SBFilterSampler(self, int(nparticles), resampling, int(nsamples), prior))
 
+    # -- exact Kalman sampler and smoother (fbs_amd/lg_kalman.py on this model's tables) ----------------
+    def _prior32(self, x0_prior):
+        """x0_prior as contiguous float32 (mean (du), chol_lower (du, du)) and its part of a cache key."""
+        if x0_prior is None:
+            return None, None
+        prior = (np.ascontiguousarray(np.asarray(x0_prior[0], np.float32).reshape(self.du)),
+                 np.ascontiguousarray(np.asarray(x0_prior[1], np.float32).reshape(self.du, self.du)))
+        return prior, (prior[0].tobytes(), prior[1].tobytes())
+
+    def sb_kalman_handle(self, nsamples: int = 1, x0_prior=None):
+        """The fused Kalman-filter conditional sampler (SBKalman) for `nsamples` samples per call; x0_prior as in
+        sb_filter_sampler_handle.  Cached on the bridge by the size and the prior's float32 bytes."""
+        prior, pk = self._prior32(x0_prior)
+        return self._cached(("sb_kalman", int(nsamples), pk), lambda: SBKalman(self, int(nsamples), prior))
+
+    def sb_kalman_smoother_handle(self, nsamples: int = 1, x0_prior=None):
+        """The fused Kalman smoother and path sampler (SBKalmanSmoother) for `nsamples` paths per call, cached likewise."""
+        prior, pk = self._prior32(x0_prior)
+        return self._cached(("sb_kalman_smoother", int(nsamples), pk), lambda: SBKalmanSmoother(self, int(nsamples), prior))
+
 
 class SBFilterSampler(LGFilterSampler):
     """Owns one fbsmi_lg_fsamp handle made by fbsmi_lg_fsamp_create_em: the bootstrap-filter conditional sampler of
@@ -140,3 +168,92 @@ class SBFilterSampler(LGFilterSampler):
 
     def _of_size(self, B):
         return self.model.sb_filter_sampler_handle(self.n, self.resampling, B, self.prior)
+
+
+# ---- the exact Kalman sampler and smoother of the SB toy (include/fbsmi.h, fbsmi_kf_set_em_forward) ---------------------
+def _need_sb(bridge, what):
+    if not isinstance(bridge, GaussianSBBridge):
+        raise NotImplementedError(f"{what} takes a GaussianSBBridge (an Euler-Maruyama forward process); a "
+                                  f"{type(bridge).__name__} such as LinearGaussianBridge has the entry point without sb_")
+
+
+def sb_kalman_model(bridge: GaussianSBBridge):
+    """The SB bridge's Kalman tables -- lg_kalman_tables(bridge.tables64, bridge.pmcmc_tables_host(None),
+    initial_cov(bridge.cov1, du)) -- as host float64 (``tables64``), host float32 (``host``) and an fbsmi_kf_model struct
+    whose F, sqQ are the model's all-zero placeholders; built once and cached on the bridge."""
+    _need_sb(bridge, "sb_kalman_model")
+    return bridge._cached(("sb_kalman_model",), lambda: _kf_struct(bridge))
+
+
+def sb_kalman_smoother_model(bridge: GaussianSBBridge):
+    """lg_smoother_tables on top of sb_kalman_model as an fbsmi_kfs_model struct, built once and cached on the bridge."""
+    kf = sb_kalman_model(bridge)
+    return bridge._cached(("sb_kalman_smoother_model",), lambda: _kfs_struct(bridge, kf))
+
+
+class _SBFront:
+    """What SBKalman and SBKalmanSmoother add to their base classes: the prior, and the Euler-Maruyama front set on the
+    library's handle once it exists (``_SET`` names the entry of libfbsmi)."""
+
+    _SET = None
+
+    def _set_front(self, model, x0_prior):
+        self.prior = x0_prior
+        self._prior_dev = None if x0_prior is None else tuple(torch.from_numpy(a).to(model.device) for a in x0_prior)
+        mean, chol = (None, None) if self._prior_dev is None else (t.data_ptr() for t in self._prior_dev)
+        with torch.cuda.device(model.device):
+            _lib.call(self._SET, self.h, C.byref(model.em_struct), mean, chol)
+
+
+class SBKalman(_SBFront, LGKalman):
+    """LGKalman on a GaussianSBBridge: sample() draws each observation path as SBFilterSampler does on the same key (x0,
+    the joint Euler-Maruyama path, the reversal of its y half), then runs the exact filter and the draw; filter() and
+    views() are LGKalman's.  A ragged call runs on the bridge's handle of that size and the same prior."""
+
+    _SET = "fbsmi_kf_set_em_forward"
+
+    def __init__(self, model: GaussianSBBridge, nsamples=1, x0_prior=None):
+        _need_sb(model, "SBKalman")
+        LGKalman.__init__(self, model, nsamples)
+        self._set_front(model, x0_prior)
+
+    def _struct_of(self, model):
+        return sb_kalman_model(model)
+
+    def _of_size(self, B):
+        return self.model.sb_kalman_handle(B, self.prior)
+
+
+class SBKalmanSmoother(_SBFront, LGKalmanSmoother):
+    """LGKalmanSmoother on a GaussianSBBridge: sample() on the observation paths of SBKalman.sample; sample_on(), smooth()
+    and views() are LGKalmanSmoother's."""
+
+    _SET = "fbsmi_kfs_set_em_forward"
+
+    def __init__(self, model: GaussianSBBridge, nsamples=1, x0_prior=None):
+        _need_sb(model, "SBKalmanSmoother")
+        LGKalmanSmoother.__init__(self, model, nsamples)
+        self._set_front(model, x0_prior)
+
+    def _struct_of(self, model):
+        return sb_kalman_smoother_model(model)
+
+    def _of_size(self, B):
+        return self.model.sb_kalman_smoother_handle(B, self.prior)
+
+
+def sb_kalman_conditional_sampler(keys, y0, bridge, x0_prior=None, return_moments=False, _bound=KF_PATH_ELEMS):
+    """The Kalman-filter conditional sampler for every key of `keys` (B, 2) [or (2,)] on a GaussianSBBridge, each on the
+    observation path sb_filter_conditional_sampler draws from that key: -> samples (B, du) [, filtering means (B, du),
+    exact log-likelihoods log p(v_1..v_T | v_0) (B)].  x0_prior = (mean, chol_lower) ('proper') or None ('heuristic').
+    The batch runs in chunks that keep one call's B * (T + 1) * dv within `_bound` elements."""
+    _need_sb(bridge, "sb_kalman_conditional_sampler")
+    return _conditional_chunks(keys, y0, bridge, lambda B: bridge.sb_kalman_handle(B, x0_prior), return_moments, _bound)
+
+
+def sb_kalman_path_sampler(keys, y0, bridge, x0_prior=None, return_moments=False, _bound=KF_PATH_ELEMS):
+    """The forward-filter / backward-sampler for every key of `keys` on a GaussianSBBridge: exact draws from
+    p(u_0..u_T | v_0..v_T) on each key's own observation path -> paths (B, T+1, du) [, smoothed means (B, T+1, du), exact
+    log-likelihoods (B)]; paths[:, T] is sb_kalman_conditional_sampler's draw on the same keys."""
+    _need_sb(bridge, "sb_kalman_path_sampler")
+    return _path_chunks(keys, y0, bridge, lambda B: bridge.sb_kalman_smoother_handle(B, x0_prior), return_moments, _bound)

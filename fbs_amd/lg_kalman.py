@@ -20,6 +20,10 @@ The smoothing law ``p(u_0..u_T | v_0..v_T)`` of the same model is Gaussian too: 
 gains and factors, ``kalman_smoother_np`` is the float64 Rauch-Tung-Striebel recursion and backward sampler, and
 ``LGKalmanSmoother`` / ``kalman_path_sampler`` own the fused, batched engine (fbsmi_kfs_*): exact whole-path draws and
 smoothed means, the yardstick of the particle engines that produce paths.
+
+The Gaussian Schrodinger-bridge toy has the same engines under names of its own (fbs_amd/gaussian_sb.py: ``sb_kalman_model``,
+``SBKalman``, ``SBKalmanSmoother``, ``sb_kalman_conditional_sampler``, ``sb_kalman_path_sampler``); the entry points here
+keep refusing a GaussianSBBridge.
 """
 from __future__ import annotations
 
@@ -185,27 +189,30 @@ def plan_kalman_chunks(nkeys: int, T: int, dv: int, bound: int = KF_PATH_ELEMS, 
 _ARRAYS = ("H", "e", "Pm", "c", "AK", "W", "lconst", "Lt")
 
 
+def _kf_struct(bridge):
+    """lg_kalman_tables of a bridge's per-step tables and terminal moments as an fbsmi_kf_model struct with its host
+    float64 (``tables64``) and float32 (``host``) copies."""
+    pm = bridge.pmcmc_tables_host(None)
+    kt = lg_kalman_tables(bridge.tables64, pm, initial_cov(bridge.terminal_moments()[1], bridge.du))
+    host = {k: np.ascontiguousarray(np.asarray(kt[k], np.float32)) for k in _ARRAYS}
+    dev = {k: torch.from_numpy(v).to(bridge.device) for k, v in host.items()}
+    for k in ("m_u", "m_v", "gain"):
+        dev[k] = torch.from_numpy(np.ascontiguousarray(kt[k])).to(bridge.device)
+    st = _lib.KFModelStruct(bridge.du, bridge.dv, bridge.T, *(dev[k].data_ptr() for k in _ARRAYS),
+                            bridge.dev["F"].data_ptr(), bridge.dev["sqQ"].data_ptr(),
+                            dev["m_u"].data_ptr(), dev["m_v"].data_ptr(), dev["gain"].data_ptr())
+    st._keep, st.host, st.tables64 = dev, host, kt
+    return st
+
+
 def kalman_model(bridge: LinearGaussianBridge):
     """The bridge's Kalman tables: host float64 (``tables64``), host float32 (``host``) and the device copies as an
     fbsmi_kf_model struct, built once and cached on the bridge."""
     if type(bridge) is not LinearGaussianBridge or getattr(bridge, "em_struct", None) is not None or bridge.sde is None:
         raise NotImplementedError("the Kalman conditional sampler is built for LinearGaussianBridge (an exact forward "
-                                  "transition and terminal moments); GaussianSBBridge is out of scope")
-
-    def make():
-        pm = bridge.pmcmc_tables_host(None)
-        kt = lg_kalman_tables(bridge.tables64, pm, initial_cov(bridge.terminal_moments()[1], bridge.du))
-        host = {k: np.ascontiguousarray(np.asarray(kt[k], np.float32)) for k in _ARRAYS}
-        dev = {k: torch.from_numpy(v).to(bridge.device) for k, v in host.items()}
-        for k in ("m_u", "m_v", "gain"):
-            dev[k] = torch.from_numpy(np.ascontiguousarray(kt[k])).to(bridge.device)
-        st = _lib.KFModelStruct(bridge.du, bridge.dv, bridge.T, *(dev[k].data_ptr() for k in _ARRAYS),
-                                bridge.dev["F"].data_ptr(), bridge.dev["sqQ"].data_ptr(),
-                                dev["m_u"].data_ptr(), dev["m_v"].data_ptr(), dev["gain"].data_ptr())
-        st._keep, st.host, st.tables64 = dev, host, kt
-        return st
-
-    return bridge._cached(("kalman_model",), make)
+                                  "transition and terminal moments); GaussianSBBridge is out of scope (its engines are "
+                                  "fbs_amd.gaussian_sb's sb_kalman_model, SBKalman, SBKalmanSmoother)")
+    return bridge._cached(("kalman_model",), lambda: _kf_struct(bridge))
 
 
 class LGKalman(_LGHandle):
@@ -216,13 +223,21 @@ class LGKalman(_LGHandle):
     _DESTROY = "fbsmi_kf_destroy"
 
     def __init__(self, model: LinearGaussianBridge, nsamples=1):
-        self.struct = kalman_model(model)
+        self.struct = self._struct_of(model)
         self.model, self.C = model, int(nsamples)
         self._last = self
         h = C.c_void_p()   # sizes the engine does not take are refused by the library, with its message
         with torch.cuda.device(model.device):
             _lib.call("fbsmi_kf_create", C.byref(self.struct), self.C, C.byref(h))
         self.h = h
+
+    def _struct_of(self, model):
+        """The model's fbsmi_kf_model struct."""
+        return kalman_model(model)
+
+    def _of_size(self, B):
+        """The model's cached handle of this one's kind for B samples per call."""
+        return self.model.kalman_handle(B)
 
     @property
     def cov_T(self):
@@ -232,7 +247,7 @@ class LGKalman(_LGHandle):
     def _route(self, B):
         if not 1 <= B <= self.C:
             raise ValueError(f"{B} samples for a handle of {self.C}")
-        self._last = self if B == self.C else self.model.kalman_handle(B)
+        self._last = self if B == self.C else self._of_size(B)
         return self._last
 
     def sample(self, keys, y0, return_moments=False):
@@ -284,12 +299,18 @@ def kalman_conditional_sampler(keys, y0, bridge, return_moments=False, _bound=KF
     -> samples (B, du) [, filtering means (B, du), exact log-likelihoods log p(v_1..v_T | v_0) (B)].  Each sample depends
     on its own key only; the batch runs in chunks that keep one call's B * (T + 1) * dv within `_bound` elements."""
     if type(bridge) is not LinearGaussianBridge:
-        raise NotImplementedError("kalman_conditional_sampler takes a LinearGaussianBridge; GaussianSBBridge is out of scope")
+        raise NotImplementedError("kalman_conditional_sampler takes a LinearGaussianBridge; GaussianSBBridge is out of scope "
+                                  "(sb_kalman_conditional_sampler serves it)")
+    return _conditional_chunks(keys, y0, bridge, bridge.kalman_handle, return_moments, _bound)
+
+
+def _conditional_chunks(keys, y0, bridge, handle_of, return_moments, bound):
+    """The chunked batch of a conditional sampler: handle_of(B) is the bridge's handle for B samples per call."""
     k = np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys).astype(np.uint32).reshape(-1, 2)
-    chunks = plan_kalman_chunks(k.shape[0], bridge.T, bridge.dv, _bound)
+    chunks = plan_kalman_chunks(k.shape[0], bridge.T, bridge.dv, bound)
     if chunks is None:
         raise NotImplementedError("one observation path alone exceeds the bound of a fused call")
-    outs = [bridge.kalman_handle(b - a).sample(k[a:b], y0, return_moments=True) for a, b in chunks]
+    outs = [handle_of(b - a).sample(k[a:b], y0, return_moments=True) for a, b in chunks]
     samples, means, ll = (torch.cat([o[i] for o in outs]) for i in range(3))
     return (samples, means, ll) if return_moments else samples
 
@@ -309,16 +330,17 @@ def kalman_smoother_model(bridge: LinearGaussianBridge):
     """The bridge's smoother tables: host float64 (``tables64``, with cov_s and cross), host float32 (``host``) and the
     device copies as an fbsmi_kfs_model struct on top of kalman_model's, built once and cached on the bridge."""
     kf = kalman_model(bridge)
+    return bridge._cached(("kalman_smoother_model",), lambda: _kfs_struct(bridge, kf))
 
-    def make():
-        st64 = lg_smoother_tables(bridge.tables64, kf.tables64)
-        host = {k: np.ascontiguousarray(np.asarray(st64[k], np.float32)) for k in _S_ARRAYS}
-        dev = {k: torch.from_numpy(v).to(bridge.device) for k, v in host.items()}
-        st = _lib.KFSModelStruct(C.pointer(kf), *(dev[k].data_ptr() for k in _S_ARRAYS))
-        st._keep, st.host, st.tables64, st.kf_struct = dev, host, st64, kf
-        return st
 
-    return bridge._cached(("kalman_smoother_model",), make)
+def _kfs_struct(bridge, kf):
+    """lg_smoother_tables of a bridge on top of its fbsmi_kf_model struct `kf`, as an fbsmi_kfs_model struct."""
+    st64 = lg_smoother_tables(bridge.tables64, kf.tables64)
+    host = {k: np.ascontiguousarray(np.asarray(st64[k], np.float32)) for k in _S_ARRAYS}
+    dev = {k: torch.from_numpy(v).to(bridge.device) for k, v in host.items()}
+    st = _lib.KFSModelStruct(C.pointer(kf), *(dev[k].data_ptr() for k in _S_ARRAYS))
+    st._keep, st.host, st.tables64, st.kf_struct = dev, host, st64, kf
+    return st
 
 
 class LGKalmanSmoother(_LGHandle):
@@ -330,13 +352,21 @@ class LGKalmanSmoother(_LGHandle):
     _DESTROY = "fbsmi_kfs_destroy"
 
     def __init__(self, model: LinearGaussianBridge, nsamples=1):
-        self.struct = kalman_smoother_model(model)
+        self.struct = self._struct_of(model)
         self.model, self.C = model, int(nsamples)
         self._last = self
         h = C.c_void_p()
         with torch.cuda.device(model.device):
             _lib.call("fbsmi_kfs_create", C.byref(self.struct), self.C, C.byref(h))
         self.h = h
+
+    def _struct_of(self, model):
+        """The model's fbsmi_kfs_model struct."""
+        return kalman_smoother_model(model)
+
+    def _of_size(self, B):
+        """The model's cached handle of this one's kind for B paths per call."""
+        return self.model.kalman_smoother_handle(B)
 
     @property
     def cov_s(self):
@@ -346,7 +376,7 @@ class LGKalmanSmoother(_LGHandle):
     def _route(self, B):
         if not 1 <= B <= self.C:
             raise ValueError(f"{B} samples for a handle of {self.C}")
-        self._last = self if B == self.C else self.model.kalman_smoother_handle(B)
+        self._last = self if B == self.C else self._of_size(B)
         return self._last
 
     def _out(self, B, loglik):
@@ -422,14 +452,20 @@ def kalman_path_sampler(keys, y0, bridge, return_moments=False, _bound=KF_PATH_E
     from p(u_0..u_T | v_0..v_T) on each key's own observation path -> paths (B, T+1, du) [, smoothed means (B, T+1, du),
     exact log-likelihoods (B)].  The batch runs in chunks that keep every per-call buffer within `_bound` elements."""
     if type(bridge) is not LinearGaussianBridge:
-        raise NotImplementedError("kalman_path_sampler takes a LinearGaussianBridge; GaussianSBBridge is out of scope")
+        raise NotImplementedError("kalman_path_sampler takes a LinearGaussianBridge; GaussianSBBridge is out of scope "
+                                  "(sb_kalman_path_sampler serves it)")
+    return _path_chunks(keys, y0, bridge, bridge.kalman_smoother_handle, return_moments, _bound)
+
+
+def _path_chunks(keys, y0, bridge, handle_of, return_moments, bound):
+    """The chunked batch of a path sampler: handle_of(B) is the bridge's smoother handle for B paths per call."""
     k = np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys).astype(np.uint32).reshape(-1, 2)
-    chunks = plan_smoother_chunks(k.shape[0], bridge.T, bridge.du, bridge.dv, _bound)
+    chunks = plan_smoother_chunks(k.shape[0], bridge.T, bridge.du, bridge.dv, bound)
     if chunks is None:
         raise NotImplementedError("one path alone exceeds the bound of a fused call")
     paths, means, lls = [], [], []
     for a, b in chunks:
-        h = bridge.kalman_smoother_handle(b - a)
+        h = handle_of(b - a)
         p, ll = h.sample(k[a:b], y0, return_loglik=True)
         paths.append(p)
         lls.append(ll)

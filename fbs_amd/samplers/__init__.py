@@ -4,3 +4,4 @@ from .smc import (bootstrap_filter, filter_conditional_sampler, pmcmc_chain, pmc
 from .resampling import multinomial, systematic, stratified, killing
 from .gibbs import gibbs_init, gibbs_kernel
 from ..lg_kalman import kalman_conditional_sampler, kalman_path_sampler
+from ..gaussian_sb import sb_kalman_conditional_sampler, sb_kalman_path_sampler

@@ -570,6 +570,18 @@ int fbsmi_kf_filter(fbsmi_kf* h, const float* vs, float* means, float* loglik, v
 /* State of the last call, copied to dst (nullable: only *count is set): which 0 vs (B, T+1, dv), the observation paths
  * of the last fbsmi_kf_sample; 1 m_ (B, du), the initial means m_0 of the last call of either kind. */
 int fbsmi_kf_view(fbsmi_kf* h, int which, void* dst, int64_t* count, void* stream);
+/* A model whose forward process is Euler-Maruyama (the Gaussian Schrodinger bridge, experiments/sb/filter.py:137-148): its
+ * discretised reverse model is linear-Gaussian like the analytic one, so lg_kalman_tables applies to its G, g, sd, dt and
+ * fbsmi_kf_create takes the all-zero F, sqQ placeholders; fbsmi_kf_filter serves such a handle as it is.  After this call
+ * fbsmi_kf_sample serves it too: the front launch is the front of fbsmi_lg_fsamp_create_em, exactly its "keys" (key_fwd,
+ * key_x0, key_em), "x0" and "forward path" lines -- the same keys give the same vs, bit for bit -- and m_0, the step, the
+ * sample line (key_kf = split(key, 3)[2]) and the outputs are those of fbsmi_kf_sample above.  `fwd` covers the handle's T
+ * and D = du + dv and must outlive it; x0_mean (du) and x0_chol (du, du), the LOWER factor, are device float32 arrays, both
+ * null for x0 ~ N(0, I) ('heuristic') or both set ('proper'): the handle copies them, and for T > 1024 allocates the
+ * (B, T, 2) interval keys.  FBSMI_ERR_ARG (before any device call) for a null handle or fwd, a null array in fwd,
+ * fwd->nsub < 1, and exactly one of x0_mean / x0_chol null; FBSMI_ERR_UNSUPPORTED for a handle whose F, sqQ are not all
+ * zero (it has an exact forward transition).  Without this call fbsmi_kf_sample answers such a handle as before. */
+int fbsmi_kf_set_em_forward(fbsmi_kf* h, const fbsmi_em_forward* fwd, const float* x0_mean, const float* x0_chol);
 
 /* ---- batched, device-resident Kalman smoother and path sampler for the analytic model ---------------
  * The exact counterpart of fbsmi_lg_backsim, as fbsmi_kf is of fbsmi_lg_fsamp: the smoothing law
@@ -618,6 +630,9 @@ int fbsmi_kfs_smooth(fbsmi_kfs* h, const float* vs, float* smeans, float* loglik
 /* State of the last call, copied to dst (nullable: only *count is set): which 0 vs (B, T+1, dv), the observation paths of
  * the last fbsmi_kfs_sample; 1 the filter means m_k (B, T+1, du); 2 the innovations r_k (B, T, dv). */
 int fbsmi_kfs_view(fbsmi_kfs* h, int which, void* dst, int64_t* count, void* stream);
+/* fbsmi_kf_set_em_forward on the smoother's filter handle, with its checks and answers: afterwards fbsmi_kfs_sample draws
+ * the observation paths by the Euler-Maruyama front (noise xi from key_bwd = split(key, 3)[1], as above). */
+int fbsmi_kfs_set_em_forward(fbsmi_kfs* h, const fbsmi_em_forward* fwd, const float* x0_mean, const float* x0_chol);
 
 /* ---- fused SMC step for score-network models (image experiments) --------------------------------
  * The three closures of experiments/imgs/inpainting.py:102-147 (and supr.py; sb_imgs/supr.py:80-127)
