@@ -1381,7 +1381,9 @@ __global__ void __launch_bounds__(kBlock) k_lg_propQ(LgDev dd, int s) {
 //   Cat(w) per slot: top levels + three levels of every tile in LDS, then (killed slots only) three levels from the
 //   tile's published heap in one round trip and the last four leaves of w in another.
 // Workgroups: k_lg_prop1t, one tile each (a single chain, pinned launches, N = 2^k + 1); k_lg_prop1th, two or four tiles N/2
-// apart, the trees built once by the first 256 threads and the noise drawn once per pair of slots by the others meanwhile,
+// apart, the noise drawn once per pair of slots by the upper waves while the lower ones build: wave 0 finds J out of its own
+// registers, wave 1 builds the top of the w tree, waves 2-3 stage the tiles' levels, one barrier (tree_build_roles;
+// FBSMI_J_WAVE=0: the first 256 threads build everything through LDS heaps, tree_build_shared) --
 // a pair's two slots in lanes l and l + 32 of one wave so that the kill-test and redraw draws are also made once per pair
 // (from two tiles per CU on; k_lg_prop1tp, a pair's slots in two waves and those draws per slot, under
 // FBSMI_PROP_HALFWAVE=0); k_lg_prop2t, two slots N/2 apart per thread (from five tiles per CU on).
@@ -1447,7 +1449,8 @@ struct TreeLds {
     __attribute__((aligned(16))) float2 midW[kMidN * kBlock];
 };
 
-constexpr int kTreeBuildBarriers = 4;   // __syncthreads() executed by tree_build (two up-sweep exchanges, two explicit)
+constexpr int kTreeBuildBarriers = 4;   // __syncthreads() executed by tree_build (two up-sweep exchanges, two explicit): what the
+                                        // waiting waves of tree_build_shared execute as dummies (tree_build_roles has none)
 
 // Builds the heaps and finds J = choice(key_3, N, (), p=J_prob) (resamplings.py:84), the same in every thread;
 // `last` = cdf[N - 1], `rootW` = the canonical inclusive prefix at the end of the power-of-two part (== last unless N = 2^k + 1).
@@ -1661,6 +1664,218 @@ __device__ __forceinline__ int tree_build_shared(const LgDev& d, const TreeEntry
     return Jsh;
 }
 
+// ------------------------------------------------------------------------------------------
+// tree_build_roles: tree_build_shared with the work dealt out by wave and ONE workgroup barrier (k_lg_prop1th; powers of two
+// only).  J is a search that is uniform over the workgroup and touches one node per level, so one wave can make it out of
+// its own registers: wave 0 holds the 256 leaves of a tree four per lane (leaves 4 * lane .. 4 * lane + 3), takes levels 0-1
+// inside the lane and levels 2-7 with the butterfly of wave_upsweep -- the same additions in the same association as the
+// four-wave up-sweep of tree_build, as in the one-wave-per-tile form of k_lg_norm -- and reads the nodes along the walk by
+// lane (v_readlane with a uniform lane index) where tree_build writes a 256-node heap to LDS and reads it back.  Neither heap
+// of J_prob exists here (no L.topJ, no L.tileJ, no L.bc, no L.xch), and wave 0 meets no barrier before the closing one.
+// Wave 1 up-sweeps the tile sums of w, writes L.topW and `last`; waves 2-3 stage trWtop into L.midW; the other waves (the noise
+// draws of k_lg_prop1th) go straight to the closing barrier.  (With the w side left on wave 0, behind J, and the staging on
+// waves 0-3 as in tree_build, the step was no faster than tree_build_shared: DESIGN 5.00001.)
+// ------------------------------------------------------------------------------------------
+struct WaveTree {
+    float x[4];       // leaves 4 * lane .. 4 * lane + 3
+    float s01, s23;   // level 0
+    TreePath p;       // ls / own [0..5]: tree levels 2..7
+};
+
+__device__ __forceinline__ float wave_tree_upsweep(WaveTree& t) {
+    t.s01 = t.x[0] + t.x[1];
+    t.s23 = t.x[2] + t.x[3];
+    return wave_upsweep(t.s01 + t.s23, t.p);
+}
+
+// v of lane l (l uniform over the wave)
+__device__ __forceinline__ float lane_read(float v, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+__device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the sum of the 2^(k + 2) leaves in front of this lane's four, k = the lowest set bit of the lane (lane >= 1): the left half
+// of the node whose midpoint is leaf 4 * lane (tree_left_sum for four leaves per lane)
+__device__ __forceinline__ float wave_tree_left_sum(const TreePath p, int lane) {   // by value, as tree_left_sum
+    float v = p.ls[5];
+    v = (lane & 16) ? p.ls[4] : v;
+    v = (lane & 8) ? p.ls[3] : v;
+    v = (lane & 4) ? p.ls[2] : v;
+    v = (lane & 2) ? p.ls[1] : v;
+    v = (lane & 1) ? p.ls[0] : v;
+    return v;
+}
+
+// node [lo, lo + 2^(C + 1)) of a WaveTree (lo uniform): the sum of its left half, out of the record of level C of the lane that
+// holds its midpoint (a lane of the right half: its sibling block is the left half), and the value y of the leaf at its midpoint
+template <int C>
+__device__ __forceinline__ float wave_tree_half(const WaveTree& t, int lo) {
+    const int ml = (lo + (1 << C)) >> 2;
+    if constexpr (C >= 2) return lane_read(t.p.ls[C - 2], ml);
+    else if constexpr (C == 1) return lane_read(t.s01, ml);
+    else return (lo & 2) ? lane_read(t.x[2], ml) : lane_read(t.x[0], ml);   // (a select between the leaves themselves becomes
+}                                                                           // an indexed load from scratch memory)
+template <int C>
+__device__ __forceinline__ float wave_tree_mid(const float (&y)[4], int lo) {
+    const int ml = (lo + (1 << C)) >> 2;
+    if constexpr (C >= 2) return lane_read(y[0], ml);
+    else if constexpr (C == 1) return lane_read(y[2], ml);
+    else return (lo & 2) ? lane_read(y[3], ml) : lane_read(y[1], ml);
+}
+
+// four consecutive per-tile values of this lane (0 behind tile nb - 1).  Two tiles: a chain's part of the buffer is only 8-byte aligned.
+__device__ __forceinline__ float4 tile_values4(const float* p, int nb, int lane) {
+    const int t = 4 * lane;
+    if (nb >= 4) return t < nb ? *reinterpret_cast<const float4*>(p + t) : make_float4(0.f, 0.f, 0.f, 0.f);
+    return make_float4(t < nb ? p[t] : 0.0f, t + 1 < nb ? p[t + 1] : 0.0f, 0.f, 0.f);
+}
+
+// What the J wave loads at the kernel's entry, ahead of the noise draws.  Waves 1-3 have nothing else to do before the barrier
+// and take no part in the draws, so they load where they work (tree_build_roles) and hold no registers across the code in
+// between.
+struct RoleEntry {
+    float4 sj, wf;          // sums of J_prob ([i*] = 0) and the first w of the lane's four tiles
+    float refsib[8];        // sibling sums of the leaf i* in its tile's J_prob tree (published by k_lg_norm)
+};
+
+// Returns (by value, like every record that must stay in registers) the J wave's four w of the tile of i*: the tile J falls in
+// whenever J == i* (see wave_tree_J).
+__device__ __forceinline__ float4 role_entry_loads(const LgDev& d, int i_ref, RoleEntry& e) {
+    const int tid = threadIdx.x, nb = d.nb;
+    float4 wref = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tid < 64) {
+        e.sj = tile_values4(d.bsumJ, nb, tid);
+        e.wf = tile_values4(d.wfirst, nb, tid);
+        wref = *reinterpret_cast<const float4*>(d.w + i_ref / kBlock * kBlock + 4 * tid);
+#pragma unroll
+        for (int lv = 0; lv < 8; ++lv) e.refsib[lv] = d.scal[4 + lv];
+    }
+    return wref;
+}
+
+// the w side of tree_build by one wave: L.topW and `last` = cdf[N - 1] = the root of the w tree
+__device__ __forceinline__ float wave_tree_w_side(float4 sw, float4 wf, TreeLds& L) {
+    const int lane = threadIdx.x & 63;
+    WaveTree t;
+    t.x[0] = sw.x; t.x[1] = sw.y; t.x[2] = sw.z; t.x[3] = sw.w;
+    const float total = wave_tree_upsweep(t);
+    const int t0 = 4 * lane;
+    if (lane) L.topW[tree_mid_node(t0)] = make_float2(wave_tree_left_sum(t.p, lane), wf.x);
+    L.topW[tree_mid_node(t0 + 1)] = make_float2(t.x[0], wf.y);
+    L.topW[tree_mid_node(t0 + 2)] = make_float2(t.s01, wf.z);
+    L.topW[tree_mid_node(t0 + 3)] = make_float2(t.x[2], wf.w);
+    return total;
+}
+
+// J = choice(key_3, N, (), p=J_prob) by one whole wave, every step and every value as in tree_build (!plus1)
+__device__ __forceinline__ int wave_tree_J(const LgDev& d, const RoleEntry& e, const float4 wref, int i_ref, float u3, float w_max,
+                                           float inv_n) {
+    const int lane = threadIdx.x & 63, nb = d.nb;
+    i_ref = wave_uniform(i_ref);
+    const int b_ref = i_ref / kBlock, lb = b_ref >> 2;
+    // ---- the tree over the tiles: sums of J_prob with [i*] = 0; the leaves at the midpoints, the four divisions side by side
+    WaveTree t;
+    t.x[0] = e.sj.x; t.x[1] = e.sj.y; t.x[2] = e.sj.z; t.x[3] = e.sj.w;
+    const float wf[4] = {e.wf.x, e.wf.y, e.wf.z, e.wf.w};
+    float jq[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) jq[i] = jprob_pow2(wf[i], w_max, inv_n);
+    const float total = wave_tree_upsweep(t);
+    const float Ji = fmaxf(1.0f - total, 0.0f);    // J_prob[i*] (resamplings.py:80-82)
+    float jf[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) jf[i] = (4 * lane + i) * kBlock == i_ref ? Ji : (4 * lane + i < nb ? jq[i] : 0.0f);
+    // the tile that holds i*: its leaf changes from 0 to Ji, so the tile's sum is redone along the leaf's path, and so is the
+    // tree over the tiles along the path of leaf b_ref, whose sibling sums are in the records of the lane that holds it
+    const float tile_ref = tree_fold(Ji, e.refsib);
+    float bsib[8];
+    {
+        const int pos = b_ref & 3;
+        const float s0 = (pos & 2) ? ((pos & 1) ? t.x[2] : t.x[3]) : ((pos & 1) ? t.x[0] : t.x[1]);
+        bsib[0] = lane_read(s0, lb);
+        bsib[1] = lane_read((pos & 2) ? t.s01 : t.s23, lb);
+        bsib[2] = lane_read(t.p.ls[0], lb); bsib[3] = lane_read(t.p.ls[1], lb); bsib[4] = lane_read(t.p.ls[2], lb);
+        bsib[5] = lane_read(t.p.ls[3], lb); bsib[6] = lane_read(t.p.ls[4], lb); bsib[7] = lane_read(t.p.ls[5], lb);
+    }
+    const float rootJ = tree_fold(tile_ref, bsib);   // == cdfJ[N - 1]
+    // ---- the walk over the tiles.  Node [lo, lo + 2^(c+1)): the sum of its left half is in the record of level c of any
+    // lane of its right half (the lane of the midpoint here), or the fold of the new leaf when the half holds b_ref
+    const float q = rootJ * (1.0f - u3);
+    const int top_levels = 31 - __builtin_clz(nb);
+    float P = 0.0f, E = rootJ;
+    int lo = 0;
+#define FBSMI_JTOP_LEVEL(C)                                                                 \
+    if (C < top_levels) {                                                                   \
+        const int mid = lo + (1 << C);                                                      \
+        float left = wave_tree_half<C>(t, lo);                                              \
+        if (b_ref >= lo && b_ref < mid) left = tree_fold(tile_ref, bsib, C);                \
+        lo = wave_uniform(tree_walk(make_float2(left, wave_tree_mid<C>(jf, lo)), q, P, E) ? lo : mid); \
+    }
+    FBSMI_JTOP_LEVEL(7) FBSMI_JTOP_LEVEL(6) FBSMI_JTOP_LEVEL(5) FBSMI_JTOP_LEVEL(4)
+    FBSMI_JTOP_LEVEL(3) FBSMI_JTOP_LEVEL(2) FBSMI_JTOP_LEVEL(1) FBSMI_JTOP_LEVEL(0)
+#undef FBSMI_JTOP_LEVEL
+    // ---- the tile of J: its leaves rebuilt from w, four per lane, the same up-sweep and the same walk; the last two levels
+    // are the four leaves of one lane.  J_prob[i*] = 1 - (the rest) is most of the mass whenever the weights are even (all of
+    // it at step 0), so the tile is that of i* more often than not: its w is loaded at entry and its leaves are ready before
+    // the walk above ends; any other tile costs the dependent load it always did.
+    const int lo0 = lo * kBlock;
+    float w0 = wref.x, w1 = wref.y, w2 = wref.z, w3 = wref.w;   // (scalars: a select between the vectors goes through scratch)
+    if (lo != b_ref) {
+        const float4 w4 = *reinterpret_cast<const float4*>(d.w + lo0 + 4 * lane);
+        w0 = w4.x; w1 = w4.y; w2 = w4.z; w3 = w4.w;
+    }
+    const int m0 = lo0 + 4 * lane;
+    t.x[0] = m0 == i_ref ? Ji : jprob_pow2(w0, w_max, inv_n);
+    t.x[1] = m0 + 1 == i_ref ? Ji : jprob_pow2(w1, w_max, inv_n);
+    t.x[2] = m0 + 2 == i_ref ? Ji : jprob_pow2(w2, w_max, inv_n);
+    t.x[3] = m0 + 3 == i_ref ? Ji : jprob_pow2(w3, w_max, inv_n);
+    wave_tree_upsweep(t);
+    lo = 0;
+#define FBSMI_JTILE_LEVEL(C) \
+    lo = wave_uniform(tree_walk(make_float2(wave_tree_half<C>(t, lo), wave_tree_mid<C>(t.x, lo)), q, P, E) ? lo : lo + (1 << C));
+    FBSMI_JTILE_LEVEL(7) FBSMI_JTILE_LEVEL(6) FBSMI_JTILE_LEVEL(5) FBSMI_JTILE_LEVEL(4) FBSMI_JTILE_LEVEL(3) FBSMI_JTILE_LEVEL(2)
+#undef FBSMI_JTILE_LEVEL
+    // the node of four leaves, then its children: two leaves, whose probe is E itself
+    const int ml = lo >> 2;
+    const float x0 = lane_read(t.x[0], ml), x2 = lane_read(t.x[2], ml), s01 = lane_read(t.s01, ml);
+    const bool g1 = tree_walk(make_float2(s01, x2), q, P, E);
+    const float tt = P + (g1 ? x0 : x2);
+    const bool gl = q <= E;
+    E = gl ? tt : E;
+    const int leaf = lo0 + lo + (g1 ? 0 : 2) + (gl ? 0 : 1);
+    return q <= E ? leaf : leaf + 1;
+}
+
+__device__ __forceinline__ int tree_build_roles(const LgDev& d, const RoleEntry& e, const float4 wref, TreeLds& L, int i_ref, float u3,
+                                                float w_max, float inv_n, float& last) {
+    __shared__ int Jsh;
+    __shared__ float lastsh;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nb = d.nb;
+    if (wv == 0) {
+        const int J = wave_tree_J(d, e, wref, i_ref, u3, w_max, inv_n);
+        if (lane == 0) Jsh = J;
+    } else if (wv == 1) {
+        const float total = wave_tree_w_side(tile_values4(d.bsumw, nb, lane), tile_values4(d.wfirst, nb, lane), L);
+        if (lane == 0) lastsh = total;
+    } else if (wv < 4) {   // two waves, eight 16-byte pieces per thread at 256 tiles
+        constexpr int STN = 2 * 64, STK = kMidN / 2 * kBlock / STN;
+        float4 stg[STK];
+#pragma unroll
+        for (int k = 0; k < STK; ++k) {
+            const int idx = tid - 2 * 64 + STN * k;
+            stg[k] = idx < kMidN / 2 * nb ? reinterpret_cast<const float4*>(d.trWtop)[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int k = 0; k < STK; ++k) {
+            const int idx = tid - 2 * 64 + STN * k;
+            if (idx < kMidN / 2 * nb) reinterpret_cast<float4*>(L.midW)[idx] = stg[k];
+        }
+    }
+    __syncthreads();
+    last = lastsh;
+    return Jsh;
+}
+
 // k_lg_prop1t, one tile per workgroup: a single chain's launches, the pinned launches and N = 2^k + 1.  Every workgroup builds
 // the trees and finds J itself, every slot draws its own noise and uniforms.  The one kernel of the tree walk with dead slots
 // (the extra tile of N = 2^k + 1 holds one): they run the whole step on source 0 and store nothing.
@@ -1849,13 +2064,14 @@ __device__ __forceinline__ float halfwave_sum(float s) {
 // partner's source goes across with one v_permlane32_swap -- one call per lane where k_lg_prop1tp makes two, no LDS
 // traffic and no barrier (the version that passed the words between waves through LDS lost the gain to its two barriers,
 // DESIGN 5.01).  Which word is a lane's own is a per-lane select: the roll can put the lower slot's source in the upper half.
-//   The noise is still drawn once per pair by the waves that wait for the tree builders (thread NP + p draws pair p), but
+//   The noise is still drawn once per pair by the upper waves while the lower ones build the trees (thread NP + p draws pair p;
+// ROLES: who builds what, tree_build_roles, or tree_build_shared), but
 // neither slot of a pair belongs to the drawing thread now: both normals are parked in LDS, at the index of the thread that
 // owns the slot (xish[r][threadIdx.x]: conflict-free reads).
 //   The per-tile (max, sumexp): levels 0-4 of the canonical tree are inside a half-wave, levels 5-7 run over the tile's
 // eight blocks, whose partials go through part[][] -- the same two exchanges as before, eight entries per tile.
 // Every output is written per tile / per slot exactly as by k_lg_prop1tp: only the owner changes.
-template <int DMAX, int HALVES>
+template <int DMAX, int HALVES, bool ROLES>
 __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s) {
     static_assert(HALVES == 2 || HALVES == 4, "two sides of HALVES / 2 tiles");
     constexpr int HP = HALVES / 2, NP = kBlock * HP;   // tiles per side; pairs
@@ -1876,7 +2092,10 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
     const float w_max = d.scal[1];
     const float inv_n = 1.0f / (float)N;   // N is a power of two: x / N == x * inv_n exactly
     TreeEntry te{};
-    if (builder) te = tree_entry_loads(d);
+    RoleEntry re;
+    float4 wref = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ROLES) wref = role_entry_loads(d, g.i_ref, re);
+    else if (builder) te = tree_entry_loads(d);
     gibbs_step_entry_rows<DMAX>(d, s, g);
     float xi[DMAX] = {};
     if (!kPairNoise<DMAX>) {
@@ -1898,7 +2117,8 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
         }
     }
     float last;
-    const int J = tree_build_shared(d, te, L, builder, g.i_ref, g.u3, w_max, inv_n, last);
+    const int J = ROLES ? tree_build_roles(d, re, wref, L, g.i_ref, g.u3, w_max, inv_n, last)
+                        : tree_build_shared(d, te, L, builder, g.i_ref, g.u3, w_max, inv_n, last);
     const int src = roll_source(m, roll_shift(g.j_ref, J, N), N);
     // ---- round 2
     const float ws = d.w[src];
@@ -4085,6 +4305,7 @@ struct fbsmi_lg_sweep {
     bool tree_plus1 = true;  // FBSMI_TREE_PLUS1=0: no two-launch step for N = 2^k + 1
     int tree_halves = -1;   // FBSMI_TREE_HALVES=1|2|4: tiles per workgroup of k_lg_prop1t / k_lg_prop1tp / k_lg_prop1th (unset: two from two tiles per CU on)
     bool halfwave = true;   // FBSMI_PROP_HALFWAVE=0: k_lg_prop1tp (a pair's slots in two waves) where k_lg_prop1th is the rule
+    bool j_wave = true;     // FBSMI_J_WAVE=0: k_lg_prop1th with tree_build_shared (the trees and J by four waves through LDS heaps)
     bool pin = true;        // FBSMI_PIN=0: no pinned launches of the narrow two-launch step (LgDev.pin)
     bool wide_pin = true;   // FBSMI_WIDE_PIN=0: no pinned launches of the one-tile wide step
     bool em = false;     // fbsmi_lg_sweep_set_em_forward: Euler-Maruyama forward paths (k_lg_em_noise, k_lg_em_path)
@@ -4109,6 +4330,7 @@ void read_switches(fbsmi_lg_sweep* s) {
     s->tree_step = env("FBSMI_TREE_STEP", 1) != 0;
     s->tree_plus1 = env("FBSMI_TREE_PLUS1", 1) != 0;
     s->halfwave = env("FBSMI_PROP_HALFWAVE", 1) != 0;
+    s->j_wave = env("FBSMI_J_WAVE", 1) != 0;
     s->pin = env("FBSMI_PIN", 1) != 0;
     s->wide_pin = env("FBSMI_WIDE_PIN", 1) != 0;
 }
@@ -4157,6 +4379,11 @@ struct Slab {
         else if ((s)->dmax == 2) { constexpr int DMAX = 2; __VA_ARGS__; }     \
         else if ((s)->dmax == 4) { constexpr int DMAX = 4; __VA_ARGS__; }     \
         else { constexpr int DMAX = 16; __VA_ARGS__; }                        \
+    } while (0)
+#define LG_ROLES(s, ...)                                                      \
+    do {                                                                      \
+        if ((s)->j_wave) { constexpr bool ROLES = true; __VA_ARGS__; }        \
+        else { constexpr bool ROLES = false; __VA_ARGS__; }                   \
     } while (0)
 #define LG_ITEMS(s, ...)                                                      \
     do {                                                                      \
@@ -4321,14 +4548,14 @@ void sweep_steps_narrow(fbsmi_lg_sweep* s, hipStream_t st) {
             // four tiles (two pairs N/2 apart) per 1024-thread workgroup: on request only.  With tiles N/2 apart it no longer
             // wins where it used to be the rule (four tiles per CU, 1024 tiles per launch: 22.4 against 24.2 G particle-steps/s
             // with two, 8 chains as two launches of four) nor below (512 tiles per launch: 14.7 against 16.5).
-            if (s->halfwave) LG_DMAX(s, k_lg_prop1th<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k));
+            if (s->halfwave) LG_ROLES(s, LG_DMAX(s, k_lg_prop1th<DMAX, 4, ROLES><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k)));
             else LG_DMAX(s, k_lg_prop1tp<DMAX, 4><<<dim3(nb / 4, d.C), 4 * kBlock, 0, st>>>(d, k));
         } else if (tree && !d.plus1 && nb % 2 == 0 && (s->tree_halves == 2 || (s->tree_halves < 0 && (int64_t)nb * d.C >= 2 * 256))) {
             // two tiles N/2 apart per 512-thread workgroup: half the waves skip the tree building and draw the noise of both
             // tiles meanwhile, one Threefry call per pair of slots (512 tiles per launch, 4 chains as two groups: 16.5 G
             // particle-steps/s against 15.6 with one tile per workgroup; a single chain keeps one tile per workgroup)
             // (k_lg_prop1th: both slots of a pair in one wave, so the kill-test and redraw draws also take one call per pair)
-            if (s->halfwave) LG_DMAX(s, k_lg_prop1th<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k));
+            if (s->halfwave) LG_ROLES(s, LG_DMAX(s, k_lg_prop1th<DMAX, 2, ROLES><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k)));
             else LG_DMAX(s, k_lg_prop1tp<DMAX, 2><<<dim3(nb / 2, d.C), 2 * kBlock, 0, st>>>(d, k));
         } else if (tree) {
             LG_DMAX(s, k_lg_prop1t<DMAX, 1><<<dim3(nb * (d.pin ? 8 : 1), d.C), kBlock, 0, st>>>(d, k));
