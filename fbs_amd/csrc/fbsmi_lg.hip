@@ -49,6 +49,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -545,11 +546,84 @@ __device__ __forceinline__ StepTables<DMAX> step_tables(const LgDev& d, int s) {
     return t;
 }
 
+// DMAX = 1 is launched for du = dv = 1 only (s->dmax), so there the width is a compile-time constant and the `r < du`
+// tests fold away
+template <int DMAX>
+__device__ __forceinline__ int step_du(const LgDev& d) { return DMAX == 1 ? 1 : d.du; }
+
+// A step's tables BY VALUE, for the narrow Gibbs step at DMAX = 1 (du = dv = 1; GibbsStep below): every address depends on the
+// step and the chain only, so the six floats of G[s] and g[s], sd[s], lognorm[s] and the step's three vectors are loaded at the
+// kernel's entry into scalar registers, and nothing is fetched behind a barrier.  Row and column 0 belong to u, 1 to v.
+// DMAX = 1 only: built for DMAX = 2 as well (26 values), k_lg_prop1, k_lg_propQ, k_lg_step1 and k_lg_sweep1 lost a wave per SIMD to
+// the scalar registers and k_lg_prop2 gained scratch, so the other widths keep their pointers.
+template <int DMAX>
+constexpr bool kStepByValue = DMAX == 1;
+
+template <int DMAX>   // (used at DMAX = 1 only; the parameter tells the overloads of drift_row / lg_loglik apart)
+struct StepValues {
+    float G[2][2];
+    float g[2];
+    float sd, sd2, lognorm, dt;
+};
+
+template <int DMAX>
+struct StepVec {   // v_prev, v or ustar of a step, by value
+    float x[1];
+    __device__ __forceinline__ float operator[](int i) const { return x[i]; }
+};
+
+template <int DMAX>
+__device__ __forceinline__ StepVec<DMAX> step_vec(const float* p) {
+    StepVec<DMAX> v;
+    v.x[0] = p[0];
+    return v;
+}
+
+template <int DMAX>
+__device__ __forceinline__ StepValues<DMAX> step_values(const LgDev& d, int s) {
+    StepValues<DMAX> t;
+    const float* G = d.G + (size_t)s * 4;
+    const float* g = d.g + (size_t)s * 2;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        t.g[r] = g[r];
+        t.G[r][0] = G[2 * r];
+        t.G[r][1] = G[2 * r + 1];
+    }
+    t.sd = d.sd[s];
+    t.sd2 = t.sd * t.sd;
+    t.lognorm = d.lognorm[s];
+    t.dt = d.dt;
+    return t;
+}
+
+// Keeps a wave-uniform value where it was loaded: left alone, the compiler sinks an entry load to its first use, behind the
+// barriers, which is the round trip the entry load was written to avoid.  An empty asm statement takes the value in, in a
+// scalar register, and passes an `anchor` through: whatever reads the anchor afterwards depends on the statement, so the
+// value is in its register before the anchor's next use, and stays there.  A chain of them through one anchor that is needed
+// early (the noise key) makes a group that is loaded back to back and waited for once.  Two things it must not
+// be: volatile (after such a statement the compiler no longer takes memory for unwritten, and every uniform load becomes a
+// vector load), and an output for a pointer (what comes out of the statement is a generic pointer: flat loads).
+// (A value loaded behind a store of the same kernel -- the one-launch sweeps -- arrives in a vector register and is first
+// made scalar; where it already is, that costs nothing.)
+template <class T>
+__device__ __forceinline__ T as_uniform(T v) {
+    if constexpr (sizeof(T) == 4) return __builtin_bit_cast(T, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+    else return v;
+}
+template <class A, class T>
+__device__ __forceinline__ void pin_uniform(A& anchor, const T& v) {
+    anchor = as_uniform(anchor);
+    asm("" : "+s"(anchor) : "s"(as_uniform(v)));
+}
+template <class A, class... Ts>
+__device__ __forceinline__ void pin_uniforms(A& anchor, const Ts&... vs) { (pin_uniform(anchor, vs), ...); }
+
 // row p of a narrow (structure-of-arrays) particle buffer
 template <int DMAX>
 __device__ __forceinline__ void load_row(const LgDev& d, const float* up, int p, float (&u)[DMAX]) {
 #pragma unroll
-    for (int r = 0; r < DMAX; ++r) u[r] = r < d.du ? up[(size_t)r * d.N + p] : 0.0f;
+    for (int r = 0; r < DMAX; ++r) u[r] = r < step_du<DMAX>(d) ? up[(size_t)r * d.N + p] : 0.0f;
 }
 
 // drift_r = g_r + sum_c G_rc z_c, a c-ordered fma chain started at g_r, z = (u, v_prev)
@@ -589,6 +663,22 @@ __device__ __forceinline__ float lg_loglik(const StepTables<DMAX>& t, const floa
     return acc;
 }
 
+// The same two chains on a step's tables by value (du = dv = 1): the u row, or (vrow) the v row.  Same operands, same order.
+template <int DMAX>
+__device__ __forceinline__ float drift_row(const StepValues<DMAX>& t, int r, const float (&u)[DMAX], const StepVec<DMAX>& v_prev,
+                                           bool vrow = false) {
+    const int R = vrow ? 1 : 0;
+    return fbsmi_fmaf(t.G[R][1], v_prev[0], fbsmi_fmaf(t.G[R][0], u[0], t.g[R]));
+}
+
+template <int DMAX>
+__device__ __forceinline__ float lg_loglik(const StepValues<DMAX>& t, const float (&u)[DMAX], const StepVec<DMAX>& v,
+                                           const StepVec<DMAX>& v_prev) {
+    const float dr = drift_row<DMAX>(t, 0, u, v_prev, true);
+    const float cond_m = v_prev[0] + dr * t.dt;
+    return norm_logpdf(v[0], cond_m, t.sd2, t.lognorm);
+}
+
 // ------------------------------------------------------------------------------------------
 // The per-slot step of the narrow Gibbs sweep, one text for k_lg_prop1, k_lg_propQ, k_lg_prop1t, k_lg_prop1tp, k_lg_prop1th,
 // k_lg_prop2t, k_lg_prop2 and lg_step1_body.  A kernel keeps its variant: who owns which slot, where the noise and the
@@ -598,7 +688,13 @@ __device__ __forceinline__ float lg_loglik(const StepTables<DMAX>& t, const floa
 // What a step reads at entry: all of it is addressable when the kernel starts ("round 0"), so it is loaded at the top of the
 // kernel, ahead of the noise draw, never behind a barrier and never "when needed".  Two calls, and a kernel's own entry loads
 // go BETWEEN them: gibbs_step_entry issues the scalar loads (keys, reference indices); gibbs_step_entry_rows what waits for
-// them (the reference row) and the tables.  An unused member costs no load (lg_step1_body: resampler keys, uref).
+// them (the reference row) and the tables.  Where the members are not pinned (below), an unused one costs no load.
+//   The rule is enforced, not left to the compiler, which sinks a load to its first use.  kStepByValue (DMAX = 1): the tables
+// and the step's three vectors are members BY VALUE (StepValues, StepVec), loaded by gibbs_step_entry in the same round as the
+// keys and the reference indices -- only the reference row has to wait for i_ref -- and gibbs_step_entry_rows ends by pinning
+// every one of them, the keys and the reference row (pin_uniform), so the slot body (drift_row, lg_loglik, the pin of j*)
+// reads registers and makes no load of a table between the stage barrier and the end of the kernel.  The other widths keep
+// the pointers.
 template <int DMAX>
 struct GibbsStep {
     uint32_t a0, a1, b0, b1, t0, t1;   // key_1 (kill test), key_2 (redraw), key_transition of step s (k_lg_keys)
@@ -607,8 +703,8 @@ struct GibbsStep {
     const float* up;                   // particles of step s (ping-pong u0 / u1)
     float* un;                         // ... of step s + 1
     float uref[DMAX];                  // the reference row up[:, i_ref]
-    StepTables<DMAX> t;
-    const float *v_prev, *v, *ustar;   // vs[s], vs[s + 1], us_star[s + 1]
+    std::conditional_t<kStepByValue<DMAX>, StepValues<DMAX>, StepTables<DMAX>> t;
+    std::conditional_t<kStepByValue<DMAX>, StepVec<DMAX>, const float*> v_prev, v, ustar;   // vs[s], vs[s + 1], us_star[s + 1]
 };
 
 template <int DMAX>
@@ -621,16 +717,27 @@ __device__ __forceinline__ GibbsStep<DMAX> gibbs_step_entry(const LgDev& d, int 
     g.j_ref = d.bs[s + 1];
     g.up = (s & 1) ? d.u1 : d.u0;
     g.un = (s & 1) ? d.u0 : d.u1;
+    if constexpr (kStepByValue<DMAX>) {
+        g.t = step_values<DMAX>(d, s);
+        g.v_prev = step_vec<DMAX>(d.vs + s);
+        g.v = step_vec<DMAX>(d.vs + s + 1);
+        g.ustar = step_vec<DMAX>(d.us_star + s + 1);
+    }
     return g;
 }
 
 template <int DMAX>
 __device__ __forceinline__ void gibbs_step_entry_rows(const LgDev& d, int s, GibbsStep<DMAX>& g) {
     load_row<DMAX>(d, g.up, g.i_ref, g.uref);
-    g.t = step_tables<DMAX>(d, s);
-    g.v_prev = d.vs + (size_t)s * d.dv;
-    g.v = d.vs + (size_t)(s + 1) * d.dv;
-    g.ustar = d.us_star + (size_t)(s + 1) * d.du;
+    if constexpr (kStepByValue<DMAX>) {   // anchored on the noise key, which every kernel needs first
+        pin_uniforms(g.t1, g.t.g[0], g.t.G[0][0], g.t.G[0][1], g.t.g[1], g.t.G[1][0], g.t.G[1][1], g.t.sd, g.t.lognorm,
+                     g.a0, g.a1, g.b0, g.b1, g.t0, g.u3, g.j_ref, g.v_prev.x[0], g.v.x[0], g.ustar.x[0], g.uref[0]);
+    } else {
+        g.t = step_tables<DMAX>(d, s);
+        g.v_prev = d.vs + (size_t)s * d.dv;
+        g.v = d.vs + (size_t)(s + 1) * d.dv;
+        g.ustar = d.us_star + (size_t)(s + 1) * d.du;
+    }
 }
 
 // roll by j* - J (resamplings.py:85): slot m receives the particle of slot roll_source(m, roll_shift(j*, J, N), N)
@@ -655,7 +762,7 @@ __device__ __forceinline__ void gibbs_slot_gather(const LgDev& d, const GibbsSte
     if (killed && !pinned) {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) u[r] = EARLY ? ucand[r] : g.up[(size_t)r * d.N + a];
+            if (r < step_du<DMAX>(d)) u[r] = EARLY ? ucand[r] : g.up[(size_t)r * d.N + a];
     }
     if (pinned) {
 #pragma unroll
@@ -673,7 +780,7 @@ __device__ __forceinline__ float gibbs_slot_finish(const LgDev& d, const GibbsSt
     const bool pinned = m == g.j_ref;
 #pragma unroll
     for (int r = 0; r < DMAX; ++r) {
-        if (r < d.du) {
+        if (r < step_du<DMAX>(d)) {
             const float dr = drift_row<DMAX>(g.t, r, u, g.v_prev);
             float x = (u[r] + dr * g.t.dt) + g.t.sd * xi[r];
             if (pinned) x = g.ustar[r];
@@ -696,7 +803,7 @@ __device__ __forceinline__ void pair_noise(const LgDev& d, const GibbsStep<DMAX>
     for (int r = 0; r < DMAX; ++r) {
         xiA[r] = 0.0f;
         xiB[r] = 0.0f;
-        if (r < d.du) {
+        if (r < step_du<DMAX>(d)) {
             uint32_t lo_, hi_;
             random_bits_pair(g.t0, g.t1, (uint64_t)d.N * d.du, (uint64_t)mA * d.du + r, lo_, hi_);
             xiA[r] = normal_from_bits(lo_);
@@ -1723,34 +1830,56 @@ __device__ __forceinline__ float wave_tree_mid(const float (&y)[4], int lo) {
     else return (lo & 2) ? lane_read(y[3], ml) : lane_read(y[1], ml);
 }
 
-// four consecutive per-tile values of this lane (0 behind tile nb - 1).  Two tiles: a chain's part of the buffer is only 8-byte aligned.
-__device__ __forceinline__ float4 tile_values4(const float* p, int nb, int lane) {
+// Four consecutive per-tile values of this lane (0 behind tile nb - 1; nb a power of two from 2 on), in two steps so that a
+// wave's entry loads go out back to back and wait once: tile_values4_issue makes two 8-byte loads at clamped addresses -- one
+// shape for every tile count, no branch and no predicate (a chain's part of the buffer is 8-byte aligned at two tiles, and a
+// load per shape had its own wait, with the shapes merged through other registers) -- and tile_values4 zeroes what lies behind
+// the last tile, where the values are first used.
+struct TileQuad {
+    float2 lo, hi;
+};
+
+__device__ __forceinline__ TileQuad tile_values4_issue(const float* p, int nb, int lane) {
     const int t = 4 * lane;
-    if (nb >= 4) return t < nb ? *reinterpret_cast<const float4*>(p + t) : make_float4(0.f, 0.f, 0.f, 0.f);
-    return make_float4(t < nb ? p[t] : 0.0f, t + 1 < nb ? p[t + 1] : 0.0f, 0.f, 0.f);
+    TileQuad q;
+    q.lo = *reinterpret_cast<const float2*>(p + (t < nb ? t : nb - 2));
+    q.hi = *reinterpret_cast<const float2*>(p + (t + 2 < nb ? t + 2 : nb - 2));
+    return q;
+}
+
+__device__ __forceinline__ float4 tile_values4(const TileQuad q, int nb, int lane) {
+    const bool a = 4 * lane < nb, b = 4 * lane + 2 < nb;
+    return make_float4(a ? q.lo.x : 0.0f, a ? q.lo.y : 0.0f, b ? q.hi.x : 0.0f, b ? q.hi.y : 0.0f);
 }
 
 // What the J wave loads at the kernel's entry, ahead of the noise draws.  Waves 1-3 have nothing else to do before the barrier
 // and take no part in the draws, so they load where they work (tree_build_roles) and hold no registers across the code in
 // between.
 struct RoleEntry {
-    float4 sj, wf;          // sums of J_prob ([i*] = 0) and the first w of the lane's four tiles
+    TileQuad sj, wf;        // sums of J_prob ([i*] = 0) and the first w of the lane's four tiles (tile_values4_issue)
     float refsib[8];        // sibling sums of the leaf i* in its tile's J_prob tree (published by k_lg_norm)
+    float w_max;            // the J wave's own copy: it goes out with refsib, not whenever the other waves' copy does
 };
 
-// Returns (by value, like every record that must stay in registers) the J wave's four w of the tile of i*: the tile J falls in
-// whenever J == i* (see wave_tree_J).
-__device__ __forceinline__ float4 role_entry_loads(const LgDev& d, int i_ref, RoleEntry& e) {
+// Two calls.  What the kernel's arguments address goes out with the keys and the reference indices: no load here waits for
+// another, and the scalar ones share the wait that i_ref needs anyway ...
+__device__ __forceinline__ void role_entry_loads(const LgDev& d, RoleEntry& e) {
     const int tid = threadIdx.x, nb = d.nb;
-    float4 wref = make_float4(0.f, 0.f, 0.f, 0.f);
     if (tid < 64) {
-        e.sj = tile_values4(d.bsumJ, nb, tid);
-        e.wf = tile_values4(d.wfirst, nb, tid);
-        wref = *reinterpret_cast<const float4*>(d.w + i_ref / kBlock * kBlock + 4 * tid);
+        e.sj = tile_values4_issue(d.bsumJ, nb, tid);
+        e.wf = tile_values4_issue(d.wfirst, nb, tid);
+        e.w_max = d.scal[1];
 #pragma unroll
         for (int lv = 0; lv < 8; ++lv) e.refsib[lv] = d.scal[4 + lv];
     }
-    return wref;
+}
+
+// ... and, once i_ref is there, the four w per lane of the tile of i*, the tile J falls in whenever J == i* (see wave_tree_J):
+// returned by value, like every record that must stay in registers.  EVERY wave makes this load (the same kilobyte, by lane),
+// though only the J wave reads it: inside the J wave's branch its wait for i_ref would not count for the code behind the
+// branch, and the reference row would go out a round later.
+__device__ __forceinline__ float4 role_entry_ref_tile(const LgDev& d, int i_ref) {
+    return *reinterpret_cast<const float4*>(d.w + i_ref / kBlock * kBlock + 4 * (threadIdx.x & 63));
 }
 
 // the w side of tree_build by one wave: L.topW and `last` = cdf[N - 1] = the root of the w tree
@@ -1775,8 +1904,9 @@ __device__ __forceinline__ int wave_tree_J(const LgDev& d, const RoleEntry& e, c
     const int b_ref = i_ref / kBlock, lb = b_ref >> 2;
     // ---- the tree over the tiles: sums of J_prob with [i*] = 0; the leaves at the midpoints, the four divisions side by side
     WaveTree t;
-    t.x[0] = e.sj.x; t.x[1] = e.sj.y; t.x[2] = e.sj.z; t.x[3] = e.sj.w;
-    const float wf[4] = {e.wf.x, e.wf.y, e.wf.z, e.wf.w};
+    const float4 sj = tile_values4(e.sj, nb, lane), wf4 = tile_values4(e.wf, nb, lane);
+    t.x[0] = sj.x; t.x[1] = sj.y; t.x[2] = sj.z; t.x[3] = sj.w;
+    const float wf[4] = {wf4.x, wf4.y, wf4.z, wf4.w};
     float jq[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) jq[i] = jprob_pow2(wf[i], w_max, inv_n);
@@ -1847,15 +1977,16 @@ __device__ __forceinline__ int wave_tree_J(const LgDev& d, const RoleEntry& e, c
 }
 
 __device__ __forceinline__ int tree_build_roles(const LgDev& d, const RoleEntry& e, const float4 wref, TreeLds& L, int i_ref, float u3,
-                                                float w_max, float inv_n, float& last) {
+                                                float inv_n, float& last) {
     __shared__ int Jsh;
     __shared__ float lastsh;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nb = d.nb;
     if (wv == 0) {
-        const int J = wave_tree_J(d, e, wref, i_ref, u3, w_max, inv_n);
+        const int J = wave_tree_J(d, e, wref, i_ref, u3, e.w_max, inv_n);
         if (lane == 0) Jsh = J;
     } else if (wv == 1) {
-        const float total = wave_tree_w_side(tile_values4(d.bsumw, nb, lane), tile_values4(d.wfirst, nb, lane), L);
+        const TileQuad sw = tile_values4_issue(d.bsumw, nb, lane), wf = tile_values4_issue(d.wfirst, nb, lane);
+        const float total = wave_tree_w_side(tile_values4(sw, nb, lane), tile_values4(wf, nb, lane), L);
         if (lane == 0) lastsh = total;
     } else if (wv < 4) {   // two waves, eight 16-byte pieces per thread at 256 tiles
         constexpr int STN = 2 * 64, STK = kMidN / 2 * kBlock / STN;
@@ -2087,28 +2218,30 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
     const int m = mL + (hw ? hN : 0);
     const int ts = wv >> 3, bk = wv & 7;                 // the tile of the side, and this half-wave's block of 32 slots in it
     const int tileb = blockIdx.x * HP + ts + (hw ? d.nb >> 1 : 0);   // == m / kBlock
-    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
-    // ---- round 0: everything addressable now
-    const float w_max = d.scal[1];
-    const float inv_n = 1.0f / (float)N;   // N is a power of two: x / N == x * inv_n exactly
+    // ---- round 0: everything addressable now.  One round for what the arguments address (the J wave's tile sums, the keys and
+    // the reference indices, the step's tables), one for what i_ref addresses (the tile of i*, the reference row).
     TreeEntry te{};
     RoleEntry re;
+    GibbsStep<DMAX> g = gibbs_step_entry<DMAX>(d, s);
+    const float w_max = d.scal[1];
+    if (ROLES) role_entry_loads(d, re);
+    const float inv_n = 1.0f / (float)N;   // N is a power of two: x / N == x * inv_n exactly
     float4 wref = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ROLES) wref = role_entry_loads(d, g.i_ref, re);
+    if (ROLES) wref = role_entry_ref_tile(d, g.i_ref);
     else if (builder) te = tree_entry_loads(d);
     gibbs_step_entry_rows<DMAX>(d, s, g);
     float xi[DMAX] = {};
     if (!kPairNoise<DMAX>) {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) xi[r] = normal_at(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
+            if (r < step_du<DMAX>(d)) xi[r] = normal_at(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)m * d.du + r);
     } else if (tid >= NP) {   // pair p: element (slot p of the lower side) * du + r is in the first half of the draw, its
                               // partner belongs to the slot N/2 above; the owners are lanes l and l + 32 of wave p / 32
         const int p = tid - NP, own = (p >> 5) * 64 + (p & 31);
         const int mp = blockIdx.x * NP + p;
 #pragma unroll
         for (int r = 0; r < DMAX; ++r) {
-            if (r < d.du) {
+            if (r < step_du<DMAX>(d)) {
                 uint32_t lo_, hi_;
                 random_bits_pair(g.t0, g.t1, (uint64_t)N * d.du, (uint64_t)mp * d.du + r, lo_, hi_);
                 xish[r][own] = normal_from_bits(lo_);
@@ -2117,7 +2250,7 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
         }
     }
     float last;
-    const int J = ROLES ? tree_build_roles(d, re, wref, L, g.i_ref, g.u3, w_max, inv_n, last)
+    const int J = ROLES ? tree_build_roles(d, re, wref, L, g.i_ref, g.u3, inv_n, last)
                         : tree_build_shared(d, te, L, builder, g.i_ref, g.u3, w_max, inv_n, last);
     const int src = roll_source(m, roll_shift(g.j_ref, J, N), N);
     // ---- round 2
@@ -2127,7 +2260,7 @@ __global__ void __launch_bounds__(kBlock * HALVES) k_lg_prop1th(LgDev dd, int s)
     if (kPairNoise<DMAX>) {
 #pragma unroll
         for (int r = 0; r < DMAX; ++r)
-            if (r < d.du) xi[r] = xish[r][tid];
+            if (r < step_du<DMAX>(d)) xi[r] = xish[r][tid];
     }
     // uniform_at(a0, a1, N, src) and uniform_at(b0, b1, N, src) from one call per lane.  The partner's source is src +- N/2,
     // so both lanes of a pair have the same counter c; `swp` (the same in both lanes) says that the LOWER slot's source is
