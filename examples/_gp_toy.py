@@ -24,6 +24,18 @@ def add_common_args(parser):
     return parser
 
 
+def print_diag(what, ess, lse, n):
+    """The --diag summary of the drivers: ess (..., rows) and the step rows of lse (..., steps) of every sweep / run, n
+    weights per vector.  Per sweep (run) the minimum and the median ESS over its steps and the summed log-normaliser
+    sum_k (lse_k - log n); printed as their range over the sweeps (runs)."""
+    ess, lse = np.asarray(ess, np.float64), np.asarray(lse, np.float64)
+    lo, med = ess.min(axis=-1).ravel(), np.median(ess, axis=-1).ravel()
+    logz = (lse - np.log(n)).sum(axis=-1).ravel()
+    print(f'diag | {lo.size} {what}s of {ess.shape[-1]} weight vectors of {n} | min ESS over steps: {lo.min():.4g} .. {lo.max():.4g} '
+          f'(median {np.median(lo):.4g}) | median ESS over steps: {med.min():.4g} .. {med.max():.4g} '
+          f'(median {np.median(med):.4g}) | summed log-normaliser: {logz.min():.6g} .. {logz.max():.6g} (mean {logz.mean():.6g})')
+
+
 def gp_setting(args, dev):
     """-> dict(key, d, y0 (np f32), gp_mean, gp_cov, ts, sde, bridge).  Key schedule as gp_*.py:30-47."""
     key = ops.PRNGKey(args.id)

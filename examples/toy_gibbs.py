@@ -33,6 +33,7 @@ def main(argv=None):
     parser.add_argument('--nchains', type=int, default=4, help='The number of MCMC chains.')
     parser.add_argument('--outdir', type=str, default='./toy/results')
     parser.add_argument('--quiet', action='store_true')
+    parser.add_argument('--diag', action='store_true', help='Per-step ESS and log-normaliser of every sweep (saved as ess, lse).')
     args = parser.parse_args(argv)
     dev = torch.device('cuda:0')
     key = ops.PRNGKey(args.id)                                                   # gp_gibbs.py:30
@@ -88,18 +89,34 @@ def main(argv=None):
 
     # Gibbs loop, gp_gibbs.py:180-190: per iteration key, subkey = split(key); key_chains = split(subkey, nchains)
     # (--marg: gibbs_kernel(marg_y=True), the observation path re-drawn by the Doob bridge inside every fused sweep, gp_gibbs.py:167)
-    sweep = bridge.sweep_handle(nparticles, args.explicit_backward, args.explicit_final, nchains=nchains, marg_y=args.marg)
-    key, x0s, bs_stars, samples = sweep.chain(key, x0s, y0, bs_stars, nsamples)
+    sweep = bridge.sweep_handle(nparticles, args.explicit_backward, args.explicit_final, nchains=nchains, marg_y=args.marg,
+                                diagnostics=args.diag)
+    diag = {}
+    if args.diag:   # the handle keeps the rows of its last sweep: one sweep per call (the same key schedule), fetched after each
+        samples, ess, lse = [], [], []
+        for _ in range(nsamples):
+            key, x0s, bs_stars, one = sweep.chain(key, x0s, y0, bs_stars, 1)
+            dg = sweep.diagnostics()
+            samples.append(one)
+            ess.append(dg["ess"].reshape(nchains, nsteps + 1))
+            lse.append(dg["lse"].reshape(nchains, nsteps + 1))
+        samples = torch.cat(samples, 0).reshape(nsamples, nchains, d)
+        diag = dict(ess=torch.stack(ess, 1).cpu().numpy(), lse=torch.stack(lse, 1).cpu().numpy())   # (nchains, nsamples, T + 1)
+    else:
+        key, x0s, bs_stars, samples = sweep.chain(key, x0s, y0, bs_stars, nsamples)
     gibbs_samples = samples.permute(1, 0, 2).cpu().numpy()                          # (nchains, nsamples, d)
     if not args.quiet:
         burn = min(100, nsamples // 2)
         err = np.abs(gibbs_samples[:, burn:].mean(axis=(0, 1)) - gp_mean).max()
         print(f'ID: {args.id} | Gibbs | {nchains} chains x {nsamples} sweeps | max |mean - gp_mean| = {err:.3f}')
+    if args.diag:
+        from _gp_toy import print_diag
+        print_diag('sweep', diag['ess'], diag['lse'][..., 1:], sweep.n_rows)
 
     os.makedirs(args.outdir, exist_ok=True)
     out = os.path.join(args.outdir, f'gibbs{"-eb" if args.explicit_backward else ""}{"-ef" if args.explicit_final else ""}'
                        f'{"-marg" if args.marg else ""}-{args.sde}-{args.nparticles}-{args.id}')
-    np.savez(out, samples=gibbs_samples, gp_mean=gp_mean, gp_cov=gp_cov)               # gp_gibbs.py:193-195
+    np.savez(out, samples=gibbs_samples, gp_mean=gp_mean, gp_cov=gp_cov, **diag)       # gp_gibbs.py:193-195
     return gibbs_samples, gp_mean, gp_cov
 
 

@@ -153,7 +153,11 @@ def sb_setting(args, dev):
 def main(argv=None):
     parser = common_args(argparse.ArgumentParser())
     parser.add_argument('--explicit_backward', action='store_true', default=False)
+    parser.add_argument('--diag', action='store_true',
+                        help='With --fused: per-step ESS and log-normaliser of every sweep (saved as ess, lse).')
     args = parser.parse_args(argv)
+    if args.diag and not args.fused:
+        parser.error('--diag reads the fused engine: it needs --fused')
     dev = torch.device('cuda:0')
     g = sb_setting(args, dev)
     key, d, y0, ts, nsteps, drift, gp_mean, gp_cov = g.key, g.d, g.y0, g.ts, g.nsteps, g.drift, g.gp_mean, g.gp_cov
@@ -173,10 +177,21 @@ def main(argv=None):
     x0, us_star, bs_star = gibbs_init(subkey)
     samples = torch.empty((args.nsamples, d), device=dev)
     accs = np.zeros(args.nsamples, bool)
+    diag = {}
     if g.bridge is not None:
         # the whole loop on the device: per sweep key, subkey = split(key); gibbs_kernel(subkey, ...) (:176-184)
-        sweep = g.bridge.sweep_handle(args.nparticles, args.explicit_backward, False)
-        _, _, _, samples = sweep.chain(key, x0, y0, bs_star, args.nsamples)
+        sweep = g.bridge.sweep_handle(args.nparticles, args.explicit_backward, False, diagnostics=args.diag)
+        if args.diag:   # the handle keeps the rows of its last sweep: one sweep per call (the same key schedule), fetched after each
+            ess, lse = [], []
+            for i in range(args.nsamples):
+                key, x0, bs_star, one = sweep.chain(key, x0, y0, bs_star, 1)
+                dg = sweep.diagnostics()
+                samples[i] = one[0]
+                ess.append(dg["ess"])
+                lse.append(dg["lse"])
+            diag = dict(ess=torch.stack(ess).cpu().numpy(), lse=torch.stack(lse).cpu().numpy())   # (nsamples, T + 1)
+        else:
+            _, _, _, samples = sweep.chain(key, x0, y0, bs_star, args.nsamples)
     for i in range(0 if g.bridge is not None else args.nsamples):                   # :176-184
         key, subkey = ops.split(key)
         x0, us_star, bs_star, acc = gibbs_kernel(subkey, x0, y0, us_star, bs_star, ts, fwd_sampler, None, unpack,
@@ -190,9 +205,12 @@ def main(argv=None):
         err = np.abs(samples[burn:].mean(axis=0) - gp_mean).max()
         acc = 'fused chain' if g.bridge is not None else f'acc rate {accs.mean():.3f}'
         print(f'ID: {args.id} | SB Gibbs | {args.nsamples} sweeps | {acc} | max |mean - gp_mean| = {err:.3f}')
+    if args.diag:
+        from _gp_toy import print_diag
+        print_diag('sweep', diag['ess'], diag['lse'][..., 1:], args.nparticles)
     os.makedirs(args.outdir, exist_ok=True)
     np.savez(os.path.join(args.outdir, f'gibbs{"-eb" if args.explicit_backward else ""}-{args.nparticles}-{args.id}'),
-             samples=samples, gp_mean=gp_mean, gp_cov=gp_cov)                      # :187-188
+             samples=samples, gp_mean=gp_mean, gp_cov=gp_cov, **diag)              # :187-188
     return samples, gp_mean, gp_cov
 
 

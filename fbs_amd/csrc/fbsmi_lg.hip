@@ -3481,6 +3481,85 @@ __global__ void __launch_bounds__(kBlock) k_lgwf_final(LgDev dd) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Opt-in diagnostics (fbsmi_lg_sweep_set_diagnostics / fbsmi_lg_filter_set_diagnostics; definitions in include/fbsmi.h):
+// one (lse, ess) row per vector of unnormalised log-weights, lse the two-level logsumexp, ess = 1 / tree-sum of w_i^2 with
+// w_i = exp(lw_i - lse).  Only a handle with diagnostics on launches these; they take their descriptor as an argument of
+// their own, so LgDev and every kernel above are what they are without them.
+// The log-weights of a step lie in HBM between the step's last launch and the next normalisation: in d.lw (FORM 0), or, in the
+// one-tile wide regimes, as the per-row terms d.lpw whose row sums they are (FORM 1: lgw_row_sum, as k_lgw_lse).  With several
+// tiles the step's last launch has also published the tiles' (max, sumexp) in d.bmax / d.bsumexp for the normalisation that
+// follows: k_lg_diag combines them as k_lg_norm does and leaves one tree-sum of w^2 per tile, k_lg_diag_top takes the root.
+// One tile: k_lg_diag does it all.
+// ------------------------------------------------------------------------------------------
+struct DiagDev {
+    float* rows;   // [C][nrows][2]: (lse, ess)
+    float* q;      // [C][nb]: per-tile sums of w^2 (several tiles)
+    int nrows;
+};
+
+// tile bx of chain c, by one workgroup; xch: 3 x 4 floats of LDS untouched since the last barrier.  Addresses are clamped
+// into the vector and what lies beyond it is replaced afterwards: no load waits on a per-lane predicate.
+template <int ITEMS, int FORM>
+__device__ __forceinline__ void diag_tile(const LgDev& d, const DiagDev& g, int c, int row, int bx, float (*xch)[4]) {
+    const int N = d.N;
+    const int base = (bx * kBlock + (int)threadIdx.x) * ITEMS;
+    float l[ITEMS];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const int e = base + i, ec = e < N ? e : N - 1;
+        const float x = FORM == 1 ? lgw_row_sum(d, ec) : d.lw[ec];
+        l[i] = e < N ? x : -__builtin_inff();
+    }
+    float lse, Mraw;
+    if (d.nb == 1) {   // one tile: the combine multiplies its sum by exp(0) = 1 and adds zeros (as lgw_pre_body)
+        float sx;
+        block_lse_partial<ITEMS>(l, xch[0], xch[1], Mraw, sx);
+        lse = fbsmi_logf(sx) + finite_or_zero_f(Mraw);
+    } else {
+        lse_from_partials(d.bmax, d.bsumexp, d.nb, xch[0], xch[1], lse, Mraw);
+    }
+    float x[ITEMS];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const float w = fbsmi_expf(l[i] - lse);
+        x[i] = base + i < N ? w * w : 0.0f;
+        if (ITEMS > 4 && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // four float64 exponentials at a time (k_lg_norm)
+    }
+    TreePath path;
+    const float tot = block_upsweep(chunk_total<ITEMS>(x), path, xch[2]);
+    if (threadIdx.x == 0) {
+        float* out = g.rows + ((size_t)c * g.nrows + row) * 2;
+        if (bx == 0) out[0] = lse;
+        if (d.nb == 1) out[1] = 1.0f / tot;
+        else g.q[(size_t)c * d.nb + bx] = tot;
+    }
+}
+
+template <int ITEMS, int FORM>
+__global__ void __launch_bounds__(kBlock) k_lg_diag(LgDev dd, DiagDev g, int row) {
+    const LgDev d = chain_view(dd, blockIdx.y);
+    __shared__ float xch[3][4];
+    diag_tile<ITEMS, FORM>(d, g, blockIdx.y, row, blockIdx.x, xch);
+}
+
+// several tiles: ess = 1 / root of the tree over the tiles' sums (at most kMaxTopBlock of them, four per thread)
+__global__ void __launch_bounds__(kBlock) k_lg_diag_top(LgDev dd, DiagDev g, int row) {
+    __shared__ float s4[4];
+    const int nb = dd.nb;
+    const float* __restrict__ q = g.q + (size_t)blockIdx.y * nb;
+    float x[kTopItems];
+#pragma unroll
+    for (int i = 0; i < kTopItems; ++i) {
+        const int e = threadIdx.x * kTopItems + i;
+        const float v = q[e < nb ? e : nb - 1];
+        x[i] = e < nb ? v : 0.0f;
+    }
+    TreePath path;
+    const float root = block_upsweep(chunk_total<kTopItems>(x), path, s4);
+    if (threadIdx.x == 0) g.rows[((size_t)blockIdx.y * g.nrows + row) * 2 + 1] = 1.0f / root;
+}
+
+// ------------------------------------------------------------------------------------------
 // Narrow models with at most 256 particles: the ensemble is one tile and one workgroup, so a whole SMC
 // step -- normalise, both CDFs (in LDS), J, redraws, gather, Euler-Maruyama, pin, log-weight -- is
 // ONE launch of one workgroup per chain (the step prologue is shared with the wide path).
@@ -3530,8 +3609,11 @@ __global__ void __launch_bounds__(kBlock) k_lg_sweep1(LgDev dd) {
 // pmcmc_filter_step smc.py:138-157) in ONE launch of one workgroup per chain -- per step the filter
 // prologue (logsumexp, log-likelihood accumulator, weights, cumsum, stratified / systematic ancestors, all in
 // LDS) followed by gather, propagate and weight, a workgroup barrier between steps.
-template <int DMAX>
-__global__ void __launch_bounds__(kBlock) k_filt_sweep1(LgDev dd, const float* u0s_all) {
+// (DIAG = DiagDev, a handle with diagnostics on: the (lse, ess) row of every weight vector in front of its normalisation, by
+// diag_tile on the workgroup's own stores.  DIAG = NoDiag is the kernel as it is without them.)
+struct NoDiag {};
+template <int DMAX, typename DIAG = NoDiag>
+__global__ void __launch_bounds__(kBlock) k_filt_sweep1(LgDev dd, const float* u0s_all, DIAG g) {
     const LgDev d = chain_view(dd, blockIdx.y);
     __shared__ LgwPreLds pre;
     const int N = d.N, m = threadIdx.x, T = d.T;
@@ -3560,6 +3642,7 @@ __global__ void __launch_bounds__(kBlock) k_filt_sweep1(LgDev dd, const float* u
         const bool resample = d.flow == 1 || k > 0;
         int a = m;
         if (resample) {
+            if constexpr (std::is_same<DIAG, DiagDev>::value) diag_tile<1, 0>(d, g, blockIdx.y, d.flow == 1 ? k : k - 1, 0, pre.xch);
             lgw_fpre_body<false>(d, d.flow == 1 ? k : k - 1, true, pre, []() {});
             a = live ? pre.ancS[m] : 0;
         }
@@ -4445,6 +4528,8 @@ struct fbsmi_lg_sweep {
     EmDev emd{};
     bool bridge = false; // fbsmi_lg_sweep_set_bridge: marg_y=True, vs re-drawn by the Doob bridge (k_lg_bridge_noise, k_lg_bridge)
     BridgeDev brd{};
+    DiagDev diag{};      // fbsmi_lg_sweep_set_diagnostics / fbsmi_lg_filter_set_diagnostics: rows != null = on (k_lg_diag after every step)
+    bool ran = false;    // a sweep or filter run has been enqueued: the launch list is settled
     std::vector<hipEvent_t> prof_ev[kNumProfKernels];  // pairs (start, stop)
     double prof_us[kNumProfKernels] = {0, 0, 0};
     int64_t prof_n[kNumProfKernels] = {0, 0, 0};
@@ -4566,6 +4651,18 @@ struct WideGeom {
     int v_tiles() const { return nrt - v_tile0; }
 };
 
+// Diagnostics on: the (lse, ess) row `row` of the log-weights as they lie in HBM now -- d.lw (and, with several tiles, the
+// tile partials next to it), or with `rows` the per-row terms d.lpw (one-tile wide regimes).  One launch for one tile, two for
+// several.  Off: nothing.
+void enqueue_diag(fbsmi_lg_sweep* s, hipStream_t st, int row, bool rows) {
+    if (!s->diag.rows) return;
+    const LgDev& d = s->d;
+    const dim3 g(d.nb, d.C);
+    if (rows) k_lg_diag<1, 1><<<g, kBlock, 0, st>>>(d, s->diag, row);
+    else LG_ITEMS(s, k_lg_diag<ITEMS, 0><<<g, kBlock, 0, st>>>(d, s->diag, row));
+    if (d.nb > 1) k_lg_diag_top<<<dim3(1, d.C), kBlock, 0, st>>>(d, s->diag, row);
+}
+
 // ---- the launch sequence of one sweep on stream st, by regime ---------------------------------
 
 void sweep_prologue(fbsmi_lg_sweep* s, hipStream_t st, int chain, const WideGeom& w) {
@@ -4597,7 +4694,8 @@ void sweep_one_tile_persistent(fbsmi_lg_sweep* s, hipStream_t st) {
     LG_DMAX(s, k_lg_sweep1<DMAX><<<dim3(1, d.C), kBlock, 0, st>>>(d));
 }
 
-// one tile, wide (the drift product) or narrow while profiling (so that the steps can be timed): one launch per step
+// one tile, wide (the drift product) or narrow while profiling (so that the steps can be timed) or with diagnostics on (so that
+// a step's log-weights, which k_lg_sweep1 hands on inside one launch, can be read between two steps): one launch per step
 void sweep_one_tile_stepwise(fbsmi_lg_sweep* s, hipStream_t st, const WideGeom& w) {
     const LgDev& d = s->d;
     const int gwide = w.nst * w.nrt;
@@ -4607,11 +4705,14 @@ void sweep_one_tile_stepwise(fbsmi_lg_sweep* s, hipStream_t st, const WideGeom& 
     // (unpinned: + extra blocks that draw the next step's noise beside the step: one per 1024 elements, at most 16)
     const int extra = grid_1d((int64_t)d.N * d.du, 1024, 16);
     for (int k = 0; k < d.T; ++k) {
+        // what step k normalises: d.lw (k_lg_init, k_lgw_init, k_lg_step1) or the per-row terms a wide drift product left
+        enqueue_diag(s, st, k, d.wide && (k || d.ef));
         ProfScope p(s, 2, st);
         if (pinned) k_lgw_gemm<1><<<dim3(gwide * 8, d.C), kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3, 8 + ((2 * d.c0) & 7));
         else if (d.wide) k_lgw_gemm<1><<<dim3(gwide + extra, d.C), kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3, 0);
         else LG_DMAX(s, k_lg_step1<DMAX><<<dim3(1, d.C), kBlock, 0, st>>>(d, k));
     }
+    enqueue_diag(s, st, d.T, d.wide);
 }
 
 // Several tiles: the launches of a step in front of its propagation.  tree (N a power of two): normalise and publish the
@@ -4649,6 +4750,9 @@ void sweep_steps_wide(fbsmi_lg_sweep* s, hipStream_t st, const WideGeom& w) {
         gz = dim3(gtile.x + dz.nz, gtile.y);
     }
     for (int k = 0; k < d.T; ++k) {
+        // what step k normalises, d.lw and its tile partials: by k_lgw_init / k_lgw_lse, then by the end of the step before
+        // (k_lgw_gemm_fat<true> + k_lg_lwpart, or k_lgw_lse)
+        enqueue_diag(s, st, k, false);
         step_norm_cdf(s, st, k, false, gz, dz);
         ProfScope p(s, 2, st);
         k_lgw_anc<<<gz, kBlock, 0, st>>>(dz, k);
@@ -4658,6 +4762,7 @@ void sweep_steps_wide(fbsmi_lg_sweep* s, hipStream_t st, const WideGeom& w) {
         if (fat_rowsum) k_lg_lwpart<<<gtile, kBlock, 0, st>>>(d);   // tile partials of the log-weights the drift kernel left
         else k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);
     }
+    enqueue_diag(s, st, d.T, false);
 }
 
 // narrow, several tiles: two (tree), three or four (several slots per thread) launches per step
@@ -4673,6 +4778,8 @@ void sweep_steps_narrow(fbsmi_lg_sweep* s, hipStream_t st) {
     // N a power of two: the searches walk the summation tree, no cdf launch (k_lg_prop1t)
     const bool tree = s->tree_step && d.trW;
     for (int k = 0; k < d.T; ++k) {
+        // what step k normalises: every kernel that writes d.lw (k_lg_init, the propagation kernels) leaves its tile's partials
+        enqueue_diag(s, st, k, false);
         step_norm_cdf(s, st, k, tree, gtile, d);
         ProfScope p(s, 2, st);
         if (tree && two_slot && !d.plus1) {
@@ -4702,6 +4809,7 @@ void sweep_steps_narrow(fbsmi_lg_sweep* s, hipStream_t st) {
             LG_ITEMS(s, LG_DMAX(s, k_lg_propQ<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k)));
         }
     }
+    enqueue_diag(s, st, d.T, false);
 }
 
 // the backward pass (explicit: force-move tail and a second forward path; else backward scanning), parity view, chain step
@@ -4730,9 +4838,10 @@ void sweep_epilogue(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
 int enqueue_sweep(fbsmi_lg_sweep* s, hipStream_t st, int chain) {
     const LgDev& d = s->d;
     const WideGeom w(d);
+    s->ran = true;
     sweep_prologue(s, st, chain, w);
     if (d.N <= kBlock) {
-        if (d.wide || s->profile) sweep_one_tile_stepwise(s, st, w);
+        if (d.wide || s->profile || s->diag.rows) sweep_one_tile_stepwise(s, st, w);
         else sweep_one_tile_persistent(s, st);
         // log-weights / tile partial for the final-mode kernels
         if (d.wide) k_lgw_lse<<<dim3(d.nb, d.C), kBlock, 0, st>>>(d);
@@ -5064,6 +5173,40 @@ int fbsmi_lg_sweep_set_bridge(fbsmi_lg_sweep* s, const fbsmi_doob_bridge* b) {
     return FBSMI_OK;
 }
 
+namespace {
+// rows per chain: T + 1 for a sweep, T for a filter
+int set_diagnostics(fbsmi_lg_sweep* s, int enable, int nrows, const char* who) {
+    if (s->ran || s->graph_single || s->graph_chain)
+        return fail(FBSMI_ERR_ARG, std::string(who) + ": call it before the handle's first run");
+    if (!enable) {
+        s->diag.rows = nullptr;   // (the buffers stay with the handle)
+        return FBSMI_OK;
+    }
+    if (s->diag.rows) return FBSMI_OK;
+    DiagDev g{};
+    g.nrows = nrows;
+    if (dev_alloc(s, &g.q, (size_t)s->d.C * s->d.nb) || dev_alloc(s, &g.rows, (size_t)s->d.C * nrows * 2)) return FBSMI_ERR_HIP;
+    s->diag = g;
+    return FBSMI_OK;
+}
+
+int copy_diagnostics(fbsmi_lg_sweep* s, void* dst, int64_t* count, hipStream_t ust, const char* who) {
+    if (!s->diag.rows) return fail(FBSMI_ERR_ARG, std::string(who) + ": the handle has no diagnostics (set_diagnostics)");
+    const int64_t n = (int64_t)s->d.C * s->diag.nrows * 2;
+    if (count) *count = n;
+    if (dst) {
+        FBSMI_HIP_TRY(hipStreamSynchronize(s->stream));
+        FBSMI_HIP_TRY(hipMemcpyAsync(dst, s->diag.rows, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, ust));
+    }
+    return FBSMI_OK;
+}
+}  // namespace
+
+int fbsmi_lg_sweep_set_diagnostics(fbsmi_lg_sweep* s, int enable) {
+    if (!s) return fail(FBSMI_ERR_ARG, "lg_sweep_set_diagnostics: null handle");
+    return set_diagnostics(s, enable, s->d.T + 1, "lg_sweep_set_diagnostics");
+}
+
 int fbsmi_lg_sweep_set_group(fbsmi_lg_sweep* s, int32_t nchains_total, int32_t first_chain) {
     if (!s || nchains_total < s->d.C || first_chain < 0 || first_chain + s->d.C > nchains_total)
         return fail(FBSMI_ERR_ARG, "lg_sweep_set_group: bad arguments");
@@ -5123,6 +5266,7 @@ int fbsmi_lg_sweep_view(fbsmi_lg_sweep* s, int which, void* dst, int64_t* count,
         case 4: src = d.lwss; n = (int64_t)d.C * (d.T + 1) * d.N; break;
         case 5: src = d.us_star; n = (int64_t)d.C * (d.T + 1) * d.du; break;
         case 6: src = d.vs; n = (int64_t)d.C * (d.T + 1) * d.dv; break;
+        case 7: return copy_diagnostics(s, dst, count, (hipStream_t)stream, "lg_sweep_view");
         default: return fail(FBSMI_ERR_ARG, "lg_sweep_view: unknown view");
     }
     if (!src) n = 0;
@@ -5150,7 +5294,8 @@ namespace {
 void filter_narrow_one_launch(fbsmi_lg_filter* f, hipStream_t st) {
     fbsmi_lg_sweep* s = f->core;
     const LgDev& d = s->d;
-    LG_DMAX(s, k_filt_sweep1<DMAX><<<dim3(1, d.C), kBlock, 0, st>>>(d, f->u0s));
+    if (s->diag.rows) LG_DMAX(s, k_filt_sweep1<DMAX, DiagDev><<<dim3(1, d.C), kBlock, 0, st>>>(d, f->u0s, s->diag));
+    else LG_DMAX(s, k_filt_sweep1<DMAX><<<dim3(1, d.C), kBlock, 0, st>>>(d, f->u0s, NoDiag{}));
 }
 
 // wide, several logsumexp tiles: the prologue of a step is its own launches (row sums + partials, normalise, cumsum,
@@ -5161,6 +5306,7 @@ void filter_wide_tiles(fbsmi_lg_filter* f, hipStream_t st, const WideGeom& w) {
     const dim3 gall(w.nst * w.nrt, d.C), gu(w.nst * w.u_tiles, d.C), gv(w.nst * w.v_tiles(), d.C), gg(64, d.C);
     auto resample = [&](int kres) {
         k_lgw_lse<<<gtile, kBlock, 0, st>>>(d);
+        enqueue_diag(f->core, st, kres, false);   // d.lw and its tile partials, as k_filt_norm takes them
         k_filt_norm<1><<<gtile, kBlock, 0, st>>>(d);
         k_lg_cdf<1, 2><<<gtile, kBlock, 0, st>>>(d, d.T);
         k_lgwf_anc<<<gtile, kBlock, 0, st>>>(d, kres);
@@ -5197,12 +5343,14 @@ void filter_wide_one_tile(fbsmi_lg_filter* f, hipStream_t st, const WideGeom& w)
         for (int k = 0; k < d.T; ++k) {
             if (k == 0) k_lgw_gemm<3><<<gall, kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3 | pe, 0);
             else k_lgw_gemm<2><<<gall, kBlock, w.lds, st>>>(d, k, 0, w.nrt, w.Kp, w.S, 3 | pe, k - 1);
+            enqueue_diag(s, st, k, true);   // the per-row terms of step k, which the next launch's prologue sums and normalises
         }
         k_lgwf_final<<<dim3(1, d.C), kBlock, 0, st>>>(d);
     } else {
         // weight the current particles (rows >= du, no resampling), then resample + propagate (rows < du)
         k_lgw_gemm<3><<<gv, kBlock, w.lds, st>>>(d, 0, w.v_tile0, w.v_tiles(), w.Kp, w.S, 2 | pe, 0);
         for (int k = 0; k < d.T; ++k) {
+            enqueue_diag(s, st, k, true);   // the per-row terms the weighting product left (the propagation product writes none)
             k_lgw_gemm<2><<<gu, kBlock, w.lds, st>>>(d, k, 0, w.u_tiles, w.Kp, w.S, 1 | pe, k);
             if (k + 1 < d.T) k_lgw_gemm<3><<<gv, kBlock, w.lds, st>>>(d, k + 1, w.v_tile0, w.v_tiles(), w.Kp, w.S, 2 | pe, 0);
         }
@@ -5218,6 +5366,7 @@ void filter_narrow_tree(fbsmi_lg_filter* f, hipStream_t st) {
     LG_ITEMS(s, LG_DMAX(s, k_filt_init<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, f->u0s)));
     for (int k = 0; k < d.T; ++k) {
         if (d.flow == 0) LG_DMAX(s, k_filt_prop1t<DMAX><<<gpin, kBlock, 0, st>>>(d, k, k > 0, k > 0 ? k - 1 : 0, 1, 1));
+        enqueue_diag(s, st, k, false);   // d.lw and its tile partials (k_filt_init, k_filt_prop1t), as k_filt_norm takes them
         k_filt_norm<1, true><<<gpin, kBlock, 0, st>>>(d);
         if (d.flow == 1) LG_DMAX(s, k_filt_prop1t<DMAX><<<gpin, kBlock, 0, st>>>(d, k, 1, k, k + 1 < d.T ? 2 : 0, 1));
     }
@@ -5233,6 +5382,7 @@ void filter_narrow_general(fbsmi_lg_filter* f, hipStream_t st) {
     for (int k = 0; k < d.T; ++k) {
         if (d.flow == 0)
             LG_ITEMS(s, LG_DMAX(s, k_filt_prop<ITEMS, DMAX><<<gtile, kBlock, 0, st>>>(d, k, k > 0, k > 0 ? k - 1 : 0, 1, 1)));
+        enqueue_diag(s, st, k, false);   // d.lw and its tile partials (k_filt_init, k_filt_prop), as k_filt_norm takes them
         LG_ITEMS(s, k_filt_norm<ITEMS><<<gtile, kBlock, 0, st>>>(d));
         LG_ITEMS(s, k_lg_cdf<ITEMS, 2><<<gtile, kBlock, 0, st>>>(d, d.T));
         if (d.flow == 1)
@@ -5244,6 +5394,7 @@ void filter_narrow_general(fbsmi_lg_filter* f, hipStream_t st) {
 int enqueue_filter(fbsmi_lg_filter* f, hipStream_t st) {
     fbsmi_lg_sweep* s = f->core;
     const LgDev& d = s->d;
+    s->ran = true;
     k_filt_keys<<<dim3(1, d.C), kBlock, 0, st>>>(d);
     if (d.wide) {
         const WideGeom w(d);
@@ -5311,6 +5462,17 @@ int fbsmi_lg_filter_run(fbsmi_lg_filter* f, const uint32_t* keys, const float* v
     if (path)
         FBSMI_HIP_TRY(hipMemcpyAsync(path, d.uss, C * T1 * d.N * d.du * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     return join_out(s, ust);
+}
+
+int fbsmi_lg_filter_set_diagnostics(fbsmi_lg_filter* f, int enable) {
+    if (!f || !f->core) return fail(FBSMI_ERR_ARG, "lg_filter_set_diagnostics: null handle");
+    if (f->graph) return fail(FBSMI_ERR_ARG, "lg_filter_set_diagnostics: call it before the handle's first run");
+    return set_diagnostics(f->core, enable, f->core->d.T, "lg_filter_set_diagnostics");
+}
+
+int fbsmi_lg_filter_diag(fbsmi_lg_filter* f, void* dst, int64_t* count, void* stream) {
+    if (!f || !f->core) return fail(FBSMI_ERR_ARG, "lg_filter_diag: null handle");
+    return copy_diagnostics(f->core, dst, count, (hipStream_t)stream, "lg_filter_diag");
 }
 
 int fbsmi_lg_sweep_profile(fbsmi_lg_sweep* s, int enable) {

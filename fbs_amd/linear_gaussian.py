@@ -264,16 +264,21 @@ class LinearGaussianBridge:
         return self._cached(("bridge_tables", int(nsub)), make)
 
     def sweep_handle(self, nparticles: int, explicit_backward=True, explicit_final=False, store_path=None,
-                     nchains: int = 1, marg_y: bool = False):
-        """marg_y: every sweep re-draws the observation path by the Doob bridge (bridge_sampler, gibbs.py:17-20,130)."""
+                     nchains: int = 1, marg_y: bool = False, diagnostics: bool = False):
+        """marg_y: every sweep re-draws the observation path by the Doob bridge (bridge_sampler, gibbs.py:17-20,130).
+        diagnostics: the handle records (logsumexp, ESS) of every step's log-weights (LGSweep.diagnostics)."""
         store = (not explicit_backward) if store_path is None else bool(store_path)
         keyt = (int(nparticles), bool(explicit_backward), bool(explicit_final), store, int(nchains), bool(marg_y))
-        return self._cached(keyt, lambda: LGSweep(self, *keyt))
+        if not diagnostics:
+            return self._cached(keyt, lambda: LGSweep(self, *keyt))
+        return self._cached(keyt + ("diagnostics",), lambda: LGSweep(self, *keyt, diagnostics=True))
 
     def filter_handle(self, nparticles: int, flow: str, resampling: str = "stratified", store_path: bool = False,
-                      nchains: int = 1):
-        keyt = ("filter", int(nparticles), flow, resampling, bool(store_path), int(nchains))
-        return self._cached(keyt, lambda: LGFilter(self, int(nparticles), flow, resampling, bool(store_path), int(nchains)))
+                      nchains: int = 1, diagnostics: bool = False):
+        """diagnostics: the handle records (logsumexp, ESS) of every step's log-weights (LGFilter.diagnostics)."""
+        keyt = ("filter", int(nparticles), flow, resampling, bool(store_path), int(nchains)) + (("diagnostics",) if diagnostics else ())
+        return self._cached(keyt, lambda: LGFilter(self, int(nparticles), flow, resampling, bool(store_path), int(nchains),
+                                                   bool(diagnostics)))
 
     def backsim_handle(self, nslots: int, mode: str, nchains: int = 1):
         """The fused backward simulation on stored paths of `nslots` rows per time slice: mode 'smoother'
@@ -373,6 +378,10 @@ class _LGHandle:
     def _sq(self, t, axis=0):
         return t.squeeze(axis) if self.C == 1 else t
 
+    def _diag_dict(self, rows):
+        """rows ([C,] nrows, 2) -> {"lse": ([C,] nrows), "ess": ([C,] nrows)} (the names of ShardedEnsemble.diagnostics)."""
+        return {"lse": rows[..., 0].contiguous(), "ess": rows[..., 1].contiguous()}
+
 
 class LGSweep(_LGHandle):
     """Owns one fbsmi_lg_sweep handle (device buffers + captured hipGraph) for `nchains` chains.
@@ -383,10 +392,12 @@ class LGSweep(_LGHandle):
 
     _DESTROY = "fbsmi_lg_sweep_destroy"
 
-    def __init__(self, model: LinearGaussianBridge, nparticles, eb, ef, store, nchains=1, marg_y=False, _group=None):
+    def __init__(self, model: LinearGaussianBridge, nparticles, eb, ef, store, nchains=1, marg_y=False, _group=None,
+                 diagnostics=False):
         self.model = model
         self.nparticles, self.eb, self.ef, self.store, self.C = nparticles, eb, ef, store, int(nchains)
         self.marg_y = bool(marg_y)
+        self.has_diagnostics = bool(diagnostics)
         self.n_rows = nparticles + 1 if ef else nparticles
         self.children, self.h = [], None
         # A batch of four or more chains is driven as two handles of half the chains each, on their own streams: the step
@@ -420,7 +431,8 @@ class LGSweep(_LGHandle):
                 sz = [self.C // G + (1 if g < self.C % G else 0) for g in range(G)]
         if sz is not None and len(sz) > 1:
             first = np.cumsum([0] + sz[:-1])
-            self.children = [LGSweep(model, nparticles, eb, ef, store, n, marg_y, _group=(self.C, int(f))) for n, f in zip(sz, first)]
+            self.children = [LGSweep(model, nparticles, eb, ef, store, n, marg_y, _group=(self.C, int(f)), diagnostics=diagnostics)
+                             for n, f in zip(sz, first)]
             self._harr = (C.c_void_p * len(sz))(*[c.h for c in self.children])
             return
         h = C.c_void_p()
@@ -433,6 +445,8 @@ class LGSweep(_LGHandle):
                 _lib.call("fbsmi_lg_sweep_set_em_forward", self.h, C.byref(em))
             if self.marg_y:     # the Doob bridge of the observation path, 100 sub-steps per interval (gibbs.py:17-20)
                 _lib.call("fbsmi_lg_sweep_set_bridge", self.h, C.byref(model.bridge_tables(100)))
+            if self.has_diagnostics:
+                _lib.call("fbsmi_lg_sweep_set_diagnostics", self.h, 1)
         if _group is not None:
             _lib.call("fbsmi_lg_sweep_set_group", self.h, int(_group[0]), int(_group[1]))
 
@@ -505,7 +519,25 @@ class LGSweep(_LGHandle):
             buf = torch.empty(cnt.value, dtype=dtype, device=m.device)
             _lib.call("fbsmi_lg_sweep_view", self.h, which, buf.data_ptr(), C.byref(cnt), ops._stream())
             out[name] = self._sq(buf.reshape((Cn,) + shape))
+        if self.has_diagnostics:
+            out["diag"] = self._diag_rows()
         return out
+
+    def _diag_rows(self):
+        """View 7: the (lse, ess) rows ([C,] T+1, 2) of the last sweep.  A handle without diagnostics is refused by the library."""
+        if self.children:
+            return torch.cat([ch._diag_rows().reshape(ch.C, self.model.T + 1, 2) for ch in self.children], dim=0)
+        cnt = C.c_int64()
+        _lib.call("fbsmi_lg_sweep_view", self.h, 7, None, C.byref(cnt), ops._stream())
+        buf = torch.empty(cnt.value, dtype=torch.float32, device=self.model.device)
+        _lib.call("fbsmi_lg_sweep_view", self.h, 7, buf.data_ptr(), C.byref(cnt), ops._stream())
+        return self._sq(buf.reshape(self.C, self.model.T + 1, 2))
+
+    def diagnostics(self):
+        """{"lse": ([C,] T+1), "ess": ([C,] T+1)} of the last sweep (device tensors): per step, the logsumexp of the
+        unnormalised log-weights -- the increment of the log normalising constant -- and the effective sample size
+        (include/fbsmi.h, fbsmi_lg_sweep_set_diagnostics).  Needs sweep_handle(..., diagnostics=True)."""
+        return self._diag_dict(self._diag_rows())
 
     def profile(self, enable: bool):
         if self.children:
@@ -532,13 +564,26 @@ class LGFilter(_LGHandle):
     _RES = {"stratified": 0, "systematic": 1}
     _DESTROY = "fbsmi_lg_filter_destroy"
 
-    def __init__(self, model: LinearGaussianBridge, nparticles, flow, resampling, store_path, nchains=1):
+    def __init__(self, model: LinearGaussianBridge, nparticles, flow, resampling, store_path, nchains=1, diagnostics=False):
         self.model, self.n, self.flow, self.store, self.C = model, nparticles, flow, store_path, int(nchains)
+        self.has_diagnostics = bool(diagnostics)
         h = C.c_void_p()
         with torch.cuda.device(model.device):
             _lib.call("fbsmi_lg_filter_create", C.byref(model.struct), nparticles, self._FLOW[flow],
                       self._RES[resampling], int(store_path), self.C, C.byref(h))
-        self.h = h
+            self.h = h
+            if self.has_diagnostics:
+                _lib.call("fbsmi_lg_filter_set_diagnostics", self.h, 1)
+
+    def diagnostics(self):
+        """{"lse": ([C,] T), "ess": ([C,] T)} of the last run (device tensors): per step the logsumexp `_c` of the
+        log-weights (smc.py:66 / :145) and their effective sample size (include/fbsmi.h).  Needs
+        filter_handle(..., diagnostics=True); a handle without is refused by the library."""
+        cnt = C.c_int64()
+        _lib.call("fbsmi_lg_filter_diag", self.h, None, C.byref(cnt), ops._stream())
+        buf = torch.empty(cnt.value, dtype=torch.float32, device=self.model.device)
+        _lib.call("fbsmi_lg_filter_diag", self.h, buf.data_ptr(), C.byref(cnt), ops._stream())
+        return self._diag_dict(self._sq(buf.reshape(self.C, self.model.T, 2)))
 
     def run(self, key, vs, u0s, use_graph=True):
         """-> (particles ([C,] n, du), log-likelihood ([C]) tensor[, filtering path ([C,] T+1, n, du)])."""

@@ -243,10 +243,28 @@ typedef struct fbsmi_doob_bridge {
     const float* ddt;
 } fbsmi_doob_bridge;
 int fbsmi_lg_sweep_set_bridge(fbsmi_lg_sweep* s, const fbsmi_doob_bridge* b);
+/* Opt-in per-step diagnostics of the fused engines (the reference computes neither).  For a vector lw of n unnormalised
+ * float32 log-weights a diagnostic row is (lse, ess):
+ *   lse = the project's logsumexp of lw: the two-level tiled definition of include/fbsmi_math.h, tile fbsmi_tile(n);
+ *   ess = 1 / S, S the root of the canonical pairwise tree over w_i * w_i, w_i = fbsmi_expf(lw_i - lse); the division is
+ *         float32 and correctly rounded.
+ * These are the definitions of fbsmi_normalise_ess: no other numeric convention.  The vectors:
+ *   Gibbs sweep (n = nparticles, +1 with explicit_final): T + 1 rows per chain.  Row 0: the initial log-weights before
+ *     normalise (explicit_final: the init likelihood, gibbs.py:136-137; else the constant -log n vector, :143-144);
+ *     row k = 1..T: the likelihood_logpdf values of step k - 1 (csmc.py:145, before :146).
+ *   Filter flow 0 (bootstrap_filter): T rows, row k = log_weights of smc.py:65, its lse the _c of :66.
+ *   Filter flow 1 (pmcmc_filter_step): T rows, row k = log_ws of smc.py:144, its lse the _c of :145.
+ * fbsmi_lg_sweep_set_diagnostics(s, 1) allocates nchains * (T + 1) * 2 floats and adds the diagnostic launches to the
+ * handle's launch list (one graph replay per sweep still; narrow ensembles of one tile then take one launch per step instead
+ * of one per sweep).  Call it before the handle's first sweep (FBSMI_ERR_ARG afterwards); it combines with set_bridge,
+ * set_em_forward, set_group and fbsmi_lg_gibbs_chain.  The buffer holds the rows of the LAST sweep; view 7 fetches it.
+ * A handle without diagnostics launches exactly what it launched before these entry points existed. */
+int fbsmi_lg_sweep_set_diagnostics(fbsmi_lg_sweep* s, int enable);
 /* Parity views of the last sweep: copies view `which` into dst (device, nullable) and reports its
  * element count.  which: 0 final particles (n,du) row-major, 1 final normalised log-weights (n),
  * 2 As (T,n) int32, 3 uss (T+1,n,du), 4 log_wss (T+1,n) [2-4 only with store_path],
- * 5 us_star (T+1,du) and 6 vs (T+1,dv) of the sweep; each with a leading [nchains] axis; any other
+ * 5 us_star (T+1,du) and 6 vs (T+1,dv) of the sweep, 7 the diagnostic rows (T+1,2), [..,0] = lse, [..,1] = ess
+ * (FBSMI_ERR_ARG on a handle without diagnostics); each with a leading [nchains] axis; any other
  * `which` is FBSMI_ERR_ARG.  n = nparticles (+1 if explicit_final). */
 int fbsmi_lg_sweep_view(fbsmi_lg_sweep* s, int which, void* dst, int64_t* count, void* stream);
 /* Fused particle filters for the analytic model, stratified (resampling = 0) or systematic (1)
@@ -262,6 +280,11 @@ int fbsmi_lg_filter_create(const fbsmi_lg_model* model, int32_t nparticles, int 
 void fbsmi_lg_filter_destroy(fbsmi_lg_filter* f);
 int fbsmi_lg_filter_run(fbsmi_lg_filter* f, const uint32_t* keys, const float* vs, const float* u0s, float* uT,
                         float* loglik, float* path, int use_graph, void* stream);
+/* The diagnostics of fbsmi_lg_sweep_set_diagnostics (defined there) for a filter handle: call set_diagnostics before the
+ * handle's first run; fbsmi_lg_filter_diag copies the (nchains, T, 2) rows of the LAST run into dst (device, nullable) and
+ * reports their element count; FBSMI_ERR_ARG on a handle without diagnostics. */
+int fbsmi_lg_filter_set_diagnostics(fbsmi_lg_filter* f, int enable);
+int fbsmi_lg_filter_diag(fbsmi_lg_filter* f, void* dst, int64_t* count, void* stream);
 
 /* Fused particle-marginal Metropolis-Hastings for the analytic model: pmcmc_kernel (fbs/samplers/smc.py:171-258, with
  * delta = None or the pCN proposal of smc.py:161-168) for `nchains` chains in every launch, inside the loop of
