@@ -25,7 +25,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fbs_amd import ops  # noqa: E402
 from fbs_amd.images import ImageRestore  # noqa: E402
-from fbs_amd.samplers import gibbs_init, gibbs_kernel, pmcmc_kernel, stratified  # noqa: E402
+from fbs_amd.samplers import gibbs_init, gibbs_kernel, gibbs_kernel_batched, pmcmc_kernel, stratified  # noqa: E402
 from fbs_amd.score import ScoreBridge  # noqa: E402
 from fbs_amd.sdes import StationaryConstLinearSDE, StationaryLinLinearSDE  # noqa: E402
 from fbs_amd.unet import UNet  # noqa: E402
@@ -54,6 +54,7 @@ def main(argv=None):
     p.add_argument('--dim', type=int, default=64, help='UNet width (64 in the reference).')
     p.add_argument('--fp32', action='store_true', help='float32 network instead of bf16 autocast.')
     p.add_argument('--chunk', type=int, default=4096, help='Particles per network call (a power of two: MIOpen ships kernels for those batch sizes; bigger calls are faster per particle).')
+    p.add_argument('--batch', type=int, default=1, help="gibbs* methods: test images that advance together, one network call per step for all of them (1: one image at a time).")
     p.add_argument('--outdir', type=str, default='./imgs/results')
     p.add_argument('--quiet', action='store_true')
     args = p.parse_args(argv)
@@ -108,6 +109,51 @@ def main(argv=None):
               likelihood_logpdf=sb.likelihood_logpdf)
     os.makedirs(args.outdir, exist_ok=True)
     out = None
+    if args.batch > 1 and 'gibbs' in args.method:
+        # Groups of --batch test images advance together (gibbs_kernel_batched): one network call per step for the group.
+        # Every image keeps the keys of the sequential run: an image consumes 1 + nsamples splits of the `key` chain (one
+        # for gibbs_init, one per sweep), so its keys follow from its position alone.
+        jobs = []
+        for k in range(args.ny0s):
+            data_key, subkey = ops.split(data_key)
+            if k < args.start_from:
+                continue
+            k_img, k_mask = ops.split(subkey)
+            key, k_init = ops.split(key)
+            k_sweeps = np.zeros((args.nsamples, 2), np.uint32)
+            for i in range(args.nsamples):
+                key, k_sweeps[i] = ops.split(key)
+            jobs.append((k, k_img, k_mask, k_init, k_sweeps))
+        suffix = f'-gibbs{"-eb" if eb else ""}{"-ef" if ef else ""}{"-marg" if args.marg else ""}'
+        for g0 in range(0, len(jobs), args.batch):
+            group = jobs[g0:g0 + args.batch]                                       # the last group may be smaller
+            masks, y0s, heads, x0s = [], [], [], []
+            for k, k_img, k_mask, k_init, _ in group:
+                test_img = ops.uniform(k_img, (resolution, resolution, nchannels), device=dev)
+                mask = ds.gen_mask(k_mask)
+                _, test_y0 = ds.unpack(test_img, mask)
+                head = os.path.join(args.outdir, f'{args.dataset}-{task}-{args.sde}-{args.nparticles}-{k}')
+                np.savez(head + '-true', test_img=test_img.cpu().numpy())
+                x0, _ = gibbs_init(k_init, test_y0, x_shape, ts, sb.fwd_sampler, sde, sb.unpack,      # per image
+                                   nparticles=args.nparticles, method=args.init_method, marg_y=args.marg, mask_=mask, **cl)
+                np.save(head + '-gibbs-init', ds.concat(x0.unsqueeze(0), test_y0, mask)[0].cpu().numpy())
+                masks.append(mask), y0s.append(test_y0), heads.append(head), x0s.append(x0)
+            x0s = torch.stack(x0s, 0)
+            bs_stars = np.zeros((len(group), nsteps + 1), np.int32)
+            restored = np.zeros((len(group), args.nsamples, resolution, resolution, nchannels), np.float32)
+            for i in range(args.nsamples):
+                keys_i = np.stack([job[4][i] for job in group], 0)
+                x0s, _, bs_stars, acc = gibbs_kernel_batched(keys_i, x0s, y0s, None, bs_stars, ts, sb.fwd_sampler, sde,
+                                                             sb.unpack, args.nparticles, marg_y=args.marg,
+                                                             explicit_backward=eb, explicit_final=ef, mask_=masks, **cl)
+                for b in range(len(group)):
+                    restored[b, i] = ds.concat(x0s[b].unsqueeze(0), y0s[b], masks[b])[0].cpu().numpy()
+                if not args.quiet:
+                    print(f'{task} | Gibbs x{len(group)} | iter: {i}, acc: {float(acc.float().mean()):.3f}')
+            for b in range(len(group)):
+                np.save(heads[b] + suffix, restored[b])
+            out = restored[-1]
+        return out
     for k in range(args.ny0s):
         data_key, subkey = ops.split(data_key)
         if k < args.start_from:

@@ -12,7 +12,8 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip",
-                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip", "fbsmi_bs.hip", "fbsmi_kf.hip", "fbsmi_kf_em.hip")]
+                                                  "fbsmi_tw.hip", "fbsmi_csgm.hip", "fbsmi_bs.hip", "fbsmi_kf.hip", "fbsmi_kf_em.hip",
+                                                  "fbsmi_batch.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", "fbsmi_device.h"), os.path.join(_HERE, "csrc", "fbsmi_host.h"),
                 os.path.join(_HERE, "csrc", "fbsmi_em_path.h"), os.path.join(_HERE, "csrc", "fbsmi_kf_em.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi.h"), os.path.join(_HERE, "..", "include", "fbsmi_math.h"),
@@ -180,6 +181,11 @@ class EMMaskStruct(C.Structure):
                 ("role", C.c_void_p)]
 
 
+class EMMaskBatchStruct(C.Structure):
+    _fields_ = [("du", C.c_int32), ("dv", C.c_int32), ("nmasks", C.c_int32), ("u_off", C.c_void_p), ("v_off", C.c_void_p),
+                ("role", C.c_void_p)]
+
+
 class EMPlanStruct(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("kernel", "pair", "vec", "ku", "nU", "nV", "vfirst", "nseg", "lnet_bytes",
                                          "lds_bytes", "grid")]
@@ -284,6 +290,11 @@ SIGNATURES = {
                                        _i64, _vp, _vp, _vp, C.POINTER(EMPlanStruct)]),
     "fbsmi_em_transition_logpdf_plan": (C.c_int, [C.POINTER(EMMaskStruct), _vp, _vp, C.c_int, C.c_int, _vp, _i64, _vp,
                                                   C.POINTER(EMPlanStruct)]),
+    "fbsmi_normalise_batched": (C.c_int, [_vp, _i64, _i64, C.c_int, _vp, _vp, _vp]),
+    "fbsmi_cond_killing_batched": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "fbsmi_em_concat_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _vp, _vp, _i64, _i64, C.c_int, _vp, _vp]),
+    "fbsmi_em_finish_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _vp, _vp, C.c_int, C.c_int, _f, _f, _f, _f, _vp,
+                                          _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     # include/fbsmi_nn.h
     "fbsmi_nn_linear_attention": (C.c_int, [_vp, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp]),
     "fbsmi_nn_qkv_linear_attention": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),

@@ -1,0 +1,412 @@
+// fbsmi_batch.hip -- the closure tier's sampler operations for B independent ensembles that advance in lockstep (the test
+// images of one run, the chains of one image): one launch per operation for all of them.
+//
+//   fbsmi_normalise_batched     row b = fbsmi_normalise on lw[b]
+//   fbsmi_cond_killing_batched  row b = fbsmi_cond_resample(kind 1, keys[b], w[b], i[b], j[b], conditional)
+//   fbsmi_em_concat_batched     ensemble b = fbsmi_em_concat
+//   fbsmi_em_finish_batched     ensemble b = fbsmi_em_finish with n_total = n, row0 = 0, net_A = NULL
+//
+// each bit for bit.  An ensemble has 1 <= n <= 1024 rows, so everything the single-ensemble entry points spread over
+// several launches and a workspace in memory -- the two-level logsumexp, the canonical-tree CDFs, the searches, the draws --
+// fits ONE workgroup per ensemble and its LDS.  The trees are built in place in LDS the way k_top_scan (fbsmi_prims.hip)
+// builds the top-level tree: an up-sweep over the element index, zero padded to a power of two, then the two-value descent
+// of fbsmi_device.h per element.  Padding with zeros and the number of levels above the data do not change a bit (0 + x is
+// exact), so the result is the tree fbsmi_cumsum / fbsmi_sum / fbsmi_logsumexp define whatever their tiling was.
+//
+// The two image kernels are plain: a workgroup per particle row, a thread per element.  The step they belong to spends
+// its time in the network; the dispatch variants of fbsmi_em.hip are not repeated here.  gfx950 only.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/fbsmi.h"
+#include "fbsmi_device.h"
+#include "fbsmi_host.h"
+
+namespace fbsmi {
+
+namespace {
+
+constexpr int kMaxRows = 1024;          // rows of one ensemble: one thread each
+constexpr int kLseTile = 256;           // fbsmi_tile(n) for n <= 131072 (include/fbsmi_math.h)
+constexpr int kMaxSeg = 4096;           // 256-element segments of an observed part: dv <= 2^20
+
+// In-place up-sweep of the canonical tree over a[0, np), np a power of two, up to blocks of `top` elements: afterwards
+// a[q * s + s - 1] is the tree sum of the aligned block q of s elements, for every power of two s <= top.  Every thread of
+// the workgroup calls it; it starts and ends with a barrier.
+__device__ __forceinline__ void lds_upsweep(float* a, int np, int top) {
+    for (int d = 1; d < top; d <<= 1) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < np / (2 * d); i += blockDim.x) {
+            const int r = (i + 1) * 2 * d - 1;
+            a[r] = a[r - d] + a[r];
+        }
+    }
+    __syncthreads();
+}
+
+// scan value of element e from the up-swept tree (the E of its leaf)
+__device__ __forceinline__ float lds_scan_at(const float* a, int np, int e) {
+    float P = 0.0f, E = a[np - 1];
+    int pos = 0;
+    for (int d = np >> 1; d >= 1; d >>= 1) {
+        const float t = P + a[pos + d - 1];
+        if (e & d) {
+            P = t;
+            pos += d;
+        } else {
+            E = t;
+        }
+    }
+    return E;
+}
+
+// ------------------------------------------------------------------------------------------------
+// normalise: blockDim.x = np = next_pow2(n) (at least 64), thread e owns element e
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kMaxRows) k_normalise_b(const float* __restrict__ lw, int n, int np, int log_space,
+                                                          float* __restrict__ out, float* __restrict__ out_lse) {
+    __shared__ float tr[kMaxRows];
+    __shared__ float smax[kMaxRows / 64];
+    const int b = blockIdx.x, e = threadIdx.x;
+    const float l = e < n ? lw[(int64_t)b * n + e] : -__builtin_inff();
+    const float mw = wave_max(l);
+    if ((e & 63) == 0) smax[e >> 6] = mw;
+    __syncthreads();
+    // per-tile maxima of the two-level logsumexp: tile q = elements [256 q, 256 q + 256)
+    const int tile = np < kLseTile ? np : kLseTile, wpt = tile >> 6 ? tile >> 6 : 1;
+    const int ntile = np / tile, nb = (n + kLseTile - 1) / kLseTile;
+    float mt[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float m = -__builtin_inff();
+        for (int w = 0; w < wpt; ++w)
+            if (q < ntile) m = fmaxf(m, smax[q * wpt + w]);
+        mt[q] = m;
+    }
+    const int myq = e / tile;
+    float mine = mt[0];
+#pragma unroll
+    for (int q = 1; q < 4; ++q) mine = myq == q ? mt[q] : mine;
+    tr[e] = fbsmi_expf(l - finite_or_zero(mine));   // exp(-inf - m') = 0 beyond n: the zero padding
+    lds_upsweep(tr, np, tile);
+    const float Mp = finite_or_zero(fmaxf(fmaxf(mt[0], mt[1]), fmaxf(mt[2], mt[3])));
+    float a[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        a[q] = q < nb ? tr[(q < ntile ? q : 0) * tile + tile - 1] * fbsmi_expf(finite_or_zero(mt[q]) - Mp) : 0.0f;
+    const float s01 = a[0] + a[1], s23 = a[2] + a[3];
+    const float tot = s01 + s23;
+    const float lse = fbsmi_logf(tot) + Mp;
+    if (e == 0 && out_lse) out_lse[b] = lse;
+    if (e < n) {
+        const float v = l - lse;
+        out[(int64_t)b * n + e] = log_space ? v : fbsmi_expf(v);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// conditional killing (csmc/resamplings.py:40-88; k_killing_finish and fbsmi_cond_resample in fbsmi_prims.hip)
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kMaxRows) k_cond_killing_b(const uint32_t* __restrict__ keys, const float* __restrict__ w,
+                                                             const int32_t* __restrict__ iref, const int32_t* __restrict__ jref,
+                                                             int n, int np, int32_t* __restrict__ idx) {
+    __shared__ float sw[kMaxRows], tr[kMaxRows], cdf[kMaxRows], cdfJ[kMaxRows];
+    __shared__ float smax[kMaxRows / 64];
+    __shared__ int s_shift;
+    const int b = blockIdx.x, e = threadIdx.x;
+    const int32_t i_ref = iref[b], j_ref = jref[b];
+    const float we = e < n ? w[(int64_t)b * n + e] : 0.0f;
+    sw[e] = we;
+    const float mw = wave_max(e < n ? we : -__builtin_inff());
+    if ((e & 63) == 0) smax[e >> 6] = mw;
+    __syncthreads();
+    float w_max = -__builtin_inff();
+    for (int q = 0; q < (np >> 6); ++q) w_max = fmaxf(w_max, smax[q]);
+    // J_prob = (1 - w / w_max) / n with [i] = 0; its total gives J_prob[i] = max(1 - total, 0)
+    const float jp = e < n ? (1.0f - we / w_max) / (float)n : 0.0f;
+    tr[e] = e == i_ref ? 0.0f : jp;
+    lds_upsweep(tr, np, np);
+    const float J_i = fmaxf(1.0f - tr[np - 1], 0.0f);
+    __syncthreads();
+    tr[e] = (e == i_ref && e < n) ? J_i : jp;
+    lds_upsweep(tr, np, np);
+    cdfJ[e] = lds_scan_at(tr, np, e);
+    __syncthreads();
+    tr[e] = we;
+    lds_upsweep(tr, np, np);
+    cdf[e] = lds_scan_at(tr, np, e);
+    __syncthreads();
+    const int levels = bisect_levels(n);
+    // the three sub-keys of split(key, 3): kill test, redraw, rotation
+    const uint32_t k0 = keys[2 * b], k1 = keys[2 * b + 1];
+    uint32_t a0, a1, b0, b1, c0, c1;
+    split_at(k0, k1, 3, 0, a0, a1);
+    split_at(k0, k1, 3, 1, b0, b1);
+    if (e == 0) {
+        split_at(k0, k1, 3, 2, c0, c1);
+        const float u3 = uniform_at(c0, c1, 1, 0);
+        const int32_t J = searchsorted_left(cdfJ, n, levels, cdfJ[n - 1] * (1.0f - u3));
+        long long s = ((long long)j_ref - J) % n;
+        if (s < 0) s += n;
+        s_shift = (int)s;
+    }
+    __syncthreads();
+    if (e < n) {
+        int32_t src = e - s_shift;
+        if (src < 0) src += n;
+        const float ws = sw[src];
+        const float u1 = uniform_at(a0, a1, (uint64_t)n, (uint64_t)src);
+        int32_t a = src;
+        if (u1 * w_max >= ws) {
+            const float u2 = uniform_at(b0, b1, (uint64_t)n, (uint64_t)src);
+            a = searchsorted_left(cdf, n, levels, cdf[n - 1] * (1.0f - u2));
+        }
+        if (e == j_ref) a = i_ref;
+        idx[(int64_t)b * n + e] = a;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// the image step: one workgroup of kBlock threads per particle row of the flat (B * n) axis
+// ------------------------------------------------------------------------------------------------
+struct BatchArgs {
+    const float* us;
+    const int32_t* A;
+    const void* net;
+    const float* v;
+    const float* v_prev;
+    const uint32_t* keys;
+    const int32_t* pin_row;
+    const float* pin_value;
+    float* us_new;
+    float* lw;
+    const int32_t* u_off;
+    const int32_t* v_off;
+    const int32_t* role;
+    void* img;
+    int32_t du, dv, nmasks, n;
+    float cx, cs, dt, sd;
+};
+
+__device__ __forceinline__ float bf16_bits_to_f32(unsigned short h) { return fbsmi_u2f((uint32_t)h << 16); }
+
+// round to nearest even; NaN stays NaN
+__device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
+    const uint32_t u = fbsmi_f2u(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
+    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+template <int NETDT>
+__device__ __forceinline__ float net_value(const void* net, int64_t at) {
+    if (NETDT == 0) return ((const float*)net)[at];
+    return bf16_bits_to_f32(((const unsigned short*)net)[at]);
+}
+
+template <int MODE>
+__device__ __forceinline__ float reverse_drift(float cx, float cs, float x, float s) {
+    if (MODE == 1) return s;
+    const float t1 = cx * x, t2 = cs * s;
+    return t1 + t2;
+}
+
+// the ancestor of row r of ensemble b, kept inside the ensemble whatever the index array holds
+__device__ __forceinline__ int64_t source_row(const BatchArgs& a, int b, int r) {
+    if (!a.A) return r;
+    const int32_t s = a.A[(int64_t)b * a.n + r];
+    return s < 0 ? 0 : (s > a.n - 1 ? a.n - 1 : s);
+}
+
+template <int OUTDT>
+__global__ void __launch_bounds__(kBlock) k_em_concat_b(const BatchArgs a) {
+    const int64_t row = blockIdx.x;
+    const int b = (int)(row / a.n), r = (int)(row - (int64_t)b * a.n);
+    const int D = a.du + a.dv;
+    const int32_t* __restrict__ role = a.role + (a.nmasks == 1 ? 0 : (int64_t)b * D);
+    const float* __restrict__ x = a.us + ((int64_t)b * a.n + source_row(a, b, r)) * a.du;
+    const float* __restrict__ vp = a.v_prev + (int64_t)b * a.dv;
+    for (int e = threadIdx.x; e < D; e += kBlock) {
+        const int o = role[e];
+        const float xv = o >= 0 ? x[o] : vp[~o];
+        if (OUTDT == 0) ((float*)a.img)[row * D + e] = xv;
+        else ((unsigned short*)a.img)[row * D + e] = f32_to_bf16_bits(xv);
+    }
+}
+
+template <int NETDT, int MODE>
+__global__ void __launch_bounds__(kBlock) k_em_finish_b(const BatchArgs a) {
+    __shared__ float seg[kMaxSeg];
+    const int64_t row = blockIdx.x;
+    const int b = (int)(row / a.n), r = (int)(row - (int64_t)b * a.n);
+    const int du = a.du, dv = a.dv, D = du + dv;
+    const int mb = a.nmasks == 1 ? 0 : b;
+    const int64_t net_row = row * D;
+    if (a.us_new) {
+        // us_new[r] = (x + drift * dt) + sd * z, z = row r of normal(keys[b], (n, du)); the pinned row takes its value
+        const int32_t* __restrict__ u_off = a.u_off + (int64_t)mb * du;
+        const float* __restrict__ x = a.us + ((int64_t)b * a.n + source_row(a, b, r)) * du;
+        float* __restrict__ y = a.us_new + row * du;
+        const uint32_t k0 = a.keys[2 * b], k1 = a.keys[2 * b + 1];
+        const uint64_t ntot = (uint64_t)a.n * (uint64_t)du;
+        const bool pinned = a.pin_row && a.pin_row[b] == r;
+        for (int p = threadIdx.x; p < du; p += kBlock) {
+            float out;
+            if (pinned) {
+                out = a.pin_value[(int64_t)b * du + p];
+            } else {
+                const float xv = x[p];
+                const float s = net_value<NETDT>(a.net, net_row + u_off[p]);
+                const float z = normal_from_bits(random_bits_at(k0, k1, ntot, (uint64_t)r * du + p));
+                const float d = reverse_drift<MODE>(a.cx, a.cs, xv, s);
+                const float m = xv + d * a.dt;
+                const float nz = a.sd * z;
+                out = m + nz;
+            }
+            y[p] = out;
+        }
+    }
+    if (a.lw) {
+        // lw[r] = tree-sum_j ( log(2 pi sd^2) + (v[j] - (v_prev[j] + drift_j * dt))^2 / sd^2 ) / -2 over the index bits of j:
+        // four elements in the thread, six levels in the wave, the 256-element segment sums in LDS
+        const int32_t* __restrict__ v_off = a.v_off + (int64_t)mb * dv;
+        const float* __restrict__ v = a.v + (int64_t)b * dv;
+        const float* __restrict__ vp = a.v_prev + (int64_t)b * dv;
+        const int nseg = (dv + 255) >> 8;
+        const int nsp = next_pow2(nseg > 1 ? nseg : 1);
+        const float var = a.sd * a.sd;
+        const float lognorm = fbsmi_logf(6.2831855f * var);
+        for (int i = threadIdx.x; i < nsp; i += kBlock) seg[i] = 0.0f;
+        __syncthreads();
+        for (int s0 = 0; s0 < dv; s0 += 4 * kBlock) {   // uniform trip count: every wave takes part in every round
+            const int j0 = s0 + (int)threadIdx.x * 4;
+            float t[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                t[k] = 0.0f;
+                if (j0 + k < dv) {
+                    const float sv = net_value<NETDT>(a.net, net_row + v_off[j0 + k]);
+                    const float bv = vp[j0 + k];
+                    const float dr = reverse_drift<MODE>(a.cx, a.cs, bv, sv);
+                    const float m = bv + dr * a.dt;
+                    const float df = v[j0 + k] - m;
+                    const float sq = df * df;
+                    const float q = sq / var;
+                    t[k] = (lognorm + q) * -0.5f;
+                }
+            }
+            const float s01 = t[0] + t[1], s23 = t[2] + t[3];
+            TreePath path;
+            const float sum = wave_upsweep(s01 + s23, path);
+            const int sg = (s0 >> 8) + ((int)threadIdx.x >> 6);
+            if ((threadIdx.x & 63) == 0 && sg < nseg) seg[sg] = sum;
+        }
+        lds_upsweep(seg, nsp, nsp);
+        if (threadIdx.x == 0) a.lw[row] = seg[nsp - 1];
+    }
+}
+
+#define FBSMI_NEED(cond, msg) \
+    if (!(cond)) return fail(FBSMI_ERR_ARG, msg)
+#define FBSMI_LAUNCH_CHECK()                                                     \
+    do {                                                                         \
+        hipError_t e_ = hipGetLastError();                                       \
+        if (e_ != hipSuccess) return fail(FBSMI_ERR_HIP, hipGetErrorString(e_)); \
+    } while (0)
+
+int threads_for(int64_t n) {
+    const int np = next_pow2((int)n);
+    return np < 64 ? 64 : np;
+}
+
+constexpr int64_t kMaxGrid = ((int64_t)1 << 31) - 1;
+constexpr int64_t kMaxDraw = ((int64_t)1 << 32) - 4;   // fbsmi_em_finish's bound on the flat draw of one ensemble
+
+// the checks the two image entry points share; everything here reads values only
+int check_em(const char* who, const fbsmi_em_mask_batch* m, int64_t B, int64_t n) {
+    const std::string w(who);
+    FBSMI_NEED(m && m->u_off && m->role && (m->dv == 0 || m->v_off), w + ": null mask");
+    FBSMI_NEED(B >= 1 && n >= 1 && m->du >= 1 && m->dv >= 0, w + ": B, n and du must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, w + ": more than 1024 rows per ensemble");
+    FBSMI_NEED(m->nmasks == 1 || m->nmasks == B, w + ": nmasks must be 1 or B");
+    FBSMI_NEED(n * (int64_t)m->du <= kMaxDraw, w + ": the noise draw exceeds 2^32 - 4 elements");
+    FBSMI_NEED(B * n <= kMaxGrid, w + ": too many rows for one grid");
+    if (m->dv > kMaxSeg * 256) return fail(FBSMI_ERR_UNSUPPORTED, w + ": observed part too long");
+    return FBSMI_OK;
+}
+
+}  // namespace
+
+}  // namespace fbsmi
+
+using namespace fbsmi;
+
+extern "C" {
+
+int fbsmi_normalise_batched(const float* lw, int64_t B, int64_t n, int log_space, float* out, float* out_lse,
+                            void* stream) {
+    FBSMI_NEED(lw && out, "normalise_batched: null pointer");
+    FBSMI_NEED(B >= 1 && n >= 1 && B <= kMaxGrid, "normalise_batched: B and n must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "normalise_batched: more than 1024 rows per ensemble");
+    const int np = threads_for(n);
+    k_normalise_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(lw, (int)n, np, log_space, out, out_lse);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_cond_killing_batched(const uint32_t* keys, const float* w, const int32_t* i, const int32_t* j, int64_t B,
+                               int64_t n, int32_t* idx, void* stream) {
+    FBSMI_NEED(keys && w && i && j && idx, "cond_killing_batched: null pointer");
+    FBSMI_NEED(B >= 1 && n >= 1 && B <= kMaxGrid, "cond_killing_batched: B and n must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "cond_killing_batched: more than 1024 rows per ensemble");
+    const int np = threads_for(n);
+    k_cond_killing_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(keys, w, i, j, (int)n, np, idx);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_em_concat_batched(const fbsmi_em_mask_batch* mask, const float* us, const int32_t* A, const float* v_prev,
+                            int64_t B, int64_t n, int out_dtype, void* img, void* stream) {
+    const int rc = check_em("em_concat_batched", mask, B, n);
+    if (rc) return rc;
+    FBSMI_NEED(us && img && (mask->dv == 0 || v_prev), "em_concat_batched: null pointer");
+    FBSMI_NEED(out_dtype == 0 || out_dtype == 1, "em_concat_batched: out_dtype must be 0 or 1");
+    BatchArgs a = {};
+    a.us = us; a.A = A; a.v_prev = v_prev; a.role = mask->role; a.img = img;
+    a.du = mask->du; a.dv = mask->dv; a.nmasks = mask->nmasks; a.n = (int32_t)n;
+    const dim3 grid((unsigned)(B * n));
+    hipStream_t st = (hipStream_t)stream;
+    if (out_dtype == 0) k_em_concat_b<0><<<grid, kBlock, 0, st>>>(a);
+    else k_em_concat_b<1><<<grid, kBlock, 0, st>>>(a);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_em_finish_batched(const fbsmi_em_mask_batch* mask, const float* us, const int32_t* A, const void* net,
+                            int net_dtype, int mode, float cx, float cs, float dt, float sd, const float* v,
+                            const float* v_prev, const uint32_t* keys, int64_t B, int64_t n, const int32_t* pin_row,
+                            const float* pin_value, float* us_new, float* lw, void* stream) {
+    const int rc = check_em("em_finish_batched", mask, B, n);
+    if (rc) return rc;
+    FBSMI_NEED(net && (us_new || lw), "em_finish_batched: null network output, or neither us_new nor lw asked for");
+    FBSMI_NEED((net_dtype == 0 || net_dtype == 1) && (mode == 0 || mode == 1), "em_finish_batched: bad net_dtype or mode");
+    FBSMI_NEED(!us_new || (us && keys && us_new != us), "em_finish_batched: the proposal needs us and keys, and us_new must not alias us");
+    FBSMI_NEED(!lw || mask->dv == 0 || (v && v_prev), "em_finish_batched: the weights need v and v_prev");
+    FBSMI_NEED(!pin_row || pin_value, "em_finish_batched: pin_row without pin_value");
+    BatchArgs a = {};
+    a.us = us; a.A = A; a.net = net; a.v = v; a.v_prev = v_prev; a.keys = keys;
+    a.pin_row = us_new ? pin_row : nullptr; a.pin_value = pin_value; a.us_new = us_new; a.lw = lw;
+    a.u_off = mask->u_off; a.v_off = mask->v_off;
+    a.du = mask->du; a.dv = mask->dv; a.nmasks = mask->nmasks; a.n = (int32_t)n;
+    a.cx = cx; a.cs = cs; a.dt = dt; a.sd = sd;
+    const dim3 grid((unsigned)(B * n));
+    hipStream_t st = (hipStream_t)stream;
+    if (net_dtype == 0 && mode == 0) k_em_finish_b<0, 0><<<grid, kBlock, 0, st>>>(a);
+    else if (net_dtype == 0) k_em_finish_b<0, 1><<<grid, kBlock, 0, st>>>(a);
+    else if (mode == 0) k_em_finish_b<1, 0><<<grid, kBlock, 0, st>>>(a);
+    else k_em_finish_b<1, 1><<<grid, kBlock, 0, st>>>(a);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+}  // extern "C"

@@ -215,6 +215,47 @@ def normalise(log_weights: torch.Tensor, log_space: bool = False, return_lse: bo
     return (out, lse.reshape(())) if return_lse else out
 
 
+def keys_to_device(keys, device) -> torch.Tensor:
+    """(..., 2) uint32 host keys -> an int32 device tensor holding the same bits (what the batched kernels read)."""
+    if isinstance(keys, torch.Tensor):
+        _require_cuda(keys, "keys")
+        return keys.contiguous()
+    k = np.ascontiguousarray(keys, dtype=np.uint32)
+    return torch.from_numpy(k.view(np.int32)).to(device)
+
+
+def normalise_batched(log_weights: torch.Tensor, log_space: bool = False, return_lse: bool = False):
+    """``normalise`` on every row of log_weights (B, n), n <= 1024, in one launch; row b has the bits of
+    ``normalise(log_weights[b])``.  return_lse adds the (B,) logsumexps."""
+    lw = _f32c(log_weights, "log_weights")
+    if lw.dim() != 2:
+        raise ValueError("normalise_batched wants log_weights of shape (B, n)")
+    B, n = lw.shape
+    out = torch.empty_like(lw)
+    lse = torch.empty(B, dtype=torch.float32, device=lw.device) if return_lse else None
+    _lib.call("fbsmi_normalise_batched", lw.data_ptr(), B, n, int(bool(log_space)), out.data_ptr(),
+              lse.data_ptr() if return_lse else None, _stream())
+    return (out, lse) if return_lse else out
+
+
+def cond_killing_batched(keys, weights: torch.Tensor, i: torch.Tensor, j: torch.Tensor) -> torch.Tensor:
+    """Conditional killing resampling (csmc/resamplings.py:40-88) of B ensembles in one launch: row b of the result
+    (B, n) int32 has the bits of ``killing(keys[b], weights[b], i[b], j[b], True)``.  keys (B, 2) uint32 on the host or
+    their bits as an int32 device tensor; i, j (B,) integer tensors on the device; n <= 1024."""
+    w = _f32c(weights, "weights")
+    if w.dim() != 2:
+        raise ValueError("cond_killing_batched wants weights of shape (B, n)")
+    B, n = w.shape
+    kd = keys_to_device(keys, w.device)
+    ii, jj = (torch.as_tensor(x, device=w.device).to(torch.int32).contiguous() for x in (i, j))
+    if kd.numel() != 2 * B or ii.numel() != B or jj.numel() != B:
+        raise ValueError("cond_killing_batched: keys (B, 2), i (B,) and j (B,) must match weights (B, n)")
+    idx = torch.empty((B, n), dtype=torch.int32, device=w.device)
+    _lib.call("fbsmi_cond_killing_batched", kd.data_ptr(), w.data_ptr(), ii.data_ptr(), jj.data_ptr(), B, n,
+              idx.data_ptr(), _stream())
+    return idx
+
+
 def searchsorted(a: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     a = _f32c(a, "a").reshape(-1)
     qq = _f32c(q, "q")

@@ -3,5 +3,6 @@ from .smc import (bootstrap_filter, filter_conditional_sampler, pmcmc_chain, pmc
                   twisted_smc)
 from .resampling import multinomial, systematic, stratified, killing
 from .gibbs import gibbs_init, gibbs_kernel
+from .gibbs_batched import gibbs_kernel_batched
 from ..lg_kalman import kalman_conditional_sampler, kalman_path_sampler
 from ..gaussian_sb import sb_kalman_conditional_sampler, sb_kalman_path_sampler

@@ -53,6 +53,26 @@ class EMMask:
         return C.byref(self.struct)
 
 
+class EMMaskBatch:
+    """The masks of B ensembles that advance in lockstep (include/fbsmi.h, fbsmi_em_mask_batch): the tables of one mask
+    shared by all, or of B masks of one shape (same du and dv) stacked."""
+
+    def __init__(self, ems):
+        ems = list(ems)
+        if not ems or any((m.du, m.dv) != (ems[0].du, ems[0].dv) for m in ems):
+            raise ValueError("the masks of one batch must have the same du and dv")
+        self.ems = ems                                     # keeps the tables' owners (and their key objects) alive
+        self.nmasks, self.du, self.dv, self.D = len(ems), ems[0].du, ems[0].dv, ems[0].D
+        stack = lambda name: torch.stack([getattr(m, name) for m in ems], 0).contiguous()
+        self.u_off, self.v_off, self.role = stack("u_off"), stack("v_off"), stack("role")
+        self.struct = _lib.EMMaskBatchStruct(self.du, self.dv, self.nmasks, self.u_off.data_ptr(), self.v_off.data_ptr(),
+                                             self.role.data_ptr())
+
+    @property
+    def ref(self):
+        return C.byref(self.struct)
+
+
 class ScoreBridge:
     def __init__(self, score_fn, dataset, sde, ts, chunk: int = 1024, mode: str = "score",
                  net_input_dtype=torch.float32, fwd_drift_fn=None):
@@ -75,6 +95,7 @@ class ScoreBridge:
         self.net_input_dtype = net_input_dtype
         self._cache = None
         self._masks = {}
+        self._mask_batches = {}
         self._buf = {}
         self.profile = None                                  # set to a dict to collect torch events per phase
         self.capture = None                                  # set to a dict: operands and results of the LAST fused step
@@ -175,6 +196,77 @@ class ScoreBridge:
                                 key=np.asarray(key_, np.uint32).copy(), pin=pin, row_slice=row_slice, us_new=us_new,
                                 lw=lw, coef=self._coef(t_prev), em=em)
         return us_new.reshape((us_new.shape[0],) + tuple(self.dataset.unobs_shape)), lw
+
+    # -- the fused step for B ensembles in lockstep ---------------------------------------------------
+    def em_mask_batch(self, masks, B: int) -> EMMaskBatch:
+        """The stacked tables of one mask (shared) or a list of B masks of one shape; built once per set of masks."""
+        if isinstance(masks, EMMaskBatch):
+            mb = masks
+        else:
+            lst = [masks] if hasattr(masks, "unobs_inds_ravelled") else list(masks)
+            if len(lst) > 1 and all(m is lst[0] for m in lst):
+                lst = lst[:1]
+            key = tuple(id(m) for m in lst)
+            mb = self._mask_batches.get(key)
+            if mb is None or any(e.mask is not m for e, m in zip(mb.ems, lst)):
+                mb = EMMaskBatch([self._em_mask(m) for m in lst])
+                self._mask_batches[key] = mb
+        if mb.nmasks not in (1, int(B)):
+            raise ValueError(f"{mb.nmasks} masks for {B} ensembles: pass one mask or one per ensemble")
+        return mb
+
+    @torch.no_grad()
+    def fused_step_batched(self, us, A, v, v_prev, t_prev, keys, masks, pins=None, want_us=True):
+        """``fused_step`` for B ensembles at the same time step: one fbsmi_em_concat_batched launch, the network in
+        `chunk`-row pieces over the flat B * n rows (a chunk may straddle ensembles), one fbsmi_em_finish_batched launch.
+        us (B, n, p, c); A (B, n) ancestors local to each ensemble, or None; v, v_prev (B, q, c); keys (B, 2) (host uint32,
+        or their bits on the device: ensemble b draws normal(keys[b], (n, p, c)) as a call of its own would); masks one
+        mask, a list of B masks of one shape, or an EMMaskBatch; pins = (rows (B,) int32 with -1 for none, values
+        (B, p, c)) or None.  want_us=False: weights only (keys and pins are not read).
+        -> (us_new (B, n, p, c) or None, lw (B, n)); ensemble b has the bits of its own ``fused_step`` whenever the
+        network's output row does not depend on which rows share its call."""
+        us3 = ops._f32c(us, "us")
+        B, n = int(us3.shape[0]), int(us3.shape[1])
+        us3 = us3.reshape(B, n, -1)
+        mb = self.em_mask_batch(masks, B)
+        if us3.shape[2] != mb.du:
+            raise ValueError(f"us rows hold {us3.shape[2]} floats, the masks' unobserved part {mb.du}")
+        self._cache = None                                   # the shared network buffer is about to be rewritten
+        dev = us3.device
+        A32 = A.to(torch.int32).contiguous() if A is not None else None
+        vv, vp = ops._f32c(v, "v").reshape(B, -1), ops._f32c(v_prev, "v_prev").reshape(B, -1)
+        w, h, c = self.dataset.image_shape
+        img = self._buffer("img", (B * n, w, h, c), self.net_input_dtype, dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.call("fbsmi_em_concat_batched", mb.ref, us3.data_ptr(), ptr(A32), vp.data_ptr(), B, n,
+                  _NET_DT[self.net_input_dtype], img.data_ptr(), ops._stream())
+        tf = self.T - float(t_prev)
+        net = None
+        for s in range(0, B * n, self.chunk):
+            y = self.score_fn(img[s:s + self.chunk], tf)
+            if net is None:
+                if y.dtype not in _NET_DT:
+                    y = y.float()
+                net = self._buffer("net", (B * n, mb.D), y.dtype, dev)
+            net[s:s + self.chunk] = y.reshape(-1, mb.D)
+        mode, cx, cs, sd = self._coef(t_prev)
+        us_new = torch.empty((B, n, mb.du), dtype=torch.float32, device=dev) if want_us else None
+        lw = torch.empty((B, n), dtype=torch.float32, device=dev)
+        kd = ops.keys_to_device(keys, dev) if want_us else None
+        pin_row = pin_val = None
+        if want_us and pins is not None:
+            pin_row = torch.as_tensor(pins[0], device=dev).to(torch.int32).contiguous()
+            pin_val = ops._f32c(pins[1], "pin values").reshape(B, -1)
+            if pin_row.numel() != B or pin_val.shape[1] != mb.du:
+                raise ValueError("pins must be (rows (B,), values (B, p, c))")
+        if want_us and kd.numel() != 2 * B:
+            raise ValueError("keys must be (B, 2)")
+        _lib.call("fbsmi_em_finish_batched", mb.ref, us3.data_ptr(), ptr(A32), net.data_ptr(), _NET_DT[net.dtype], mode,
+                  cx, cs, self.dt, sd, vv.data_ptr(), vp.data_ptr(), ptr(kd), B, n, ptr(pin_row), ptr(pin_val),
+                  ptr(us_new), lw.data_ptr(), ops._stream())
+        if us_new is not None:
+            us_new = us_new.reshape((B, n) + tuple(self.dataset.unobs_shape))
+        return us_new, lw
 
     def fused_weight_then_propose(self, us, v, v_prev, t_prev, key_, mask_, resample):
         """One step of pmcmc_filter_step (fbs/samplers/smc.py:144-150): weight the particles, resample,

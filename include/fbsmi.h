@@ -737,6 +737,45 @@ int fbsmi_em_finish_plan(const fbsmi_em_mask* mask, const void* us, const void* 
 int fbsmi_em_transition_logpdf_plan(const fbsmi_em_mask* mask, const void* us, const void* net, int net_dtype, int mode,
                                     const void* u, int64_t n, const void* lw, fbsmi_em_plan* plan);
 
+/* ---- the closure tier for B ensembles in lockstep (fbs_amd/csrc/fbsmi_batch.hip) -----------------
+ * B independent ensembles of n rows each (the test images of one run, the chains of one image) share the time grid, the
+ * SDE and the network, so a step is ONE launch per sampler operation for all of them and one network call on B * n rows.
+ * One workgroup per ensemble, everything of an ensemble in its LDS: no workspace.  1 <= n <= 1024; B is bounded by the
+ * grid only.  Decided on the host before any HIP call: FBSMI_ERR_ARG for a null pointer, B < 1 or n < 1, nmasks outside
+ * {1, B} and n * du > 2^32 - 4; FBSMI_ERR_UNSUPPORTED for n > 1024.
+ *
+ * Row b of out (B, n) = fbsmi_normalise on lw[b], bit for bit (the two-level logsumexp of include/fbsmi_math.h, sums in
+ * the canonical tree over the element index); out_lse (B), nullable, receives the logsumexp of every row. */
+int fbsmi_normalise_batched(const float* lw, int64_t B, int64_t n, int log_space, float* out, float* out_lse,
+                            void* stream);
+/* Row b of idx (B, n) = fbsmi_cond_resample(kind 1, keys[b], w[b], i[b], j[b], conditional = 1), bit for bit; the indices
+ * are local to the ensemble.  keys (B, 2), w (B, n), i (B), j (B): device arrays. */
+int fbsmi_cond_killing_batched(const uint32_t* keys, const float* w, const int32_t* i, const int32_t* j, int64_t B,
+                               int64_t n, int32_t* idx, void* stream);
+
+/* The masks of the B ensembles: nmasks == 1 (one mask for all) or nmasks == B; every mask has the same du and dv (the
+ * inpainting rectangles of one size, the super-resolution masks of one rate).  Tables as in fbsmi_em_mask, stacked:
+ * u_off (nmasks, du), v_off (nmasks, dv), role (nmasks, du + dv). */
+typedef struct fbsmi_em_mask_batch {
+    int32_t du, dv, nmasks;
+    const int32_t* u_off;
+    const int32_t* v_off;
+    const int32_t* role;
+} fbsmi_em_mask_batch;
+
+/* Ensemble b = fbsmi_em_concat: img[b * n + r] = concat(us[b][A[b][r]], v_prev[b]).  us (B, n, du), A (B, n) nullable
+ * (identity; ancestors local to the ensemble), v_prev (B, dv), img (B * n, D) float32 or bfloat16 (out_dtype 0 / 1). */
+int fbsmi_em_concat_batched(const fbsmi_em_mask_batch* mask, const float* us, const int32_t* A, const float* v_prev,
+                            int64_t B, int64_t n, int out_dtype, void* img, void* stream);
+/* Ensemble b = fbsmi_em_finish with n_total = n, row0 = 0, net_A = NULL, bit for bit: it draws normal(keys[b], (n, du))
+ * exactly as a call of its own would.  net (B * n, D); v, v_prev (B, dv); keys (B, 2); pin_row (B) nullable, -1 = no pin
+ * in that ensemble; pin_value (B, du); us_new (B, n, du) nullable (weights only), lw (B, n) nullable.  mode, cx, cs, dt,
+ * sd are shared: the ensembles are at the same time step. */
+int fbsmi_em_finish_batched(const fbsmi_em_mask_batch* mask, const float* us, const int32_t* A, const void* net,
+                            int net_dtype, int mode, float cx, float cs, float dt, float sd, const float* v,
+                            const float* v_prev, const uint32_t* keys, int64_t B, int64_t n, const int32_t* pin_row,
+                            const float* pin_value, float* us_new, float* lw, void* stream);
+
 /* HIP-event timing hooks: average duration in microseconds of the propagate ("Euler") kernel
  * over the launches since the last reset; 0 launches -> returns 0. Only measured when
  * fbsmi_lg_sweep_profile(s, 1) was set (events force non-graph launches). */
