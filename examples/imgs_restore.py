@@ -7,7 +7,9 @@ flags, same key schedule, same result arrays (`*-gibbs-eb-ef.npy`, `*-filter.npy
 baseline: whole-image particles, the twisting function's gradient through the score network by torch.autograd; result
 `*-twisted.npy`), `--method csgm` experiments/imgs/inpainting_csgm.py / supr_csgm.py (conditional score-based sampling: one
 reverse-SDE trajectory with the observed pixels re-noised every step; `*-csgm.npy`).  The closures are the bound methods of one fbs_amd.score.ScoreBridge, so
-every SMC step is two HIP kernels around one network evaluation (PyTorch-ROCm).
+every SMC step is two HIP kernels around one network evaluation (PyTorch-ROCm).  With `--batch B` the test images of the
+gibbs*, filter and pmcmc* methods advance in groups of B, one network evaluation per step for the group (fbs_amd.samplers
+gibbs_kernel_batched, gibbs_init_batched, pmcmc_kernel_batched); every image keeps the keys of the sequential run.
 
 The reference loads a trained checkpoint (`./checkpoints/<dataset>_<sde>_<epoch>.npz`, a flat `param` / `ema_param`
 vector in ravel_pytree order) and a dataset (`../datasets/mnist.npz`, `datasets/celeba_hq<res>.npy`); neither exists in
@@ -25,7 +27,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fbs_amd import ops  # noqa: E402
 from fbs_amd.images import ImageRestore  # noqa: E402
-from fbs_amd.samplers import gibbs_init, gibbs_kernel, gibbs_kernel_batched, pmcmc_kernel, stratified  # noqa: E402
+from fbs_amd.samplers import (gibbs_init, gibbs_init_batched, gibbs_kernel, gibbs_kernel_batched, pmcmc_kernel,  # noqa: E402
+                              pmcmc_kernel_batched, stratified)
 from fbs_amd.score import ScoreBridge  # noqa: E402
 from fbs_amd.sdes import StationaryConstLinearSDE, StationaryLinLinearSDE  # noqa: E402
 from fbs_amd.unet import UNet  # noqa: E402
@@ -54,7 +57,8 @@ def main(argv=None):
     p.add_argument('--dim', type=int, default=64, help='UNet width (64 in the reference).')
     p.add_argument('--fp32', action='store_true', help='float32 network instead of bf16 autocast.')
     p.add_argument('--chunk', type=int, default=4096, help='Particles per network call (a power of two: MIOpen ships kernels for those batch sizes; bigger calls are faster per particle).')
-    p.add_argument('--batch', type=int, default=1, help="gibbs* methods: test images that advance together, one network call per step for all of them (1: one image at a time).")
+    p.add_argument('--batch', type=int, default=1, help="'filter', 'gibbs*' and 'pmcmc*' methods: test images that advance together, one network call per step for all of them (1: one image at a time).")
+    p.add_argument('--batch_init', action='store_true', help="With --batch and a gibbs* method: the images' gibbs_init filters advance together too (gibbs_init_batched); by default gibbs_init runs per image.")
     p.add_argument('--outdir', type=str, default='./imgs/results')
     p.add_argument('--quiet', action='store_true')
     args = p.parse_args(argv)
@@ -109,48 +113,85 @@ def main(argv=None):
               likelihood_logpdf=sb.likelihood_logpdf)
     os.makedirs(args.outdir, exist_ok=True)
     out = None
-    if args.batch > 1 and 'gibbs' in args.method:
-        # Groups of --batch test images advance together (gibbs_kernel_batched): one network call per step for the group.
-        # Every image keeps the keys of the sequential run: an image consumes 1 + nsamples splits of the `key` chain (one
-        # for gibbs_init, one per sweep), so its keys follow from its position alone.
+    if args.batch > 1 and ('gibbs' in args.method or args.method == 'filter' or 'pmcmc' in args.method):
+        # Groups of --batch test images advance together (gibbs_kernel_batched, gibbs_init_batched, pmcmc_kernel_batched):
+        # one network call per step for the group.  Every image keeps the keys of the sequential run: an image consumes
+        # nsamples splits of the `key` chain for 'filter' (one per sample) and 1 + nsamples for gibbs (gibbs_init, then one
+        # per sweep) and pMCMC (the initial observation path, then one per iteration), so its keys follow from its
+        # position alone.
+        is_gibbs, is_filter = 'gibbs' in args.method, args.method == 'filter'
         jobs = []
         for k in range(args.ny0s):
             data_key, subkey = ops.split(data_key)
             if k < args.start_from:
                 continue
             k_img, k_mask = ops.split(subkey)
-            key, k_init = ops.split(key)
-            k_sweeps = np.zeros((args.nsamples, 2), np.uint32)
+            k_first = None
+            if not is_filter:
+                key, k_first = ops.split(key)
+            k_iters = np.zeros((args.nsamples, 2), np.uint32)
             for i in range(args.nsamples):
-                key, k_sweeps[i] = ops.split(key)
-            jobs.append((k, k_img, k_mask, k_init, k_sweeps))
-        suffix = f'-gibbs{"-eb" if eb else ""}{"-ef" if ef else ""}{"-marg" if args.marg else ""}'
+                key, k_iters[i] = ops.split(key)
+            jobs.append((k, k_img, k_mask, k_first, k_iters))
+        marg = "-marg" if args.marg else ""
+        suffix = f'-gibbs{"-eb" if eb else ""}{"-ef" if ef else ""}{marg}' if is_gibbs else (
+            f'-filter{marg}' if is_filter else f'-pmcmc-{delta}')
         for g0 in range(0, len(jobs), args.batch):
             group = jobs[g0:g0 + args.batch]                                       # the last group may be smaller
-            masks, y0s, heads, x0s = [], [], [], []
-            for k, k_img, k_mask, k_init, _ in group:
+            nb = len(group)
+            masks, y0s, heads = [], [], []
+            for k, k_img, k_mask, _, _ in group:
                 test_img = ops.uniform(k_img, (resolution, resolution, nchannels), device=dev)
                 mask = ds.gen_mask(k_mask)
                 _, test_y0 = ds.unpack(test_img, mask)
                 head = os.path.join(args.outdir, f'{args.dataset}-{task}-{args.sde}-{args.nparticles}-{k}')
                 np.savez(head + '-true', test_img=test_img.cpu().numpy())
-                x0, _ = gibbs_init(k_init, test_y0, x_shape, ts, sb.fwd_sampler, sde, sb.unpack,      # per image
-                                   nparticles=args.nparticles, method=args.init_method, marg_y=args.marg, mask_=mask, **cl)
-                np.save(head + '-gibbs-init', ds.concat(x0.unsqueeze(0), test_y0, mask)[0].cpu().numpy())
-                masks.append(mask), y0s.append(test_y0), heads.append(head), x0s.append(x0)
-            x0s = torch.stack(x0s, 0)
-            bs_stars = np.zeros((len(group), nsteps + 1), np.int32)
-            restored = np.zeros((len(group), args.nsamples, resolution, resolution, nchannels), np.float32)
-            for i in range(args.nsamples):
-                keys_i = np.stack([job[4][i] for job in group], 0)
-                x0s, _, bs_stars, acc = gibbs_kernel_batched(keys_i, x0s, y0s, None, bs_stars, ts, sb.fwd_sampler, sde,
-                                                             sb.unpack, args.nparticles, marg_y=args.marg,
-                                                             explicit_backward=eb, explicit_final=ef, mask_=masks, **cl)
-                for b in range(len(group)):
-                    restored[b, i] = ds.concat(x0s[b].unsqueeze(0), y0s[b], masks[b])[0].cpu().numpy()
-                if not args.quiet:
-                    print(f'{task} | Gibbs x{len(group)} | iter: {i}, acc: {float(acc.float().mean()):.3f}')
-            for b in range(len(group)):
+                masks.append(mask), y0s.append(test_y0), heads.append(head)
+            to_img = lambda b, x0: ds.concat(x0.unsqueeze(0), y0s[b], masks[b])[0].cpu().numpy()
+            keys_of = lambda i: np.stack([job[4][i] for job in group], 0)
+            init = lambda keys_, method: gibbs_init_batched(keys_, y0s, x_shape, ts, sb.fwd_sampler, sde, sb.unpack,
+                                                            nparticles=args.nparticles, method=method, marg_y=args.marg,
+                                                            mask_=masks, **cl)[0]
+            restored = np.zeros((nb, args.nsamples, resolution, resolution, nchannels), np.float32)
+            if is_filter:
+                for i in range(args.nsamples):
+                    x0s = init(keys_of(i), 'filter')
+                    for b in range(nb):
+                        restored[b, i] = to_img(b, x0s[b])
+                    if not args.quiet:
+                        print(f'{task} | filter x{nb} | iter: {i}')
+            elif is_gibbs:
+                if args.batch_init:
+                    x0s = init(np.stack([job[3] for job in group], 0), args.init_method)
+                else:
+                    x0s = torch.stack([gibbs_init(group[b][3], y0s[b], x_shape, ts, sb.fwd_sampler, sde, sb.unpack,   # per image
+                                                  nparticles=args.nparticles, method=args.init_method, marg_y=args.marg,
+                                                  mask_=masks[b], **cl)[0] for b in range(nb)], 0)
+                for b in range(nb):
+                    np.save(heads[b] + '-gibbs-init', to_img(b, x0s[b]))
+                bs_stars = np.zeros((nb, nsteps + 1), np.int32)
+                for i in range(args.nsamples):
+                    x0s, _, bs_stars, acc = gibbs_kernel_batched(keys_of(i), x0s, y0s, None, bs_stars, ts, sb.fwd_sampler, sde,
+                                                                 sb.unpack, args.nparticles, marg_y=args.marg,
+                                                                 explicit_backward=eb, explicit_final=ef, mask_=masks, **cl)
+                    for b in range(nb):
+                        restored[b, i] = to_img(b, x0s[b])
+                    if not args.quiet:
+                        print(f'{task} | Gibbs x{nb} | iter: {i}, acc: {float(acc.float().mean()):.3f}')
+            else:
+                x0s = torch.zeros((nb,) + x_shape, device=dev)
+                log_ells = torch.zeros(nb, device=dev)
+                yss = torch.stack([sb.fwd_ys_sampler(group[b][3], y0s[b]) for b in range(nb)], 0)
+                for i in range(args.nsamples):
+                    x0s, log_ells, yss, st = pmcmc_kernel_batched(keys_of(i), x0s, log_ells, yss, y0s, ts, sb.fwd_ys_sampler,
+                                                                  sde, sb.ref_sampler, sb.transition_sampler,
+                                                                  sb.likelihood_logpdf, stratified, args.nparticles,
+                                                                  delta=delta, mask_=masks)
+                    for b in range(nb):
+                        restored[b, i] = to_img(b, x0s[b])
+                    if not args.quiet:
+                        print(f'{task} | pMCMC {delta} x{nb} | iter: {i}, acc_prob: {float(st.acceptance_prob.mean()):.3f}')
+            for b in range(nb):
                 np.save(heads[b] + suffix, restored[b])
             out = restored[-1]
         return out

@@ -5,6 +5,8 @@
 //   fbsmi_cond_killing_batched  row b = fbsmi_cond_resample(kind 1, keys[b], w[b], i[b], j[b], conditional)
 //   fbsmi_em_concat_batched     ensemble b = fbsmi_em_concat
 //   fbsmi_em_finish_batched     ensemble b = fbsmi_em_finish with n_total = n, row0 = 0, net_A = NULL
+//   fbsmi_resample_batched      row b = fbsmi_resample(kind 0 stratified / 1 systematic, w[b], keys[b])
+//   fbsmi_em_propose_batched    ensemble b = fbsmi_em_finish with A = net_A = A[b], n_total = n, row0 = 0, proposal only
 //
 // each bit for bit.  An ensemble has 1 <= n <= 1024 rows, so everything the single-ensemble entry points spread over
 // several launches and a workspace in memory -- the two-level logsumexp, the canonical-tree CDFs, the searches, the draws --
@@ -168,6 +170,27 @@ __global__ void __launch_bounds__(kMaxRows) k_cond_killing_b(const uint32_t* __r
 }
 
 // ------------------------------------------------------------------------------------------------
+// stratified / systematic resampling (resampling.py:43-58; fbsmi_resample and k_strat_search in fbsmi_prims.hip)
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kMaxRows) k_resample_b(const uint32_t* __restrict__ keys, const float* __restrict__ w,
+                                                         int n, int np, int systematic, int32_t* __restrict__ idx) {
+    __shared__ float tr[kMaxRows], cdf[kMaxRows];
+    const int b = blockIdx.x, e = threadIdx.x;
+    tr[e] = e < n ? w[(int64_t)b * n + e] : 0.0f;
+    lds_upsweep(tr, np, np);
+    cdf[e] = lds_scan_at(tr, np, e);
+    __syncthreads();
+    if (e < n) {
+        const uint32_t k0 = keys[2 * b], k1 = keys[2 * b + 1];
+        const float u = systematic ? uniform_at(k0, k1, 1, 0) : uniform_at(k0, k1, (uint64_t)n, (uint64_t)e);
+        const float q = ((float)e + u) / (float)n;
+        int32_t k = searchsorted_left(cdf, n, bisect_levels(n), q);
+        k = k < 0 ? 0 : (k > n - 1 ? n - 1 : k);
+        idx[(int64_t)b * n + e] = k;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // the image step: one workgroup of kBlock threads per particle row of the flat (B * n) axis
 // ------------------------------------------------------------------------------------------------
 struct BatchArgs {
@@ -187,6 +210,7 @@ struct BatchArgs {
     void* img;
     int32_t du, dv, nmasks, n;
     float cx, cs, dt, sd;
+    int32_t net_by_A;   // the network's output row is the ancestor's (b * n + A[b][r]), not the slot's (b * n + r)
 };
 
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short h) { return fbsmi_u2f((uint32_t)h << 16); }
@@ -241,11 +265,12 @@ __global__ void __launch_bounds__(kBlock) k_em_finish_b(const BatchArgs a) {
     const int b = (int)(row / a.n), r = (int)(row - (int64_t)b * a.n);
     const int du = a.du, dv = a.dv, D = du + dv;
     const int mb = a.nmasks == 1 ? 0 : b;
-    const int64_t net_row = row * D;
+    const int64_t src = (int64_t)b * a.n + source_row(a, b, r);
+    const int64_t net_row = (a.net_by_A ? src : row) * D;
     if (a.us_new) {
         // us_new[r] = (x + drift * dt) + sd * z, z = row r of normal(keys[b], (n, du)); the pinned row takes its value
         const int32_t* __restrict__ u_off = a.u_off + (int64_t)mb * du;
-        const float* __restrict__ x = a.us + ((int64_t)b * a.n + source_row(a, b, r)) * du;
+        const float* __restrict__ x = a.us + src * du;
         float* __restrict__ y = a.us_new + row * du;
         const uint32_t k0 = a.keys[2 * b], k1 = a.keys[2 * b + 1];
         const uint64_t ntot = (uint64_t)a.n * (uint64_t)du;
@@ -399,6 +424,43 @@ int fbsmi_em_finish_batched(const fbsmi_em_mask_batch* mask, const float* us, co
     a.u_off = mask->u_off; a.v_off = mask->v_off;
     a.du = mask->du; a.dv = mask->dv; a.nmasks = mask->nmasks; a.n = (int32_t)n;
     a.cx = cx; a.cs = cs; a.dt = dt; a.sd = sd;
+    const dim3 grid((unsigned)(B * n));
+    hipStream_t st = (hipStream_t)stream;
+    if (net_dtype == 0 && mode == 0) k_em_finish_b<0, 0><<<grid, kBlock, 0, st>>>(a);
+    else if (net_dtype == 0) k_em_finish_b<0, 1><<<grid, kBlock, 0, st>>>(a);
+    else if (mode == 0) k_em_finish_b<1, 0><<<grid, kBlock, 0, st>>>(a);
+    else k_em_finish_b<1, 1><<<grid, kBlock, 0, st>>>(a);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_resample_batched(int kind, const uint32_t* keys, const float* w, int64_t B, int64_t n, int32_t* idx,
+                           void* stream) {
+    FBSMI_NEED(kind >= 0 && kind <= 3, "resample_batched: kind must be 0..3");
+    FBSMI_NEED(keys && w && idx, "resample_batched: null pointer");
+    FBSMI_NEED(B >= 1 && n >= 1 && B <= kMaxGrid, "resample_batched: B and n must be at least 1");
+    if (kind > 1) return fail(FBSMI_ERR_UNSUPPORTED, "resample_batched: stratified (0) and systematic (1) only");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "resample_batched: more than 1024 rows per ensemble");
+    const int np = threads_for(n);
+    k_resample_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(keys, w, (int)n, np, kind == 1, idx);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_em_propose_batched(const fbsmi_em_mask_batch* mask, const float* us, const int32_t* A, const void* net,
+                             int net_dtype, int mode, float cx, float cs, float dt, float sd, const uint32_t* keys,
+                             int64_t B, int64_t n, float* us_new, void* stream) {
+    FBSMI_NEED(us && A && net && keys && us_new, "em_propose_batched: null pointer");
+    const int rc = check_em("em_propose_batched", mask, B, n);
+    if (rc) return rc;
+    FBSMI_NEED((net_dtype == 0 || net_dtype == 1) && (mode == 0 || mode == 1), "em_propose_batched: bad net_dtype or mode");
+    FBSMI_NEED(us_new != us, "em_propose_batched: us_new must not alias us");
+    BatchArgs a = {};
+    a.us = us; a.A = A; a.net = net; a.keys = keys; a.us_new = us_new;
+    a.u_off = mask->u_off; a.v_off = mask->v_off;
+    a.du = mask->du; a.dv = mask->dv; a.nmasks = mask->nmasks; a.n = (int32_t)n;
+    a.cx = cx; a.cs = cs; a.dt = dt; a.sd = sd;
+    a.net_by_A = 1;
     const dim3 grid((unsigned)(B * n));
     hipStream_t st = (hipStream_t)stream;
     if (net_dtype == 0 && mode == 0) k_em_finish_b<0, 0><<<grid, kBlock, 0, st>>>(a);

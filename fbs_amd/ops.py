@@ -256,6 +256,29 @@ def cond_killing_batched(keys, weights: torch.Tensor, i: torch.Tensor, j: torch.
     return idx
 
 
+_RESAMPLE_BATCHED_KINDS = {"stratified": 0, "systematic": 1, "multinomial": 2, "killing": 3}
+
+
+def resample_batched(weights: torch.Tensor, keys, kind: str = "stratified") -> torch.Tensor:
+    """Stratified or systematic resampling (resampling.py:43-58) of B ensembles in one launch: row b of the result (B, n)
+    int32 has the bits of ``stratified(weights[b], keys[b])`` / ``systematic(weights[b], keys[b])``.  keys (B, 2) uint32
+    on the host or their bits as an int32 device tensor; n <= 1024.  'multinomial' and 'killing' have no batched kernel
+    (the library refuses them)."""
+    if kind not in _RESAMPLE_BATCHED_KINDS:
+        raise ValueError(f"resample_batched: unknown kind {kind!r}")
+    w = _f32c(weights, "weights")
+    if w.dim() != 2:
+        raise ValueError("resample_batched wants weights of shape (B, n)")
+    B, n = w.shape
+    kd = keys_to_device(keys, w.device)
+    if kd.numel() != 2 * B:
+        raise ValueError("resample_batched: keys (B, 2) must match weights (B, n)")
+    idx = torch.empty((B, n), dtype=torch.int32, device=w.device)
+    _lib.call("fbsmi_resample_batched", _RESAMPLE_BATCHED_KINDS[kind], kd.data_ptr(), w.data_ptr(), B, n, idx.data_ptr(),
+              _stream())
+    return idx
+
+
 def searchsorted(a: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     a = _f32c(a, "a").reshape(-1)
     qq = _f32c(q, "q")

@@ -1,0 +1,302 @@
+"""Bootstrap filters and particle-marginal MH steps of B independent ensembles in lockstep: the test images of one run,
+the samples of one image, or both.
+
+The ensembles share the time grid, the SDE and the network, so every SMC step of all of them is one network call on
+B * nparticles rows between single launches of the batched sampler kernels (fbs_amd/csrc/fbsmi_batch.hip), instead of B
+calls on `nparticles` rows each among a dozen launches per ensemble.  Every function here is the loop of its
+single-ensemble namesake in ``smc.py`` / ``gibbs.py`` over the ensembles, with the same keys, run that way, and falls back
+to that loop when the lockstep conditions do not hold.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from .. import ops
+from ..score import bridge_of
+from . import resampling as _resampling
+from .common import MCMCState
+from .gibbs import bridge_sampler, gibbs_init
+from .gibbs_batched import MAX_LOCKSTEP_ROWS, _is_mask
+from .smc import (bootstrap_backward_smoother, bootstrap_filter, pcn_proposal, pmcmc_filter_step, pmcmc_kernel)
+
+
+def _host_keys(keys) -> np.ndarray:
+    return np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys, np.uint32).reshape(-1, 2)
+
+
+def _step_keys(keys, nsteps: int):
+    """split(key, T), then split(., 2) per step, for B keys -> two (T, B, 2) uint32 arrays (first, second)."""
+    B, T = keys.shape[0], int(nsteps)
+    first, second = np.zeros((T, B, 2), np.uint32), np.zeros((T, B, 2), np.uint32)
+    for b in range(B):
+        step_keys = ops.split(keys[b], T)
+        for k in range(T):
+            first[k, b], second[k, b] = ops.split(step_keys[k], 2)
+    return first, second
+
+
+def filter_key_schedule(keys, nsteps: int) -> dict:
+    """Every key ``bootstrap_filter`` derives from its own, for B filters, on the host: smc.py:45 (init, steps), :47 (one
+    per step) and :56 (proposal, resampling).  -> (B, 2) array 'init' and (nsteps, B, 2) arrays 'proposal', 'resampling',
+    all uint32."""
+    keys = _host_keys(keys)
+    init, steps = np.zeros_like(keys), np.zeros_like(keys)
+    for b in range(keys.shape[0]):
+        init[b], steps[b] = ops.split(keys[b], 2)
+    proposal, resampling = _step_keys(steps, nsteps)
+    return {"init": init, "proposal": proposal, "resampling": resampling}
+
+
+def pmcmc_key_schedule(keys, nsteps: int) -> dict:
+    """Every key ``pmcmc_kernel`` derives from its own, for B kernels, on the host: smc.py:296 (prop, u0, filter, mh) and,
+    inside ``pmcmc_filter_step``, :255 (one per step) and :261 (proposal, resampling).  -> (B, 2) arrays 'prop', 'u0',
+    'filter', 'mh' and (nsteps, B, 2) arrays 'proposal', 'resampling', all uint32."""
+    keys = _host_keys(keys)
+    out = {name: np.zeros_like(keys) for name in ("prop", "u0", "filter", "mh")}
+    for b in range(keys.shape[0]):
+        out["prop"][b], out["u0"][b], out["filter"][b], out["mh"][b] = ops.split(keys[b], 4)
+    out["proposal"], out["resampling"] = _step_keys(out["filter"], nsteps)
+    return out
+
+
+def _masks_of(kwargs, B: int):
+    """(masks, per_mask, kw) of the ``mask_`` keyword: one mask, or a list of B."""
+    masks = kwargs.get("mask_")
+    per_mask = masks is not None and not _is_mask(masks)
+    if per_mask and len(masks) != B:
+        raise ValueError(f"{len(masks)} masks for {B} ensembles")
+    kw = lambda b: {**kwargs, "mask_": masks[b]} if per_mask else kwargs
+    return masks, per_mask, kw
+
+
+def _lockstep(transition_sampler, weight_closure, resampling, nparticles, kwargs, B: int, log: bool = True):
+    """(bridge, resampler name, mask batch) when B ensembles can advance in lockstep, else None: the closures are one
+    ScoreBridge's own, ``mask_`` is the only keyword, log weights, the package's stratified or systematic resampler,
+    masks of one shape, at most 1024 particles.  Draws nothing."""
+    if not log or set(kwargs) != {"mask_"} or int(nparticles) > MAX_LOCKSTEP_ROWS:
+        return None
+    sb = bridge_of(transition_sampler, weight_closure)
+    rname = "stratified" if resampling is _resampling.stratified else (
+        "systematic" if resampling is _resampling.systematic else None)
+    if sb is None or rname is None:
+        return None
+    masks, per_mask, kw = _masks_of(kwargs, B)
+    ems = [sb._em_mask(kw(b)["mask_"]) for b in range(B)]
+    if any((e.du, e.dv) != (ems[0].du, ems[0].dv) for e in ems):
+        return None
+    return sb, rname, sb.em_mask_batch(masks if per_mask else [masks], B)
+
+
+def _host_ts(ts):
+    """The grid as host floats, read once: the time loop then never waits for the device."""
+    return [float(t) for t in (ts.detach().cpu().numpy() if isinstance(ts, torch.Tensor) else np.asarray(ts)).reshape(-1)]
+
+
+def _take(us, inds):
+    """us[b][inds[b]] for every ensemble."""
+    return us[torch.arange(us.shape[0], device=us.device)[:, None], inds.long()]
+
+
+def _filter_lockstep(sb, rname, mb, us, vss, ts, key_proposal, key_resampling, nparticles, return_last):
+    """The time loop of ``bootstrap_filter`` (smc.py:55-71) for all ensembles.  us (B, n, p, c) the initial particles."""
+    dev = us.device
+    nsteps = vss.shape[1] - 1
+    vs = vss.transpose(0, 1).contiguous()                                          # (T + 1, B, q, c)
+    ts_h = _host_ts(ts)
+    k_prop = ops.keys_to_device(key_proposal, dev)                                  # the whole run's keys, uploaded once
+    k_res = ops.keys_to_device(key_resampling, dev)
+    nell = torch.zeros(us.shape[0], dtype=torch.float32, device=dev)
+    logn = np.float32(math.log(nparticles))
+    filtering = [us]
+    pending = None                                                                  # ancestors not gathered yet
+    for k in range(nsteps):
+        us_new, lw = sb.fused_step_batched(us, pending, vs[k + 1], vs[k], ts_h[k], k_prop[k], mb)
+        w, c = ops.normalise_batched(lw, return_lse=True)
+        nell = nell - (c - logn)
+        inds = ops.resample_batched(w, k_res[k], rname)
+        if return_last and k < nsteps - 1:
+            us, pending = us_new, inds
+            continue
+        us, pending = _take(us_new, inds), None
+        if not return_last:
+            filtering.append(us)
+    return (us if return_last else torch.stack(filtering, 1)), nell
+
+
+def bootstrap_filter_batched(transition_sampler, measurement_cond_pdf, vss, ts, init_sampler, keys, nparticles, resampling,
+                             log: bool = True, return_last: bool = True, **kwargs):
+    """``bootstrap_filter`` for B ensembles: vss (B, T + 1, q, c), keys (B, 2), ``mask_`` one mask or a list of B masks.
+    Returns (samples (B, n, p, c) [return_last] or (B, T + 1, n, p, c), nell (B,)), equal to the stacked results of
+
+        [bootstrap_filter(..., vss[b], ts, init_sampler, keys[b], ..., mask_=masks[b]) for b in range(B)]
+
+    bit for bit whenever the score function's output row does not depend on which other rows share its call.  That is
+    not promised for a real UNet: library convolution and matrix kernels may be chosen by batch size and differ in the
+    last bits, after which a resampling decision can flip and the two runs part ways as two valid draws.
+
+    The ensembles advance in lockstep -- one network call per step, one launch per sampler operation, no host
+    synchronisation inside the time loop -- when the closures are one ScoreBridge's own, ``mask_`` is the only keyword,
+    log is set, resampling is this package's stratified or systematic, the masks have one shape and nparticles <= 1024.
+    Anything else runs the loop above: the same result without the speed-up."""
+    keys = _host_keys(keys)
+    B = keys.shape[0]
+    lock = _lockstep(transition_sampler, measurement_cond_pdf, resampling, nparticles, kwargs, B, log)
+    if lock is None:
+        _, _, kw = _masks_of(kwargs, B)
+        outs = [bootstrap_filter(transition_sampler, measurement_cond_pdf, vss[b], ts, init_sampler, keys[b], nparticles,
+                                 resampling, log=log, return_last=return_last, **kw(b)) for b in range(B)]
+        return torch.stack([o[0] for o in outs], 0), torch.stack([o[1].reshape(()) for o in outs], 0)
+    sb, rname, mb = lock
+    sk = filter_key_schedule(keys, vss.shape[1] - 1)
+    us = torch.stack([init_sampler(sk["init"][b], vss[b, 0], nparticles) for b in range(B)], 0)
+    return _filter_lockstep(sb, rname, mb, us, vss, ts, sk["proposal"], sk["resampling"], nparticles, return_last)
+
+
+def pmcmc_filter_step_batched(keys, vss, u0s, ts, transition_sampler, likelihood_logpdf, resampling, nparticles, **kwargs):
+    """``pmcmc_filter_step`` for B ensembles: keys (B, 2), vss (B, T + 1, q, c), u0s (B, n, p, c) -> (us (B, n, p, c),
+    log_ell (B,)), the stacked results of the loop over the ensembles under the contract and the lockstep conditions of
+    ``bootstrap_filter_batched``."""
+    keys = _host_keys(keys)
+    B = keys.shape[0]
+    lock = _lockstep(transition_sampler, likelihood_logpdf, resampling, nparticles, kwargs, B)
+    if lock is None:
+        _, _, kw = _masks_of(kwargs, B)
+        outs = [pmcmc_filter_step(keys[b], vss[b], u0s[b], ts, transition_sampler, likelihood_logpdf, resampling,
+                                  nparticles, **kw(b)) for b in range(B)]
+        return torch.stack([o[0] for o in outs], 0), torch.stack([o[1].reshape(()) for o in outs], 0)
+    sb, rname, mb = lock
+    nsteps = (ts.shape[0] if hasattr(ts, "shape") else len(ts)) - 1
+    key_proposal, key_resampling = _step_keys(keys, nsteps)
+    return _pmcmc_lockstep(sb, rname, mb, u0s, vss, ts, key_proposal, key_resampling, nparticles)
+
+
+def _pmcmc_lockstep(sb, rname, mb, us, vss, ts, key_proposal, key_resampling, nparticles):
+    """The time loop of ``pmcmc_filter_step`` (smc.py:260-272) for all ensembles."""
+    dev = us.device
+    nsteps = len(key_proposal)
+    vs = vss.transpose(0, 1).contiguous()
+    ts_h = _host_ts(ts)
+    k_prop = ops.keys_to_device(key_proposal, dev)
+    k_res = ops.keys_to_device(key_resampling, dev)
+    log_ell = torch.zeros(us.shape[0], dtype=torch.float32, device=dev)
+    logn = np.float32(math.log(nparticles))
+    for k in range(nsteps):
+        cell = {}
+
+        def resample(lw):
+            w, cell["c"] = ops.normalise_batched(lw, return_lse=True)
+            return ops.resample_batched(w, k_res[k], rname)
+
+        us, _, _ = sb.fused_weight_then_propose_batched(us, vs[k + 1], vs[k], ts_h[k], k_prop[k], mb, resample)
+        log_ell = (log_ell - logn) + cell["c"]
+    return us, log_ell
+
+
+def _per_ensemble(x, B: int, inner_dim: int):
+    """b -> x[b] when x is a list of B or a tensor with a leading axis B over `inner_dim`-dimensional items, else b -> x."""
+    batched = isinstance(x, (list, tuple)) or (isinstance(x, torch.Tensor) and x.dim() == inner_dim + 1)
+    if batched and len(x) != B:
+        raise ValueError(f"{len(x)} observations for {B} ensembles")
+    return (lambda b: x[b]) if batched else (lambda b: x)
+
+
+def pmcmc_kernel_batched(keys, uTs, log_ells, yss, y0s, ts, fwd_ys_sampler, sde, ref_sampler, transition_sampler,
+                         likelihood_logpdf, resampling, nparticles, delta: float = None, which_u: int = 0, **kwargs):
+    """``pmcmc_kernel`` for B ensembles: keys (B, 2), uTs (B, p, c), log_ells (B,), yss (B, T + 1, q, c), y0s one
+    observation (q, c) or B of them.  Returns (uTs, log_ells, yss, MCMCState of (B,) tensors), the stacked results of the
+    loop over the ensembles under the contract and the lockstep conditions of ``bootstrap_filter_batched``.  The
+    proposal and ``ref_sampler`` run per ensemble; the filter advances in lockstep and the accept step is taken on the
+    device for all ensembles at once, without reading anything back."""
+    keys = _host_keys(keys)
+    B = keys.shape[0]
+    y0 = _per_ensemble(y0s, B, yss.dim() - 2)
+    lock = _lockstep(transition_sampler, likelihood_logpdf, resampling, nparticles, kwargs, B)
+    if lock is None:
+        _, _, kw = _masks_of(kwargs, B)
+        outs = [pmcmc_kernel(keys[b], uTs[b], log_ells[b], yss[b], y0(b), ts, fwd_ys_sampler, sde, ref_sampler,
+                             transition_sampler, likelihood_logpdf, resampling, nparticles, delta=delta, which_u=which_u,
+                             **kw(b)) for b in range(B)]
+        state = MCMCState(*(torch.stack([o[3][i].reshape(()) for o in outs], 0) for i in range(len(MCMCState._fields))))
+        return (torch.stack([o[0] for o in outs], 0), torch.stack([o[1].reshape(()) for o in outs], 0),
+                torch.stack([o[2] for o in outs], 0), state)
+    sb, rname, mb = lock
+    dev = yss.device
+    nsteps = yss.shape[1] - 1
+    sk = pmcmc_key_schedule(keys, nsteps)
+    if delta is not None:                                                           # smc.py:300-304
+        ts_np = np.asarray(ts.detach().cpu() if isinstance(ts, torch.Tensor) else ts, np.float64).reshape(-1)
+        coef = torch.as_tensor(np.asarray(sde.mean(ts_np, ts_np[0], 1.0), np.float32), device=dev)
+    props, u0s, zs = [], [], []
+    for b in range(B):                                                              # preamble, per ensemble (:297-307, :314)
+        y0_b = y0(b)
+        if delta is None:
+            prop_ys = fwd_ys_sampler(sk["prop"][b], y0_b)
+        else:
+            y0_t = y0_b if isinstance(y0_b, torch.Tensor) else torch.as_tensor(np.asarray(y0_b, np.float32), device=dev)
+            mean = (coef.reshape((-1,) + (1,) * y0_t.dim()) * y0_t).reshape(yss[b].shape)
+            prop_ys = pcn_proposal(sk["prop"][b], delta, yss[b], mean, lambda key_: fwd_ys_sampler(key_, y0_b))
+        props.append(prop_ys)
+        u0s.append(ref_sampler(sk["u0"][b], torch.flip(prop_ys, [0])[0], nparticles))
+        zs.append(ops.uniform(sk["mh"][b], (), device=dev))
+    prop_yss = torch.stack(props, 0)
+    prop_uTs, prop_log_ell = _pmcmc_lockstep(sb, rname, mb, torch.stack(u0s, 0), torch.flip(prop_yss, [1]), ts,
+                                             sk["proposal"], sk["resampling"], nparticles)
+    prop_uT = prop_uTs[:, which_u]
+    log_ell_t = (log_ells if isinstance(log_ells, torch.Tensor) else
+                 torch.as_tensor(np.asarray(log_ells, np.float32), device=dev)).to(torch.float32).reshape(B)
+    log_acc_prob = torch.minimum(torch.zeros_like(prop_log_ell), prop_log_ell - log_ell_t)       # :313
+    acc = ops.math_map("log", torch.stack(zs, 0)) < log_acc_prob                    # :315
+    state = MCMCState(acceptance_prob=torch.exp(log_acc_prob), is_accepted=acc, prop_log_ell=prop_log_ell,
+                      log_ell=log_ell_t)
+    pick = lambda new, old: torch.where(acc.reshape((B,) + (1,) * (new.dim() - 1)), new, old)
+    return pick(prop_uT, uTs), pick(prop_log_ell, log_ell_t), pick(prop_yss, yss), state
+
+
+def gibbs_init_batched(keys, y0s, x0_shape, ts, fwd_sampler, sde, unpack, transition_sampler, transition_logpdf,
+                       likelihood_logpdf, nparticles, method: str = 'smoother', marg_y: bool = True, x0s=None, **kwargs):
+    """``gibbs_init`` for B ensembles: keys (B, 2), y0s one observation or B of them, x0s None or (B, p, c), ``mask_`` one
+    mask or a list of B.  Returns (approx_x0 (B, ...), approx_us_star (B, T + 1, p, c) or None for 'debug'), the stacked
+    results of the loop over the ensembles under the contract and the lockstep conditions of
+    ``bootstrap_filter_batched``.  With 'filter' and 'smoother' the bootstrap filters advance in lockstep; the forward
+    paths, and the backward smoother, run per ensemble.  'debug' and 'kalman' run the loop."""
+    keys = _host_keys(keys)
+    B = keys.shape[0]
+    y0 = _per_ensemble(y0s, B, len(tuple(x0_shape)))
+    _, _, kw = _masks_of(kwargs, B)
+    lock = _lockstep(transition_sampler, likelihood_logpdf, _resampling.stratified, nparticles, kwargs, B) \
+        if method in ("filter", "smoother") else None
+    if lock is None:
+        outs = [gibbs_init(keys[b], y0(b), x0_shape, ts, fwd_sampler, sde, unpack, transition_sampler, transition_logpdf,
+                           likelihood_logpdf, nparticles, method=method, marg_y=marg_y,
+                           x0=None if x0s is None else x0s[b], **kw(b)) for b in range(B)]
+        return (torch.stack([o[0] for o in outs], 0),
+                None if outs[0][1] is None else torch.stack([o[1] for o in outs], 0))
+    sb, rname, mb = lock
+    y00 = y0(0)
+    dev = y00.device if isinstance(y00, torch.Tensor) else ops._default_device()
+    ks = [ops.split(keys[b], 6) for b in range(B)]                                  # gibbs.py:40: fwd, bridge, u0, bf, fwd2, bwd
+    vss, u0s = [], []
+    for b in range(B):                                                              # preamble, per ensemble (gibbs.py:38-47)
+        x0 = torch.zeros(tuple(x0_shape), dtype=torch.float32, device=dev) if x0s is None else x0s[b]
+        _, path_y = unpack(fwd_sampler(ks[b][0], x0, y0(b), **kw(b)), **kw(b))
+        vss.append(torch.flip(bridge_sampler(ks[b][1], path_y[0], path_y[-1], ts, sde), [0]) if marg_y
+                   else torch.flip(path_y, [0]))
+        u0s.append(ops.normal(ks[b][2], (nparticles,) + tuple(x0_shape), device=dev))
+    vss = torch.stack(vss, 0)
+    sk = filter_key_schedule(np.stack([ks[b][3] for b in range(B)], 0), vss.shape[1] - 1)
+    uss, _ = _filter_lockstep(sb, rname, mb, torch.stack(u0s, 0), vss, ts, sk["proposal"], sk["resampling"], nparticles,
+                              method == "filter")
+    x0n, usn = [], []
+    for b in range(B):                                                              # postamble, per ensemble (gibbs.py:49-57)
+        if method == "filter":
+            approx_x0 = uss[b, 0]
+            us_star = torch.flip(unpack(fwd_sampler(ks[b][4], approx_x0, y0(b), **kw(b)), **kw(b))[0], [0])
+        else:
+            approx_x0 = uss[b, -1, 0]
+            us_star = bootstrap_backward_smoother(ks[b][5], uss[b], vss[b], ts, transition_logpdf, **kw(b))
+        x0n.append(approx_x0)
+        usn.append(us_star)
+    return torch.stack(x0n, 0), torch.stack(usn, 0)

@@ -283,6 +283,28 @@ class ScoreBridge:
         us_new, _ = self._finish(em, us2, inds, net, t_prev, None, None, key_, None, None, True, False, net_A=inds)
         return us_new.reshape((us_new.shape[0],) + tuple(self.dataset.unobs_shape)), lw, inds
 
+    @torch.no_grad()
+    def fused_weight_then_propose_batched(self, us, v, v_prev, t_prev, keys, masks, resample):
+        """``fused_weight_then_propose`` for B ensembles at the same time step: one weights-only ``fused_step_batched``
+        (the step's only network evaluation), ``resample(lw (B, n)) -> inds (B, n)`` local to each ensemble, then one
+        fbsmi_em_propose_batched launch that reads the same network buffer through ``inds``.  us (B, n, p, c);
+        v, v_prev (B, q, c); keys (B, 2) as in ``fused_step_batched``.  -> (us_new (B, n, p, c), lw (B, n), inds)."""
+        us3 = ops._f32c(us, "us")
+        B, n = int(us3.shape[0]), int(us3.shape[1])
+        us3 = us3.reshape(B, n, -1)
+        mb = self.em_mask_batch(masks, B)
+        _, lw = self.fused_step_batched(us3, None, v, v_prev, t_prev, None, mb, want_us=False)
+        net = self._buf["net"]                               # (B * n, D), written by the call above
+        inds = resample(lw).to(torch.int32).contiguous()
+        kd = ops.keys_to_device(keys, us3.device)
+        if tuple(inds.shape) != (B, n) or kd.numel() != 2 * B:
+            raise ValueError("resample must return (B, n) ancestors and keys must be (B, 2)")
+        mode, cx, cs, sd = self._coef(t_prev)
+        us_new = torch.empty((B, n, mb.du), dtype=torch.float32, device=us3.device)
+        _lib.call("fbsmi_em_propose_batched", mb.ref, us3.data_ptr(), inds.data_ptr(), net.data_ptr(), _NET_DT[net.dtype],
+                  mode, cx, cs, self.dt, sd, kd.data_ptr(), B, n, us_new.data_ptr(), ops._stream())
+        return us_new.reshape((B, n) + tuple(self.dataset.unobs_shape)), lw, inds
+
     # -- network output shared by the closures of one step --------------------------------------------
     def _net_of(self, us_prev, v_prev, t_prev, mask_):
         c = self._cache

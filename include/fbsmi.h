@@ -776,6 +776,21 @@ int fbsmi_em_finish_batched(const fbsmi_em_mask_batch* mask, const float* us, co
                             const float* v_prev, const uint32_t* keys, int64_t B, int64_t n, const int32_t* pin_row,
                             const float* pin_value, float* us_new, float* lw, void* stream);
 
+/* Row b of idx (B, n) = fbsmi_resample(kind, w[b], keys[b], n), bit for bit, for kind 0 (stratified) and 1 (systematic);
+ * the indices are local to the ensemble.  keys (B, 2), w (B, n): device arrays.  One workgroup per ensemble, no
+ * workspace.  kind 2 (multinomial) and 3 (killing) are FBSMI_ERR_UNSUPPORTED, any other kind FBSMI_ERR_ARG; otherwise the
+ * refusals of fbsmi_normalise_batched. */
+int fbsmi_resample_batched(int kind, const uint32_t* keys, const float* w, int64_t B, int64_t n, int32_t* idx,
+                           void* stream);
+/* The proposal half of a weight -> resample -> propose step (fbs/samplers/smc.py:144-150) on the network output the
+ * weights were computed from: ensemble b = fbsmi_em_finish with A = net_A = A[b], n_total = n, row0 = 0, no pin, lw = NULL,
+ * bit for bit.  Row r proposes from us[b][A[b][r]] with the network's output row b * n + A[b][r]; its noise is row r of
+ * normal(keys[b], (n, du)).  A (B, n) is required and its entries are clamped into [0, n - 1]; us_new (B, n, du) must
+ * not alias us.  Refusals as fbsmi_em_finish_batched. */
+int fbsmi_em_propose_batched(const fbsmi_em_mask_batch* mask, const float* us, const int32_t* A, const void* net,
+                             int net_dtype, int mode, float cx, float cs, float dt, float sd, const uint32_t* keys,
+                             int64_t B, int64_t n, float* us_new, void* stream);
+
 /* HIP-event timing hooks: average duration in microseconds of the propagate ("Euler") kernel
  * over the launches since the last reset; 0 launches -> returns 0. Only measured when
  * fbsmi_lg_sweep_profile(s, 1) was set (events force non-graph launches). */
