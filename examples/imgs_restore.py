@@ -9,7 +9,9 @@ baseline: whole-image particles, the twisting function's gradient through the sc
 reverse-SDE trajectory with the observed pixels re-noised every step; `*-csgm.npy`).  The closures are the bound methods of one fbs_amd.score.ScoreBridge, so
 every SMC step is two HIP kernels around one network evaluation (PyTorch-ROCm).  With `--batch B` the test images of the
 gibbs*, filter and pmcmc* methods advance in groups of B, one network evaluation per step for the group (fbs_amd.samplers
-gibbs_kernel_batched, gibbs_init_batched, pmcmc_kernel_batched); every image keeps the keys of the sequential run.
+gibbs_kernel_batched, gibbs_init_batched, pmcmc_kernel_batched); every image keeps the keys of the sequential run.  With
+`--method csgm --batch B` the (image, sample) trajectories of the run advance in groups of B (fbs_amd.csgm
+make_image_csgm_batched), each with the key of the sequential run.
 
 The reference loads a trained checkpoint (`./checkpoints/<dataset>_<sde>_<epoch>.npz`, a flat `param` / `ema_param`
 vector in ravel_pytree order) and a dataset (`../datasets/mnist.npz`, `datasets/celeba_hq<res>.npy`); neither exists in
@@ -57,7 +59,7 @@ def main(argv=None):
     p.add_argument('--dim', type=int, default=64, help='UNet width (64 in the reference).')
     p.add_argument('--fp32', action='store_true', help='float32 network instead of bf16 autocast.')
     p.add_argument('--chunk', type=int, default=4096, help='Particles per network call (a power of two: MIOpen ships kernels for those batch sizes; bigger calls are faster per particle).')
-    p.add_argument('--batch', type=int, default=1, help="'filter', 'gibbs*' and 'pmcmc*' methods: test images that advance together, one network call per step for all of them (1: one image at a time).")
+    p.add_argument('--batch', type=int, default=1, help="'filter', 'gibbs*' and 'pmcmc*' methods: test images that advance together, one network call per step for all of them; 'csgm': (image, sample) trajectories that advance together, one launch and one network call per step (1: one at a time).")
     p.add_argument('--batch_init', action='store_true', help="With --batch and a gibbs* method: the images' gibbs_init filters advance together too (gibbs_init_batched); by default gibbs_init runs per image.")
     p.add_argument('--outdir', type=str, default='./imgs/results')
     p.add_argument('--quiet', action='store_true')
@@ -194,6 +196,41 @@ def main(argv=None):
             for b in range(nb):
                 np.save(heads[b] + suffix, restored[b])
             out = restored[-1]
+        return out
+    if args.batch > 1 and args.method == 'csgm':
+        # The (image, sample) pairs of the run are one flat list of independent trajectories, taken --batch at a time
+        # (make_image_csgm_batched): one launch and one network call per step for the group.  A sequential image consumes
+        # nsamples splits of the `key` chain, so every trajectory's key follows from its position alone.
+        from fbs_amd.csgm import make_image_csgm_batched
+        sampler = make_image_csgm_batched(lambda x, t: run(net, x, t), ds, sde, ts, chunk=args.chunk,
+                                          net_input_dtype=torch.float32 if args.fp32 else torch.bfloat16)
+        images, jobs = [], []
+        for k in range(args.ny0s):
+            data_key, subkey = ops.split(data_key)
+            if k < args.start_from:
+                continue
+            k_img, k_mask = ops.split(subkey)
+            test_img = ops.uniform(k_img, (resolution, resolution, nchannels), device=dev)
+            mask = ds.gen_mask(k_mask)
+            _, test_y0 = ds.unpack(test_img, mask)
+            head = os.path.join(args.outdir, f'{args.dataset}-{task}-{args.sde}-{args.nparticles}-{k}')
+            np.savez(head + '-true', test_img=test_img.cpu().numpy())
+            images.append((head, mask, test_y0, np.zeros((args.nsamples, resolution, resolution, nchannels), np.float32)))
+            for i in range(args.nsamples):
+                key, subkey = ops.split(key)
+                jobs.append((len(images) - 1, i, subkey))
+        for g0 in range(0, len(jobs), args.batch):
+            group = jobs[g0:g0 + args.batch]                                       # the last group may be smaller
+            x0s = sampler(np.stack([j[2] for j in group], 0), [images[j[0]][2] for j in group],
+                          [images[j[0]][1] for j in group])
+            for b, (m, i, _) in enumerate(group):
+                _, mask, test_y0, restored = images[m]
+                restored[i] = ds.concat(x0s[b].unsqueeze(0), test_y0, mask)[0].cpu().numpy()
+            if not args.quiet:
+                print(f'{task} | cSGM x{len(group)} | trajectories: {g0 + len(group)} / {len(jobs)}')
+        for head, _, _, restored in images:
+            np.save(head + '-csgm', restored)
+            out = restored
         return out
     for k in range(args.ny0s):
         data_key, subkey = ops.split(data_key)

@@ -7,6 +7,8 @@
 //   fbsmi_em_finish_batched     ensemble b = fbsmi_em_finish with n_total = n, row0 = 0, net_A = NULL
 //   fbsmi_resample_batched      row b = fbsmi_resample(kind 0 stratified / 1 systematic, w[b], keys[b])
 //   fbsmi_em_propose_batched    ensemble b = fbsmi_em_finish with A = net_A = A[b], n_total = n, row0 = 0, proposal only
+//   fbsmi_em_csgm_step_batched  trajectory b = one step of fbs_amd/csgm.py: fbsmi_em_update, then the next network input
+//   fbsmi_normal_batched        row b = fbsmi_normal(keys[b], n)
 //
 // each bit for bit.  An ensemble has 1 <= n <= 1024 rows, so everything the single-ensemble entry points spread over
 // several launches and a workspace in memory -- the two-level logsumexp, the canonical-tree CDFs, the searches, the draws --
@@ -331,6 +333,79 @@ __global__ void __launch_bounds__(kBlock) k_em_finish_b(const BatchArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// the image CSGM step (fbs_amd/csgm.py): one workgroup per trajectory, threads stride over the image positions.  `role`
+// is a bijection between positions and (u, v) elements, so ONE pass does the Euler-Maruyama update of step k (unobserved
+// positions: us -> us_new, noise = element noff + o of normal(keys[b], (ntot,))) and writes the network input of step
+// k + 1 (the updated value there, F * y0 + sq * normal(est_keys[b], (dv,)) at the observed positions).  A thread touches
+// only its own element: no barrier, no LDS, and us_new may be us.  The network read net[b * D + e] is coalesced
+// (u_off[role[e]] == e).  BatchArgs: v_prev = y0, keys = the scan keys, sd = c; n is unused (a trajectory is one row).
+// ------------------------------------------------------------------------------------------------
+template <int NETDT, int OUTDT>
+__global__ void __launch_bounds__(kBlock) k_em_csgm_step_b(const BatchArgs a, const uint32_t* __restrict__ est_keys, float F,
+                                                           float sq, uint64_t ntot, uint64_t noff) {
+    const int b = blockIdx.x;
+    const int du = a.du, dv = a.dv, D = du + dv;
+    const int32_t* __restrict__ role = a.role + (a.nmasks == 1 ? 0 : (int64_t)b * D);
+    const float* x = a.us + (int64_t)b * du;
+    float* y = a.us_new ? a.us_new + (int64_t)b * du : nullptr;
+    const bool update = a.net != nullptr, image = a.img != nullptr;
+    const uint32_t s0 = a.keys[2 * b], s1 = a.keys[2 * b + 1], e0 = est_keys[2 * b], e1 = est_keys[2 * b + 1];
+    for (int e = threadIdx.x; e < D; e += kBlock) {
+        const int r = role[e];
+        const bool unobs = r >= 0;
+        // the element inside its part whatever the table holds
+        int o = unobs ? r : ~r;
+        const int last = (unobs ? du : dv) - 1;
+        o = o > last ? last : o;
+        if (o < 0 || !(unobs ? (update || image) : image)) continue;   // dv == 0, or nothing to do at this position
+        // one draw per position, from the trajectory's scan key or the step's re-noising key: both kinds of position go
+        // through the same instructions, so a wave that holds both does not run the generator twice
+        float z = 0.0f;
+        if (unobs ? update : true)
+            z = normal_from_bits(random_bits_at(unobs ? s0 : e0, unobs ? s1 : e1, unobs ? ntot : (uint64_t)dv,
+                                                unobs ? noff + (uint64_t)o : (uint64_t)o));
+        float out;
+        if (unobs) {
+            out = x[o];
+            if (update) {
+                const float s = net_value<NETDT>(a.net, (int64_t)b * D + e);
+                const float d = reverse_drift<0>(a.cx, a.cs, out, s);
+                const float m = out + d * a.dt;
+                const float nz = a.sd * z;
+                out = m + nz;
+                y[o] = out;
+            }
+        } else {
+            const float t1 = F * a.v_prev[(int64_t)b * dv + o], t2 = sq * z;
+            out = t1 + t2;
+        }
+        if (image) {
+            if (OUTDT == 0) ((float*)a.img)[(int64_t)b * D + e] = out;
+            else ((unsigned short*)a.img)[(int64_t)b * D + e] = f32_to_bf16_bits(out);
+        }
+    }
+}
+
+// row b of out (B, n) = normal(keys[b], (n,)): k_random<2> of fbsmi_prims.hip (one Threefry call per pair of elements
+// (n + 1) / 2 apart) with the key read per row -- that kernel takes ONE key by value, so it cannot serve B of them.
+// `bpr` workgroups per row.
+__global__ void __launch_bounds__(kBlock) k_normal_b(const uint32_t* __restrict__ keys, uint64_t n, int bpr,
+                                                     float* __restrict__ out) {
+    const int64_t b = blockIdx.x / bpr;
+    const int q = (int)(blockIdx.x - b * bpr);
+    const uint32_t k0 = keys[2 * b], k1 = keys[2 * b + 1];
+    float* __restrict__ o = out + b * (int64_t)n;
+    const uint64_t half = (n + 1) >> 1;
+    for (uint64_t i = (uint64_t)q * kBlock + threadIdx.x; i < half; i += (uint64_t)bpr * kBlock) {
+        const uint64_t j = i + half;
+        uint32_t lo, hi;
+        random_bits_pair_padded(k0, k1, n, i, lo, hi);
+        o[i] = normal_from_bits(lo);
+        if (j < n) o[j] = normal_from_bits(hi);
+    }
+}
+
 #define FBSMI_NEED(cond, msg) \
     if (!(cond)) return fail(FBSMI_ERR_ARG, msg)
 #define FBSMI_LAUNCH_CHECK()                                                     \
@@ -467,6 +542,52 @@ int fbsmi_em_propose_batched(const fbsmi_em_mask_batch* mask, const float* us, c
     else if (net_dtype == 0) k_em_finish_b<0, 1><<<grid, kBlock, 0, st>>>(a);
     else if (mode == 0) k_em_finish_b<1, 0><<<grid, kBlock, 0, st>>>(a);
     else k_em_finish_b<1, 1><<<grid, kBlock, 0, st>>>(a);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_em_csgm_step_batched(const fbsmi_em_mask_batch* mask, const float* u, const void* net, int net_dtype, float cx,
+                               float cs, float dt, float c, const uint32_t* scan_keys, int64_t noise_total,
+                               int64_t noise_offset, const float* y0, float F, float sq, const uint32_t* est_keys,
+                               int out_dtype, void* img, int64_t B, float* u_new, void* stream) {
+    FBSMI_NEED(mask && mask->u_off && mask->role && (mask->dv == 0 || mask->v_off), "em_csgm_step_batched: null mask");
+    FBSMI_NEED(mask->du >= 1 && mask->dv >= 0 && (int64_t)mask->du + mask->dv <= kMaxGrid,
+               "em_csgm_step_batched: du must be at least 1, dv at least 0 and du + dv below 2^31");
+    FBSMI_NEED(u && (mask->dv == 0 || y0) && scan_keys && est_keys, "em_csgm_step_batched: null u, y0 or keys");
+    FBSMI_NEED(net || img, "em_csgm_step_batched: neither the update (net) nor the network input (img) asked for");
+    FBSMI_NEED(!net || u_new, "em_csgm_step_batched: net without u_new");
+    FBSMI_NEED(B >= 1 && B <= kMaxGrid, "em_csgm_step_batched: B must be in [1, 2^31 - 1]");
+    FBSMI_NEED(mask->nmasks == 1 || mask->nmasks == B, "em_csgm_step_batched: nmasks must be 1 or B");
+    FBSMI_NEED((net_dtype == 0 || net_dtype == 1) && (out_dtype == 0 || out_dtype == 1),
+               "em_csgm_step_batched: net_dtype and out_dtype must be 0 or 1");
+    FBSMI_NEED(noise_offset >= 0 && noise_total >= 0 && noise_offset <= noise_total - mask->du,
+               "em_csgm_step_batched: the step's noise [noise_offset, noise_offset + du) must lie inside noise_total");
+    FBSMI_NEED(noise_total <= kMaxDraw, "em_csgm_step_batched: the noise draw exceeds 2^32 - 4 elements");
+    BatchArgs a = {};
+    a.us = u; a.net = net; a.v_prev = y0; a.keys = scan_keys; a.us_new = net ? u_new : nullptr;
+    a.role = mask->role; a.img = img;
+    a.du = mask->du; a.dv = mask->dv; a.nmasks = mask->nmasks; a.n = 1;
+    a.cx = cx; a.cs = cs; a.dt = dt; a.sd = c;
+    const dim3 grid((unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t nt = (uint64_t)noise_total, no = (uint64_t)noise_offset;
+    if (net_dtype == 0 && out_dtype == 0) k_em_csgm_step_b<0, 0><<<grid, kBlock, 0, st>>>(a, est_keys, F, sq, nt, no);
+    else if (net_dtype == 0) k_em_csgm_step_b<0, 1><<<grid, kBlock, 0, st>>>(a, est_keys, F, sq, nt, no);
+    else if (out_dtype == 0) k_em_csgm_step_b<1, 0><<<grid, kBlock, 0, st>>>(a, est_keys, F, sq, nt, no);
+    else k_em_csgm_step_b<1, 1><<<grid, kBlock, 0, st>>>(a, est_keys, F, sq, nt, no);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_normal_batched(const uint32_t* keys, int64_t B, int64_t n, float* out, void* stream) {
+    FBSMI_NEED(B >= 1 && n >= 0, "normal_batched: B must be at least 1 and n at least 0");
+    FBSMI_NEED(keys && (n == 0 || out), "normal_batched: null pointer");
+    FBSMI_NEED(n <= kMaxDraw, "normal_batched: a row exceeds 2^32 - 4 elements");
+    if (n == 0) return FBSMI_OK;
+    int64_t bpr = ((n + 1) / 2 + kBlock - 1) / kBlock;   // a thread per pair of elements, at most 64 workgroups per row
+    if (bpr > 64) bpr = 64;
+    FBSMI_NEED(B <= kMaxGrid / bpr, "normal_batched: too many rows for one grid");
+    k_normal_b<<<(unsigned)(B * bpr), kBlock, 0, (hipStream_t)stream>>>(keys, (uint64_t)n, (int)bpr, out);
     FBSMI_LAUNCH_CHECK();
     return FBSMI_OK;
 }

@@ -791,6 +791,31 @@ int fbsmi_em_propose_batched(const fbsmi_em_mask_batch* mask, const float* us, c
                              int net_dtype, int mode, float cx, float cs, float dt, float sd, const uint32_t* keys,
                              int64_t B, int64_t n, float* us_new, void* stream);
 
+/* One step of the image CSGM sampler (fbs_amd/csgm.py; experiments/imgs/inpainting_csgm.py:88-113) for B independent
+ * trajectories in ONE launch: a workgroup per trajectory, a thread per image position, no LDS and no workspace.  With
+ * o = role[e] the (u, v) element of image position e < D = du + dv:
+ *   o >= 0 (unobserved), net given:  x = u[b][o], s = net[b * D + e] (float32, or bfloat16 widened; net_dtype 0 / 1),
+ *       t1 = cx * x, t2 = cs * s, d = t1 + t2, m = x + d * dt, nz = c * z, out = m + nz   -- every operation rounded
+ *       separately -- with z = element noise_offset + o of normal(scan_keys[b], (noise_total,)): fbsmi_em_update on the
+ *       drift -(a u) + b^2 s, bit for bit.  u_new[b][o] = out, and img[b][e] = out when img is given.
+ *   o >= 0, net == NULL:  img[b][e] = u[b][o].
+ *   o < 0 (observed, j = ~o), img given:  img[b][e] = (F * y0[b][j]) + (sq * zj), zj = element j of
+ *       normal(est_keys[b], (dv,)).
+ * img (B, D) is float32 or bfloat16 rounded to nearest even (out_dtype 0 / 1) and may be NULL (the last step: update
+ * only); net (B, D) may be NULL (the first launch: network input only).  u, u_new (B, du) may be the same array; y0
+ * (B, dv); scan_keys, est_keys (B, 2) device arrays, both required.  Table entries are clamped into their part before
+ * they address memory.  Decided on the host before any HIP call, FBSMI_ERR_ARG: a null mask, table, u, y0 (dv > 0) or
+ * key array; neither net nor img; net without u_new; B outside [1, 2^31 - 1] (no cap on rows otherwise); nmasks outside
+ * {1, B}; a dtype flag outside {0, 1}; noise_offset < 0 or noise_offset + du > noise_total; noise_total > 2^32 - 4 (the
+ * draw primitive's counters are 32 bits wide, as in fbsmi_em_finish). */
+int fbsmi_em_csgm_step_batched(const fbsmi_em_mask_batch* mask, const float* u, const void* net, int net_dtype, float cx,
+                               float cs, float dt, float c, const uint32_t* scan_keys, int64_t noise_total,
+                               int64_t noise_offset, const float* y0, float F, float sq, const uint32_t* est_keys,
+                               int out_dtype, void* img, int64_t B, float* u_new, void* stream);
+/* Row b of out (B, n) = fbsmi_normal(keys[b], n), bit for bit, in one launch.  keys (B, 2): device array.  FBSMI_ERR_ARG
+ * for a null pointer, B < 1, n < 0, n > 2^32 - 4 or more workgroups than one grid holds; n == 0 launches nothing. */
+int fbsmi_normal_batched(const uint32_t* keys, int64_t B, int64_t n, float* out, void* stream);
+
 /* HIP-event timing hooks: average duration in microseconds of the propagate ("Euler") kernel
  * over the launches since the last reset; 0 launches -> returns 0. Only measured when
  * fbsmi_lg_sweep_profile(s, 1) was set (events force non-graph launches). */
