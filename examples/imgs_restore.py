@@ -11,7 +11,8 @@ every SMC step is two HIP kernels around one network evaluation (PyTorch-ROCm). 
 gibbs*, filter and pmcmc* methods advance in groups of B, one network evaluation per step for the group (fbs_amd.samplers
 gibbs_kernel_batched, gibbs_init_batched, pmcmc_kernel_batched); every image keeps the keys of the sequential run.  With
 `--method csgm --batch B` the (image, sample) trajectories of the run advance in groups of B (fbs_amd.csgm
-make_image_csgm_batched), each with the key of the sequential run.
+make_image_csgm_batched), each with the key of the sequential run; with `--method twisted --batch B` the (image, sample)
+twisted-SMC runs do (fbs_amd.twisted make_image_twisted_batched: the same keys and draws, its own specified arithmetic).
 
 The reference loads a trained checkpoint (`./checkpoints/<dataset>_<sde>_<epoch>.npz`, a flat `param` / `ema_param`
 vector in ravel_pytree order) and a dataset (`../datasets/mnist.npz`, `datasets/celeba_hq<res>.npy`); neither exists in
@@ -59,7 +60,7 @@ def main(argv=None):
     p.add_argument('--dim', type=int, default=64, help='UNet width (64 in the reference).')
     p.add_argument('--fp32', action='store_true', help='float32 network instead of bf16 autocast.')
     p.add_argument('--chunk', type=int, default=4096, help='Particles per network call (a power of two: MIOpen ships kernels for those batch sizes; bigger calls are faster per particle).')
-    p.add_argument('--batch', type=int, default=1, help="'filter', 'gibbs*' and 'pmcmc*' methods: test images that advance together, one network call per step for all of them; 'csgm': (image, sample) trajectories that advance together, one launch and one network call per step (1: one at a time).")
+    p.add_argument('--batch', type=int, default=1, help="'filter', 'gibbs*' and 'pmcmc*' methods: test images that advance together, one network call per step for all of them; 'csgm': (image, sample) trajectories that advance together, one launch and one network call per step; 'twisted': (image, sample) twisted-SMC runs that advance together, six launches and two network passes per step (1: one at a time).")
     p.add_argument('--batch_init', action='store_true', help="With --batch and a gibbs* method: the images' gibbs_init filters advance together too (gibbs_init_batched); by default gibbs_init runs per image.")
     p.add_argument('--outdir', type=str, default='./imgs/results')
     p.add_argument('--quiet', action='store_true')
@@ -230,6 +231,47 @@ def main(argv=None):
                 print(f'{task} | cSGM x{len(group)} | trajectories: {g0 + len(group)} / {len(jobs)}')
         for head, _, _, restored in images:
             np.save(head + '-csgm', restored)
+            out = restored
+        return out
+    if args.batch > 1 and args.method == 'twisted':
+        # The (image, sample) pairs are independent twisted-SMC runs, grouped exactly as the csgm trajectories above
+        # (make_image_twisted_batched): two network passes and six launches per step for the group; every run's key
+        # follows from its position alone.
+        from fbs_amd.twisted import make_image_twisted_batched
+
+        def score(uv, t):                                                            # differentiable: no no_grad here
+            if args.fp32:
+                return net(uv, t).reshape(uv.shape)
+            with torch.autocast('cuda', dtype=torch.bfloat16):
+                return net(uv, t).float().reshape(uv.shape)
+
+        tw = make_image_twisted_batched(score, ds, sde, ts, args.nparticles, chunk=args.chunk,
+                                        net_input_dtype=torch.float32 if args.fp32 else torch.bfloat16)
+        images, jobs = [], []
+        for k in range(args.ny0s):
+            data_key, subkey = ops.split(data_key)
+            if k < args.start_from:
+                continue
+            k_img, k_mask = ops.split(subkey)
+            test_img = ops.uniform(k_img, (resolution, resolution, nchannels), device=dev)
+            mask = ds.gen_mask(k_mask)
+            _, test_y0 = ds.unpack(test_img, mask)
+            head = os.path.join(args.outdir, f'{args.dataset}-{task}-{args.sde}-{args.nparticles}-{k}')
+            np.savez(head + '-true', test_img=test_img.cpu().numpy())
+            images.append((head, mask, test_y0, np.zeros((args.nsamples, resolution, resolution, nchannels), np.float32)))
+            for i in range(args.nsamples):
+                key, subkey = ops.split(key)
+                jobs.append((len(images) - 1, i, subkey))
+        for g0 in range(0, len(jobs), args.batch):
+            group = jobs[g0:g0 + args.batch]                                       # the last group may be smaller
+            samples = tw.conditional_sampler_batched(np.stack([j[2] for j in group], 0), [images[j[0]][2] for j in group],
+                                                     [images[j[0]][1] for j in group], stratified)
+            for b, (m, i, _) in enumerate(group):
+                images[m][3][i] = samples[b].cpu().numpy()
+            if not args.quiet:
+                print(f'{task} | twisted x{len(group)} | runs: {g0 + len(group)} / {len(jobs)}')
+        for head, _, _, restored in images:
+            np.save(head + '-twisted', restored)
             out = restored
         return out
     for k in range(args.ny0s):

@@ -301,6 +301,14 @@ SIGNATURES = {
     "fbsmi_em_csgm_step_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _vp, C.c_int, _f, _f, _f, _f, _vp, _i64, _i64,
                                              _vp, _f, _f, _vp, C.c_int, _vp, _i64, _vp, _vp]),
     "fbsmi_normal_batched": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "fbsmi_categorical_batched": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "fbsmi_tw_img_gather_batched": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "fbsmi_tw_img_twist_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _vp, C.c_int, _f, _f, _f, _f, _vp, _vp, _vp,
+                                             _vp, _i64, _i64, _vp, _vp, _vp]),
+    "fbsmi_tw_img_cotangent_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _vp, C.c_int, _f, _f, _f, _f, _vp, _i64,
+                                                 _i64, _vp, _vp]),
+    "fbsmi_tw_img_propose_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _vp, C.c_int, _vp, _f, _f, _f, _f, _f, _vp,
+                                               _vp, _i64, _i64, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     # include/fbsmi_nn.h
     "fbsmi_nn_linear_attention": (C.c_int, [_vp, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp]),
     "fbsmi_nn_qkv_linear_attention": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),

@@ -9,8 +9,17 @@
 //   fbsmi_em_propose_batched    ensemble b = fbsmi_em_finish with A = net_A = A[b], n_total = n, row0 = 0, proposal only
 //   fbsmi_em_csgm_step_batched  trajectory b = one step of fbs_amd/csgm.py: fbsmi_em_update, then the next network input
 //   fbsmi_normal_batched        row b = fbsmi_normal(keys[b], n)
+//   fbsmi_categorical_batched   row b = fbsmi_categorical(keys[b], w[b])
 //
-// each bit for bit.  An ensemble has 1 <= n <= 1024 rows, so everything the single-ensemble entry points spread over
+// each bit for bit, and the step of the image twisted SMC (whole-image particles; fbs_amd/twisted.py
+// make_image_twisted_batched), which has no single-ensemble kernel to equal: its arithmetic is specified in include/fbsmi.h
+//
+//   fbsmi_tw_img_gather_batched     the resampled particles (the autograd leaf) and their previous twist values
+//   fbsmi_tw_img_twist_batched      lp = the twisting log-density from the network output; optionally the step's weights
+//   fbsmi_tw_img_cotangent_batched  the output cotangent of the network's vector-Jacobian product
+//   fbsmi_tw_img_propose_batched    the twisted proposal with its in-kernel draw, and both row-summed log-densities
+//
+// An ensemble has 1 <= n <= 1024 rows, so everything the single-ensemble entry points spread over
 // several launches and a workspace in memory -- the two-level logsumexp, the canonical-tree CDFs, the searches, the draws --
 // fits ONE workgroup per ensemble and its LDS.  The trees are built in place in LDS the way k_top_scan (fbsmi_prims.hip)
 // builds the top-level tree: an up-sweep over the element index, zero padded to a power of two, then the two-value descent
@@ -406,6 +415,217 @@ __global__ void __launch_bounds__(kBlock) k_normal_b(const uint32_t* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// image twisted SMC (fbs_amd/twisted.py make_image_twisted_batched; the arithmetic is specified in include/fbsmi.h):
+// particles are whole images, X (B * n, D) in image order; one workgroup per particle row, threads stride over the
+// elements, four consecutive elements per thread and round.  The head of the twisting function -- the Gaussian likelihood
+// of the observed pixels under the one-step denoising estimate den = x + (cx x + cs s) dt -- and its derivative with
+// respect to den are closed forms here; only the network's own vector-Jacobian product stays with autograd.
+// ------------------------------------------------------------------------------------------------
+struct TwArgs {
+    const float* X;
+    const void* net;
+    const float* vjp;
+    const float* y;
+    const uint32_t* keys;
+    const float* tl_in;
+    const float* pl_in;
+    const float* lpg;
+    float* out;        // ct (cotangent) or X_new (propose)
+    void* out2;        // propose: the copy of X_new in the network's input dtype
+    float* lp;
+    float* lw;
+    float* tl;
+    float* pl;
+    const int32_t* v_off;
+    const int32_t* role;
+    int32_t du, dv, nmasks, n;
+    float cx, cs, dt, sd, var_y;
+};
+
+// den = x + rd * dt with rd = (cx * x) + (cs * s), every operation rounded separately
+__device__ __forceinline__ float tw_den(const TwArgs& a, float x, float s, float& rd) {
+    rd = reverse_drift<0>(a.cx, a.cs, x, s);
+    const float p = rd * a.dt;
+    return x + p;
+}
+
+// nlp(v, m, var) = (log(2 pi var) + (v - m)^2 / var) / -2 with lognorm = log(2 pi var) given
+__device__ __forceinline__ float tw_nlp(float v, float m, float var, float lognorm) {
+    const float df = v - m;
+    const float sq = df * df;
+    const float q = sq / var;
+    return (lognorm + q) * -0.5f;
+}
+
+// one round of a row sum: this thread's four terms -> its wave's 256-element segment sum (the order of k_em_finish_b)
+__device__ __forceinline__ void tw_segment(const float (&t)[4], float* seg, int s0, int nseg) {
+    const float s01 = t[0] + t[1], s23 = t[2] + t[3];
+    TreePath path;
+    const float sum = wave_upsweep(s01 + s23, path);
+    const int sg = (s0 >> 8) + ((int)threadIdx.x >> 6);
+    if ((threadIdx.x & 63) == 0 && sg < nseg) seg[sg] = sum;
+}
+
+__device__ __forceinline__ int clamp_index(int i, int last) { return i < 0 ? 0 : (i > last ? last : i); }
+
+__global__ void __launch_bounds__(kBlock) k_tw_gather_b(const float* __restrict__ X, const float* __restrict__ lp,
+                                                        const int32_t* __restrict__ A, int n, int64_t D,
+                                                        float* __restrict__ Xp, float* __restrict__ lpg) {
+    const int64_t row = blockIdx.x;
+    const int64_t b = row / n;
+    const int32_t s = A[row];
+    const int64_t src = b * n + (s < 0 ? 0 : (s > n - 1 ? n - 1 : s));
+    const float* __restrict__ x = X + src * D;
+    float* __restrict__ o = Xp + row * D;
+    for (int64_t e = threadIdx.x; e < D; e += kBlock) o[e] = x[e];
+    if (threadIdx.x == 0 && lpg) lpg[row] = lp[src];
+}
+
+template <int NETDT>
+__global__ void __launch_bounds__(kBlock) k_tw_twist_b(const TwArgs a) {
+    __shared__ float seg[kMaxSeg];
+    const int64_t row = blockIdx.x;
+    const int b = (int)(row / a.n);
+    const int dv = a.dv, D = a.du + dv;
+    const int32_t* __restrict__ v_off = a.v_off + (a.nmasks == 1 ? 0 : (int64_t)b * dv);
+    const float* __restrict__ x = a.X + row * D;
+    const float* __restrict__ y = a.y + (int64_t)b * dv;
+    const int nseg = (dv + 255) >> 8;
+    const int nsp = next_pow2(nseg > 1 ? nseg : 1);
+    const float lognorm = fbsmi_logf(6.2831855f * a.var_y);
+    for (int i = threadIdx.x; i < nsp; i += kBlock) seg[i] = 0.0f;
+    __syncthreads();
+    for (int s0 = 0; s0 < dv; s0 += 4 * kBlock) {   // uniform trip count: every wave takes part in every round
+        const int j0 = s0 + (int)threadIdx.x * 4;
+        float t[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            t[k] = 0.0f;
+            if (j0 + k < dv) {
+                const int e = clamp_index(v_off[j0 + k], D - 1);
+                float rd;
+                const float den = tw_den(a, x[e], net_value<NETDT>(a.net, row * D + e), rd);
+                t[k] = tw_nlp(y[j0 + k], den, a.var_y, lognorm);
+            }
+        }
+        tw_segment(t, seg, s0, nseg);
+    }
+    lds_upsweep(seg, nsp, nsp);
+    if (threadIdx.x == 0) {
+        const float lp = seg[nsp - 1];
+        a.lp[row] = lp;
+        if (a.lw) {
+            const float s1 = a.tl_in[row] + lp;
+            const float s2 = s1 - a.pl_in[row];
+            a.lw[row] = s2 - a.lpg[row];
+        }
+    }
+}
+
+// g = (y - den) / var_y on an observed element (role o < 0, observed element ~o), 0 elsewhere
+template <int NETDT>
+__device__ __forceinline__ float tw_head_grad(const TwArgs& a, const float* __restrict__ y, int o, float x, float s,
+                                              float& rd) {
+    const float den = tw_den(a, x, s, rd);
+    if (o >= 0 || a.dv < 1) return 0.0f;
+    const float df = y[clamp_index(~o, a.dv - 1)] - den;
+    return df / a.var_y;
+}
+
+template <int NETDT>
+__global__ void __launch_bounds__(kBlock) k_tw_cotangent_b(const TwArgs a) {
+    const int64_t row = blockIdx.x;
+    const int b = (int)(row / a.n);
+    const int D = a.du + a.dv;
+    const int32_t* __restrict__ role = a.role + (a.nmasks == 1 ? 0 : (int64_t)b * D);
+    const float* __restrict__ x = a.X + row * D;
+    const float* __restrict__ y = a.y + (int64_t)b * a.dv;
+    const float csdt = a.cs * a.dt;
+    for (int e = threadIdx.x; e < D; e += kBlock) {
+        float rd;
+        const float g = tw_head_grad<NETDT>(a, y, role[e], x[e], net_value<NETDT>(a.net, row * D + e), rd);
+        a.out[row * D + e] = csdt * g;
+    }
+}
+
+template <int NETDT, int OUTDT>
+__global__ void __launch_bounds__(kBlock) k_tw_propose_b(const TwArgs a) {
+    __shared__ float seg_t[kMaxSeg], seg_p[kMaxSeg];
+    const int64_t row = blockIdx.x;
+    const int b = (int)(row / a.n), r = (int)(row - (int64_t)b * a.n);
+    const int D = a.du + a.dv;
+    const int32_t* __restrict__ role = a.role + (a.nmasks == 1 ? 0 : (int64_t)b * D);
+    const float* __restrict__ x = a.X + row * D;
+    const float* __restrict__ vjp = a.vjp + row * D;
+    const float* __restrict__ y = a.y + (int64_t)b * a.dv;
+    const uint32_t k0 = a.keys[2 * b], k1 = a.keys[2 * b + 1];
+    const uint64_t ntot = (uint64_t)a.n * (uint64_t)D;
+    const int nseg = (D + 255) >> 8;
+    const int nsp = next_pow2(nseg);
+    const float c1 = a.cx * a.dt;
+    const float kap = 1.0f + c1;
+    const float var = a.sd * a.sd;
+    const float lognorm = fbsmi_logf(6.2831855f * var);
+    for (int i = threadIdx.x; i < nsp; i += kBlock) seg_t[i] = seg_p[i] = 0.0f;
+    __syncthreads();
+    for (int s0 = 0; s0 < D; s0 += 4 * kBlock) {   // uniform trip count: every wave takes part in every round
+        const int e0 = s0 + (int)threadIdx.x * 4;
+        float tt[4], tp[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            tt[k] = tp[k] = 0.0f;
+            const int e = e0 + k;
+            if (e < D) {
+                const float xv = x[e];
+                float rd;
+                const float g = tw_head_grad<NETDT>(a, y, role[e], xv, net_value<NETDT>(a.net, row * D + e), rd);
+                const float hg = kap * g;
+                const float grad = hg + vjp[e];
+                const float cg = a.cs * grad;
+                const float cd = rd + cg;
+                const float pm = cd * a.dt;
+                const float m = xv + pm;
+                const float z = normal_from_bits(random_bits_at(k0, k1, ntot, (uint64_t)r * D + e));
+                const float nz = a.sd * z;
+                const float xn = m + nz;
+                const float pt = rd * a.dt;
+                const float mt = xv + pt;
+                a.out[row * D + e] = xn;
+                if (a.out2) {
+                    if (OUTDT == 0) ((float*)a.out2)[row * D + e] = xn;
+                    else ((unsigned short*)a.out2)[row * D + e] = f32_to_bf16_bits(xn);
+                }
+                tt[k] = tw_nlp(xn, mt, var, lognorm);
+                tp[k] = tw_nlp(xn, m, var, lognorm);
+            }
+        }
+        tw_segment(tt, seg_t, s0, nseg);
+        tw_segment(tp, seg_p, s0, nseg);
+    }
+    lds_upsweep(seg_t, nsp, nsp);
+    lds_upsweep(seg_p, nsp, nsp);
+    if (threadIdx.x == 0) {
+        a.tl[row] = seg_t[nsp - 1];
+        a.pl[row] = seg_p[nsp - 1];
+    }
+}
+
+// row b of out (B) = fbsmi_categorical(keys[b], w[b]): the CDF tree of k_resample_b, one search by the first thread
+__global__ void __launch_bounds__(kMaxRows) k_categorical_b(const uint32_t* __restrict__ keys, const float* __restrict__ w,
+                                                            int n, int np, int32_t* __restrict__ out) {
+    __shared__ float tr[kMaxRows], cdf[kMaxRows];
+    const int b = blockIdx.x, e = threadIdx.x;
+    tr[e] = e < n ? w[(int64_t)b * n + e] : 0.0f;
+    lds_upsweep(tr, np, np);
+    cdf[e] = lds_scan_at(tr, np, e);
+    __syncthreads();
+    if (e == 0) {
+        const float u = uniform_at(keys[2 * b], keys[2 * b + 1], 1, 0);
+        out[b] = searchsorted_left(cdf, n, bisect_levels(n), cdf[n - 1] * (1.0f - u));
+    }
+}
+
 #define FBSMI_NEED(cond, msg) \
     if (!(cond)) return fail(FBSMI_ERR_ARG, msg)
 #define FBSMI_LAUNCH_CHECK()                                                     \
@@ -433,6 +653,31 @@ int check_em(const char* who, const fbsmi_em_mask_batch* m, int64_t B, int64_t n
     FBSMI_NEED(B * n <= kMaxGrid, w + ": too many rows for one grid");
     if (m->dv > kMaxSeg * 256) return fail(FBSMI_ERR_UNSUPPORTED, w + ": observed part too long");
     return FBSMI_OK;
+}
+
+// the checks the image twisted-SMC entry points share: the particles are whole images, so the draw and the row sums
+// run over D = du + dv
+int check_tw(const char* who, const fbsmi_em_mask_batch* m, int64_t B, int64_t n) {
+    const std::string w(who);
+    FBSMI_NEED(m && m->u_off && m->role && (m->dv == 0 || m->v_off), w + ": null mask");
+    FBSMI_NEED(B >= 1 && n >= 1 && m->du >= 1 && m->dv >= 0, w + ": B, n and du must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, w + ": more than 1024 rows per ensemble");
+    FBSMI_NEED(m->nmasks == 1 || m->nmasks == B, w + ": nmasks must be 1 or B");
+    const int64_t D = (int64_t)m->du + m->dv;
+    FBSMI_NEED(n * D <= kMaxDraw, w + ": the noise draw exceeds 2^32 - 4 elements");
+    FBSMI_NEED(B * n <= kMaxGrid, w + ": too many rows for one grid");
+    if (D > kMaxSeg * 256) return fail(FBSMI_ERR_UNSUPPORTED, w + ": image too long");
+    return FBSMI_OK;
+}
+
+TwArgs tw_args(const fbsmi_em_mask_batch* m, const float* X, const void* net, const float* y, int64_t n, float cx, float cs,
+               float dt, float var_y) {
+    TwArgs a = {};
+    a.X = X; a.net = net; a.y = y;
+    a.v_off = m->v_off; a.role = m->role;
+    a.du = m->du; a.dv = m->dv; a.nmasks = m->nmasks; a.n = (int32_t)n;
+    a.cx = cx; a.cs = cs; a.dt = dt; a.var_y = var_y;
+    return a;
 }
 
 }  // namespace
@@ -588,6 +833,87 @@ int fbsmi_normal_batched(const uint32_t* keys, int64_t B, int64_t n, float* out,
     if (bpr > 64) bpr = 64;
     FBSMI_NEED(B <= kMaxGrid / bpr, "normal_batched: too many rows for one grid");
     k_normal_b<<<(unsigned)(B * bpr), kBlock, 0, (hipStream_t)stream>>>(keys, (uint64_t)n, (int)bpr, out);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_tw_img_gather_batched(const float* X, const float* lp, const int32_t* A, int64_t B, int64_t n, int64_t D,
+                                float* Xp, float* lp_prev_g, void* stream) {
+    FBSMI_NEED(X && A && Xp && (!lp_prev_g || lp), "tw_img_gather_batched: null pointer");
+    FBSMI_NEED(B >= 1 && n >= 1 && D >= 1, "tw_img_gather_batched: B, n and D must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "tw_img_gather_batched: more than 1024 rows per ensemble");
+    FBSMI_NEED(D <= kMaxDraw && n * D <= kMaxDraw, "tw_img_gather_batched: an ensemble exceeds 2^32 - 4 elements");
+    FBSMI_NEED(B * n <= kMaxGrid, "tw_img_gather_batched: too many rows for one grid");
+    FBSMI_NEED(Xp != X, "tw_img_gather_batched: Xp must not alias X");
+    k_tw_gather_b<<<(unsigned)(B * n), kBlock, 0, (hipStream_t)stream>>>(X, lp, A, (int)n, D, Xp, lp_prev_g);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_tw_img_twist_batched(const fbsmi_em_mask_batch* mask, const float* X, const void* net, int net_dtype, float cx,
+                               float cs, float dt, float var_y, const float* y, const float* tl, const float* pl,
+                               const float* lp_prev_g, int64_t B, int64_t n, float* lp, float* lw, void* stream) {
+    const int rc = check_tw("tw_img_twist_batched", mask, B, n);
+    if (rc) return rc;
+    FBSMI_NEED(X && net && lp && (mask->dv == 0 || y), "tw_img_twist_batched: null pointer");
+    FBSMI_NEED(net_dtype == 0 || net_dtype == 1, "tw_img_twist_batched: net_dtype must be 0 or 1");
+    FBSMI_NEED(!lw || (tl && pl && lp_prev_g), "tw_img_twist_batched: the weights need tl, pl and lp_prev_g");
+    TwArgs a = tw_args(mask, X, net, y, n, cx, cs, dt, var_y);
+    a.tl_in = tl; a.pl_in = pl; a.lpg = lp_prev_g; a.lp = lp; a.lw = lw;
+    const dim3 grid((unsigned)(B * n));
+    hipStream_t st = (hipStream_t)stream;
+    if (net_dtype == 0) k_tw_twist_b<0><<<grid, kBlock, 0, st>>>(a);
+    else k_tw_twist_b<1><<<grid, kBlock, 0, st>>>(a);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_tw_img_cotangent_batched(const fbsmi_em_mask_batch* mask, const float* X, const void* net, int net_dtype,
+                                   float cx, float cs, float dt, float var_y, const float* y, int64_t B, int64_t n,
+                                   float* ct, void* stream) {
+    const int rc = check_tw("tw_img_cotangent_batched", mask, B, n);
+    if (rc) return rc;
+    FBSMI_NEED(X && net && ct && (mask->dv == 0 || y), "tw_img_cotangent_batched: null pointer");
+    FBSMI_NEED(net_dtype == 0 || net_dtype == 1, "tw_img_cotangent_batched: net_dtype must be 0 or 1");
+    TwArgs a = tw_args(mask, X, net, y, n, cx, cs, dt, var_y);
+    a.out = ct;
+    const dim3 grid((unsigned)(B * n));
+    hipStream_t st = (hipStream_t)stream;
+    if (net_dtype == 0) k_tw_cotangent_b<0><<<grid, kBlock, 0, st>>>(a);
+    else k_tw_cotangent_b<1><<<grid, kBlock, 0, st>>>(a);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_tw_img_propose_batched(const fbsmi_em_mask_batch* mask, const float* Xp, const void* net, int net_dtype,
+                                 const float* vjp, float cx, float cs, float dt, float sd, float var_y, const float* y,
+                                 const uint32_t* keys, int64_t B, int64_t n, float* X_new, float* tl, float* pl,
+                                 int out_dtype, void* X_new_net, void* stream) {
+    const int rc = check_tw("tw_img_propose_batched", mask, B, n);
+    if (rc) return rc;
+    FBSMI_NEED(Xp && net && vjp && keys && X_new && tl && pl && (mask->dv == 0 || y),
+               "tw_img_propose_batched: null pointer");
+    FBSMI_NEED((net_dtype == 0 || net_dtype == 1) && (out_dtype == 0 || out_dtype == 1),
+               "tw_img_propose_batched: net_dtype and out_dtype must be 0 or 1");
+    FBSMI_NEED(X_new != Xp && X_new_net != (const void*)Xp, "tw_img_propose_batched: X_new must not alias Xp");
+    TwArgs a = tw_args(mask, Xp, net, y, n, cx, cs, dt, var_y);
+    a.vjp = vjp; a.keys = keys; a.sd = sd; a.out = X_new; a.out2 = X_new_net; a.tl = tl; a.pl = pl;
+    const dim3 grid((unsigned)(B * n));
+    hipStream_t st = (hipStream_t)stream;
+    if (net_dtype == 0 && out_dtype == 0) k_tw_propose_b<0, 0><<<grid, kBlock, 0, st>>>(a);
+    else if (net_dtype == 0) k_tw_propose_b<0, 1><<<grid, kBlock, 0, st>>>(a);
+    else if (out_dtype == 0) k_tw_propose_b<1, 0><<<grid, kBlock, 0, st>>>(a);
+    else k_tw_propose_b<1, 1><<<grid, kBlock, 0, st>>>(a);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_categorical_batched(const uint32_t* keys, const float* w, int64_t B, int64_t n, int32_t* out, void* stream) {
+    FBSMI_NEED(keys && w && out, "categorical_batched: null pointer");
+    FBSMI_NEED(B >= 1 && n >= 1 && B <= kMaxGrid, "categorical_batched: B and n must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "categorical_batched: more than 1024 rows per ensemble");
+    const int np = threads_for(n);
+    k_categorical_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(keys, w, (int)n, np, out);
     FBSMI_LAUNCH_CHECK();
     return FBSMI_OK;
 }

@@ -279,6 +279,21 @@ def resample_batched(weights: torch.Tensor, keys, kind: str = "stratified") -> t
     return idx
 
 
+def categorical_batched(keys, weights: torch.Tensor) -> torch.Tensor:
+    """``categorical`` on every row of weights (B, n), n <= 1024, in one launch: entry b of the (B,) int32 result has the
+    bits of ``categorical(keys[b], weights[b])``.  keys (B, 2) uint32 on the host or their bits as an int32 device tensor."""
+    w = _f32c(weights, "weights")
+    if w.dim() != 2:
+        raise ValueError("categorical_batched wants weights of shape (B, n)")
+    B, n = w.shape
+    kd = keys_to_device(keys, w.device)
+    if kd.numel() != 2 * B:
+        raise ValueError("categorical_batched: keys (B, 2) must match weights (B, n)")
+    out = torch.empty(B, dtype=torch.int32, device=w.device)
+    _lib.call("fbsmi_categorical_batched", kd.data_ptr(), w.data_ptr(), B, n, out.data_ptr(), _stream())
+    return out
+
+
 def searchsorted(a: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     a = _f32c(a, "a").reshape(-1)
     qq = _f32c(q, "q")

@@ -9,6 +9,9 @@ resampling, gathers, normalisation and the noise draws are libfbsmi kernels, the
 The reference evaluates the score up to four times per step on the same batch (transition_logpdf, twisting_logpdf, the
 proposal's sampler and its log-density; XLA's CSE merges them under jit).  Here the results are remembered per
 (tensor object, time): one forward evaluation and one forward + backward evaluation per step.
+
+``make_image_twisted_batched`` runs B such SMC runs in lockstep on the fbsmi_tw_img_*_batched kernels: two network passes and
+six launches per step for all of them.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .sdes import make_linear_sde
 
 
@@ -142,3 +145,243 @@ def make_image_twisted(score_fn, ds, sde, ts, nparticles: int, data_variance: fl
                            twisting_prop_sampler=twisting_prop_sampler, twisting_prop_logpdf=twisting_prop_logpdf,
                            reverse_cond_drift=reverse_cond_drift, reverse_drift=reverse_drift,
                            conditional_sampler=conditional_sampler, dt=dt, T=T)
+
+
+def twisted_key_schedule(keys, nsteps: int) -> dict:
+    """Every key ``conditional_sampler`` and ``twisted_smc`` derive from an ensemble's own, for B ensembles, on the host:
+    (filter, select) = split(key); (init, scan) = split(filter, 2); split(scan, nsteps); (resampling_k, prop_k) =
+    split(keys_k, 2).  -> (B, 2) arrays 'filter', 'select', 'init' and (nsteps, B, 2) arrays 'resampling', 'prop', uint32."""
+    keys = np.asarray(keys, np.uint32).reshape(-1, 2)
+    B, T = keys.shape[0], int(nsteps)
+    out = {n: np.zeros((B, 2), np.uint32) for n in ("filter", "select", "init")}
+    out.update({n: np.zeros((T, B, 2), np.uint32) for n in ("resampling", "prop")})
+    for b in range(B):
+        out["filter"][b], out["select"][b] = ops.split(keys[b])
+        sub = twisted_filter_key_schedule(out["filter"][b], T)
+        out["init"][b], out["resampling"][:, b], out["prop"][:, b] = sub["init"][0], sub["resampling"][:, 0], sub["prop"][:, 0]
+    return out
+
+
+def twisted_filter_key_schedule(filter_keys, nsteps: int) -> dict:
+    """The part of ``twisted_key_schedule`` below the filter keys (what ``twisted_smc`` does with its key)."""
+    keys = np.asarray(filter_keys, np.uint32).reshape(-1, 2)
+    B, T = keys.shape[0], int(nsteps)
+    out = {"init": np.zeros((B, 2), np.uint32), "resampling": np.zeros((T, B, 2), np.uint32),
+           "prop": np.zeros((T, B, 2), np.uint32)}
+    for b in range(B):
+        out["init"][b], key_scan = ops.split(keys[b], 2)
+        for k, key_k in enumerate(ops.split(key_scan, T) if T else ()):
+            out["resampling"][k, b], out["prop"][k, b] = ops.split(key_k, 2)
+    return out
+
+
+def make_image_twisted_batched(score_fn, ds, sde, ts, nparticles: int, data_variance: float = 0.06, chunk: int = 4096,
+                               net_input_dtype=torch.float32):
+    """score_fn(uv (rows, w, h, c), t) -> score of the same shape (float32 or bfloat16), differentiable with respect to uv
+    when called with grad enabled.  -> namespace(twisted_smc_batched, conditional_sampler_batched): B independent runs of
+    ``make_image_twisted``'s twisted SMC in lockstep.
+
+        twisted_smc_batched(keys (B, 2), ys, masks, resampling, trace=None) -> (uvs (B, n, w, h, c), log_ws (B, n))
+        conditional_sampler_batched(keys (B, 2), ys, masks, resampling)     -> (B, w, h, c)
+
+    ys: a list of B observations (q, c) or their stack (one (q, c) tensor: shared); masks: one mask or a list of B masks.
+    The keys of twisted_smc_batched are what ``twisted_smc`` takes (the filter keys), those of
+    conditional_sampler_batched what ``conditional_sampler`` takes; all derived keys are computed on the host once
+    (``twisted_key_schedule``) and uploaded once.
+
+    Per step, for all B ensembles: resample_batched, fbsmi_tw_img_gather_batched, ONE network forward with grad on the
+    gathered particles (`chunk` rows at a time), fbsmi_tw_img_cotangent_batched, one torch.autograd.grad per chunk (the
+    network's vector-Jacobian product), fbsmi_tw_img_propose_batched, ONE network forward without grad on the proposed
+    particles, fbsmi_tw_img_twist_batched (twist and weights), normalise_batched: six launches and two network passes,
+    nothing per ensemble and no host synchronisation inside the time loop.  The head of the twisting function -- the
+    Gaussian likelihood of the observed pixels under the one-step denoising estimate -- and its derivative are closed forms
+    inside the kernels; only the network itself is on the autograd tape.
+
+    Unlike the other batched image samplers this path is NOT bit-equal to the loop
+
+        [make_image_twisted(...).conditional_sampler(keys[b], ys[b], resampling, mask_=masks[b]) for b in range(B)]
+
+    That loop sums rows with torch reductions, differentiates the head by autograd and takes the transition's drift from
+    a forward pass of its own; here the rows are summed in the canonical tree, the head's derivative is a closed form and
+    the drift of the transition density is the one the proposal was built from.  What does hold:
+      * the same keys give the same draws: the initial particles and every step's noise z are bit-identical to the loop's
+        (so are the ancestors and the final pick, given bit-identical weights);
+      * the arithmetic is the specification in include/fbsmi.h (fbsmi_tw_img_*_batched), operation by operation;
+      * an ensemble's result does not depend on B, nor on which ensembles share its run, whenever the score function's
+        output row does not depend on which rows share its call.
+
+    trace: a list; entry 0 receives (None, X0, lp0, log_ws0), every step appends (ancestors (B, n) int32,
+    X_new (B, n, D), lp (B, n), normalised log_ws (B, n)), all clones.
+
+    The lockstep path needs the package's stratified or systematic resampler, masks of one (du, dv), nparticles <= 1024
+    and nparticles * w * h * c <= 2^32 - 4; anything else runs the loop above (``twisted_smc`` per ensemble for
+    twisted_smc_batched; trace is then left untouched)."""
+    from .samplers import resampling as _resampling
+    from .samplers.smc import twisted_smc
+    from .score import _NET_DT, ScoreBridge
+    ts = np.asarray(ts, np.float64)
+    T = float(ts[-1])
+    nsteps = ts.size - 1
+    dt = T / nsteps
+    n = int(nparticles)
+    chunk = int(chunk)
+    discretise = make_linear_sde(sde)[0]
+    xy_shape = tuple(ds.image_shape)
+    D = int(np.prod(xy_shape))
+    single = make_image_twisted(score_fn, ds, sde, ts, nparticles, data_variance)
+    sb = ScoreBridge(score_fn, ds, sde, ts, chunk=chunk, net_input_dtype=net_input_dtype)   # mask tables and buffers, cached
+    # per-time float32 scalars from float64: entry k belongs to reverse time ts[k] (forward time s = T - ts[k])
+    s_fwd = [T - float(t) for t in ts]
+    FQ = [tuple(float(x) for x in discretise(s_, float(ts[0]))) for s_ in s_fwd]
+    f32 = lambda v: float(np.float32(v))
+    tab = {"cx": [f32(-float(sde.drift(1.0, s_))) for s_ in s_fwd],
+           "cs": [f32(float(sde.dispersion(s_)) ** 2) for s_ in s_fwd],
+           "sd": [f32(math.sqrt(dt) * float(sde.dispersion(s_))) for s_ in s_fwd],
+           "var_y": [f32(F ** 2 * data_variance + Q) for F, Q in FQ]}
+    dt32 = f32(dt)
+
+    def _inputs(keys, ys, masks):
+        keys = np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys, np.uint32).reshape(-1, 2)
+        B = keys.shape[0]
+        per_mask = not hasattr(masks, "unobs_inds_ravelled")
+        if per_mask and len(masks) != B:
+            raise ValueError(f"{len(masks)} masks for {B} ensembles")
+        shared_y = isinstance(ys, torch.Tensor) and ys.dim() == 2
+        if not shared_y and len(ys) != B:
+            raise ValueError(f"{len(ys)} observations for {B} ensembles")
+        y = lambda b: ys if shared_y else ys[b]
+        mask = lambda b: masks[b] if per_mask else masks
+        return keys, B, per_mask, y, mask
+
+    def _lockstep(B, per_mask, mask, resampling):
+        rname = "stratified" if resampling is _resampling.stratified else (
+            "systematic" if resampling is _resampling.systematic else None)
+        if rname is None or n > 1024 or n * D > 2 ** 32 - 4:
+            return None
+        ems = [sb._em_mask(mask(b)) for b in range(B if per_mask else 1)]
+        if any((e.du, e.dv) != (ems[0].du, ems[0].dv) for e in ems):
+            return None
+        return rname
+
+    def _score_rows(X4, s_, net, vjp_of=None):
+        """The network on the rows of X4 (R, w, h, c), `chunk` at a time -> net (R, D); with vjp_of (a function that
+        turns the complete net into the cotangent (R, D)) also the vector-Jacobian product (R, D) float32."""
+        R = X4.shape[0]
+        tape = []
+        for s in range(0, R, chunk):
+            xc = X4[s:s + chunk]
+            if vjp_of is not None:
+                xc = xc.detach().requires_grad_(True)
+            out = score_fn(xc, s_)
+            if net is None:
+                dtype = out.dtype if out.dtype in _NET_DT else torch.float32
+                net = sb._buffer("tw_net", (R, D), dtype, X4.device)
+            net[s:s + chunk] = out.detach().reshape(-1, D)
+            tape.append((xc, out))
+        if vjp_of is None:
+            return net, None
+        ct = vjp_of(net)
+        vjp = sb._buffer("tw_vjp", (R, D), torch.float32, X4.device)
+        for i, (xc, out) in enumerate(tape):
+            g = ct[i * chunk:(i + 1) * chunk].reshape(out.shape).to(out.dtype)
+            vjp[i * chunk:(i + 1) * chunk] = torch.autograd.grad(out, xc, grad_outputs=g)[0].reshape(-1, D)
+        return net, vjp
+
+    def _run(filter_keys, B, per_mask, y, mask, rname, trace):
+        dev = ds.device
+        mb = sb.em_mask_batch([mask(b) for b in range(B)] if per_mask else [mask(0)], B)
+        dv = mb.dv
+        if mb.D != D:
+            raise ValueError(f"the masks cover {mb.D} elements, an image has {D}")
+        ks = twisted_filter_key_schedule(filter_keys, nsteps)                         # uploaded once
+        k_init, k_res, k_prop = (ops.keys_to_device(ks[name], dev) for name in ("init", "resampling", "prop"))
+        yv = torch.stack([ops._f32c(y(b), "y").reshape(-1) for b in range(B)], 0).contiguous()
+        if yv.shape[1] != dv:
+            raise ValueError(f"y holds {yv.shape[1]} floats, the masks' observed part {dv}")
+        R = B * n
+        st = ops._stream
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        own_input = net_input_dtype != torch.float32          # the no-grad pass reads a copy in the network's input dtype
+        Xin = sb._buffer("tw_in", (R,) + xy_shape, net_input_dtype, dev) if own_input else None
+
+        def twist(X, net, k, tl=None, pl=None, lpg=None):
+            lp, lw = new(B, n), (new(B, n) if tl is not None else None)
+            _lib.call("fbsmi_tw_img_twist_batched", mb.ref, X.data_ptr(), net.data_ptr(), _NET_DT[net.dtype], tab["cx"][k],
+                      tab["cs"][k], dt32, tab["var_y"][k], ptr(yv), ptr(tl), ptr(pl), ptr(lpg), B, n, lp.data_ptr(), ptr(lw),
+                      st())
+            return lp, lw
+
+        # exp(normalised log-weights), what the next resampling reads: the bits of exp(ops.normalise(lw[b], log_space=True));
+        # the log-space form is computed only where someone reads it (the trace, the result)
+        weights = lambda lw_: ops.normalise_batched(lw_, log_space=False)
+
+        X = new(R, D)
+        _lib.call("fbsmi_normal_batched", k_init.data_ptr(), B, n * D, X.data_ptr(), st())   # init_sampler
+        with torch.no_grad():
+            src = X if not own_input else Xin.copy_(X.reshape(Xin.shape))
+            net, _ = _score_rows(src.reshape((R,) + xy_shape), s_fwd[0], None)
+        lp, _ = twist(X, net, 0)
+        w = weights(lp)
+        if trace is not None:
+            trace.append((None, X.reshape(B, n, D).clone(), lp.clone(), ops.normalise_batched(lp, log_space=True)))
+        for k in range(nsteps):
+            k1 = k + 1                                                                # t_prev = ts[k + 1] (smc.py:306-307)
+            A = ops.resample_batched(w, k_res[k], rname)
+            Xp, lpg = new(R, D), new(B, n)
+            _lib.call("fbsmi_tw_img_gather_batched", X.data_ptr(), lp.data_ptr(), A.data_ptr(), B, n, D, Xp.data_ptr(),
+                      lpg.data_ptr(), st())
+
+            def cotangent(net_):
+                ct = sb._buffer("tw_ct", (R, D), torch.float32, dev)
+                _lib.call("fbsmi_tw_img_cotangent_batched", mb.ref, Xp.data_ptr(), net_.data_ptr(), _NET_DT[net_.dtype],
+                          tab["cx"][k1], tab["cs"][k1], dt32, tab["var_y"][k1], ptr(yv), B, n, ct.data_ptr(), st())
+                return ct
+
+            # the library convolutions' backward kernels are kept out of the differentiable pass (torch's own are used), as
+            # in make_image_twisted.reverse_cond_drift
+            lib_convs = torch.backends.cudnn.enabled
+            torch.backends.cudnn.enabled = False
+            try:
+                with torch.enable_grad():
+                    net_p, vjp = _score_rows(Xp.reshape((R,) + xy_shape), s_fwd[k1], None, cotangent)
+            finally:
+                torch.backends.cudnn.enabled = lib_convs
+            X_new, tl, pl = new(R, D), new(B, n), new(B, n)
+            _lib.call("fbsmi_tw_img_propose_batched", mb.ref, Xp.data_ptr(), net_p.data_ptr(), _NET_DT[net_p.dtype],
+                      vjp.data_ptr(), tab["cx"][k1], tab["cs"][k1], dt32, tab["sd"][k1], tab["var_y"][k1], ptr(yv),
+                      k_prop[k].data_ptr(), B, n, X_new.data_ptr(), tl.data_ptr(), pl.data_ptr(), _NET_DT[net_input_dtype],
+                      Xin.data_ptr() if own_input else None, st())
+            with torch.no_grad():
+                net, _ = _score_rows((Xin if own_input else X_new).reshape((R,) + xy_shape), s_fwd[k1], None)
+            lp, lw = twist(X_new, net, k1, tl, pl, lpg)
+            w = weights(lw)
+            X = X_new
+            if trace is not None:
+                trace.append((A.clone(), X.reshape(B, n, D).clone(), lp.clone(), ops.normalise_batched(lw, log_space=True)))
+        last = lw if nsteps else lp
+        return X.reshape((B, n) + xy_shape), ops.normalise_batched(last, log_space=True)
+
+    def twisted_smc_batched(keys, ys, masks, resampling, trace=None):
+        keys, B, per_mask, y, mask = _inputs(keys, ys, masks)
+        rname = _lockstep(B, per_mask, mask, resampling)
+        if rname is None:
+            runs = [twisted_smc(keys[b], y(b), ts, single.init_sampler, single.transition_logpdf, single.twisting_logpdf,
+                                single.twisting_prop_sampler, single.twisting_prop_logpdf, resampling=resampling,
+                                nparticles=nparticles, mask_=mask(b)) for b in range(B)]
+            return torch.stack([r[0] for r in runs], 0), torch.stack([r[1] for r in runs], 0)
+        return _run(keys, B, per_mask, y, mask, rname, trace)
+
+    def conditional_sampler_batched(keys, ys, masks, resampling):
+        keys, B, per_mask, y, mask = _inputs(keys, ys, masks)
+        rname = _lockstep(B, per_mask, mask, resampling)
+        if rname is None:
+            return torch.stack([single.conditional_sampler(keys[b], y(b), resampling, mask_=mask(b)) for b in range(B)], 0)
+        top = [ops.split(keys[b]) for b in range(B)]                                  # (filter, select)
+        uvs, log_ws = _run(np.stack([t[0] for t in top], 0), B, per_mask, y, mask, rname, None)
+        pick = ops.categorical_batched(np.stack([t[1] for t in top], 0), ops.math_map("exp", log_ws))
+        pick = pick.long().clamp_(0, n - 1)
+        return uvs[torch.arange(B, device=uvs.device), pick]
+
+    return SimpleNamespace(twisted_smc_batched=twisted_smc_batched, conditional_sampler_batched=conditional_sampler_batched,
+                           single=single, dt=dt, T=T)

@@ -815,6 +815,58 @@ int fbsmi_em_csgm_step_batched(const fbsmi_em_mask_batch* mask, const float* u, 
 /* Row b of out (B, n) = fbsmi_normal(keys[b], n), bit for bit, in one launch.  keys (B, 2): device array.  FBSMI_ERR_ARG
  * for a null pointer, B < 1, n < 0, n > 2^32 - 4 or more workgroups than one grid holds; n == 0 launches nothing. */
 int fbsmi_normal_batched(const uint32_t* keys, int64_t B, int64_t n, float* out, void* stream);
+/* Row b of out (B) = fbsmi_categorical(keys[b], w[b], n), bit for bit, in one launch: one workgroup per ensemble, the CDF
+ * tree in LDS, no workspace.  keys (B, 2), w (B, n): device arrays.  Refusals as fbsmi_normalise_batched. */
+int fbsmi_categorical_batched(const uint32_t* keys, const float* w, int64_t B, int64_t n, int32_t* out, void* stream);
+
+/* ---- the step of the image twisted SMC for B ensembles in lockstep (fbs_amd/twisted.py make_image_twisted_batched;
+ * experiments/imgs/inpainting_twisted.py:97-154; score mode only) ----
+ * Particles are whole images: X (B * n, D) float32 in image order, D = du + dv = w * h * c, row b * n + r = particle r of
+ * ensemble b.  role[e] < 0: image element e is observed element ~role[e] of y (B, dv); v_off[j] is the image element of
+ * observed element j.  net (B * n, D) is the score at the rows of the X it comes with, float32 or bfloat16 widened
+ * (net_dtype 0 / 1).  cx = -a(s), cs = b(s)^2, dt, sd = sqrt(dt) b(s), var_y = F(s)^2 data_variance + Q(s) at the forward
+ * time s = T - t of the step: float64 on the host, rounded to float32.  One workgroup of 256 threads per row.
+ *
+ * Every operation below is one float32 operation, rounded to nearest, in the order written (no fused multiply-add):
+ *   t1 = cx * x,  t2 = cs * s,  rd = t1 + t2,  p = rd * dt,  den = x + p                 (the one-step denoising estimate)
+ *   nlp(a, m, v):  df = a - m,  sq = df * df,  q = sq / v,  (fbsmi_logf(6.2831855f * v) + q) * -0.5f
+ *   g = (y[b][~role[e]] - den_e) / var_y on an observed element e, 0 elsewhere
+ * A row sum ("tree-sum") over an index i in [0, d) is the canonical pairwise tree of include/fbsmi_math.h over i, zero
+ * padded: four consecutive elements in a thread ((t0 + t1) + (t2 + t3)), six levels in the wave, the 256-element segment
+ * sums in LDS and the same tree over the segments.  Table entries are clamped into their range before they address
+ * memory, ancestors into [0, n - 1].
+ *
+ * Decided on the host before any HIP call: FBSMI_ERR_ARG for a null pointer (mask, tables, or any array the call needs),
+ * B < 1, n < 1, nmasks outside {1, B}, a dtype flag outside {0, 1}, n * D > 2^32 - 4 and B * n > 2^31 - 1;
+ * FBSMI_ERR_UNSUPPORTED for n > 1024 and D > 2^20.
+ *
+ * gather: Xp[b][r] = X[b][A[b][r]] and, when lp_prev_g is given, lp_prev_g[b][r] = lp[b][A[b][r]].  Xp (float32: the
+ * autograd leaf) must not alias X.  D is passed as a number: no mask is read. */
+int fbsmi_tw_img_gather_batched(const float* X, const float* lp, const int32_t* A, int64_t B, int64_t n, int64_t D,
+                                float* Xp, float* lp_prev_g, void* stream);
+/* twist: lp[row] = tree-sum over the observed index j in [0, dv) of nlp(y[b][j], den_{v_off[j]}, var_y) (0 for dv == 0).
+ * With lw given (tl, pl, lp_prev_g (B * n) are then required):  s1 = tl + lp,  s2 = s1 - pl,  lw = s2 - lp_prev_g  -- the
+ * unnormalised log-weights of a step; without it, the initial ones. */
+int fbsmi_tw_img_twist_batched(const fbsmi_em_mask_batch* mask, const float* X, const void* net, int net_dtype, float cx,
+                               float cs, float dt, float var_y, const float* y, const float* tl, const float* pl,
+                               const float* lp_prev_g, int64_t B, int64_t n, float* lp, float* lw, void* stream);
+/* cotangent: ct[row][e] = (cs * dt) * g_e, float32 (B * n, D): d lp / d net, the output cotangent of the network's
+ * vector-Jacobian product. */
+int fbsmi_tw_img_cotangent_batched(const fbsmi_em_mask_batch* mask, const float* X, const void* net, int net_dtype,
+                                   float cx, float cs, float dt, float var_y, const float* y, int64_t B, int64_t n,
+                                   float* ct, void* stream);
+/* propose: with vjp (B * n, D) float32 = the vector-Jacobian product of the network at Xp with cotangent ct,
+ *   c1 = cx * dt,  kap = 1 + c1,  hg = kap * g,  grad = hg + vjp       (d lp / d x: the head in closed form + the network)
+ *   cg = cs * grad,  cd = rd + cg,  pm = cd * dt,  m = x + pm          (the twisted proposal's mean)
+ *   nz = sd * z,  x_new = m + nz,  z = element r * D + e of normal(keys[b], (n * D,)) = of normal(keys[b], (n, w, h, c))
+ *   var = sd * sd;  tl[row] = tree-sum over e in [0, D) of nlp(x_new, den, var)     (the transition density)
+ *                   pl[row] = tree-sum over e in [0, D) of nlp(x_new, m, var)       (the proposal density)
+ * X_new (B * n, D) float32 must not alias Xp; X_new_net, nullable, receives a copy of X_new in float32 or bfloat16 rounded
+ * to nearest even (out_dtype 0 / 1): the input of the next network call.  keys (B, 2): device array. */
+int fbsmi_tw_img_propose_batched(const fbsmi_em_mask_batch* mask, const float* Xp, const void* net, int net_dtype,
+                                 const float* vjp, float cx, float cs, float dt, float sd, float var_y, const float* y,
+                                 const uint32_t* keys, int64_t B, int64_t n, float* X_new, float* tl, float* pl,
+                                 int out_dtype, void* X_new_net, void* stream);
 
 /* HIP-event timing hooks: average duration in microseconds of the propagate ("Euler") kernel
  * over the launches since the last reset; 0 launches -> returns 0. Only measured when
