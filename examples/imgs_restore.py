@@ -106,7 +106,8 @@ def main(argv=None):
 
     sb = ScoreBridge(lambda x, t: run(net, x, t), ds, sde, ts, chunk=args.chunk, mode='drift' if args.sb else 'score',
                      net_input_dtype=torch.float32 if args.fp32 else torch.bfloat16,
-                     fwd_drift_fn=(lambda x, t: run(net_fwd, x.unsqueeze(0), t).float().reshape(x.shape)) if args.sb else None)
+                     fwd_drift_fn=(lambda x, t: run(net_fwd, x.unsqueeze(0), t).float().reshape(x.shape)) if args.sb else None,
+                     fwd_drift_rows_fn=(lambda x, t: run(net_fwd, x, t)) if args.sb else None)
     x_shape = tuple(ds.unobs_shape)
     delta = float(args.method.split('-')[-1]) if ('pmcmc' in args.method and len(args.method.split('-')) > 1) else None
     eb, ef = ('eb' in args.method, 'ef' in args.method) if 'gibbs' in args.method else (True, True)

@@ -302,6 +302,10 @@ SIGNATURES = {
                                              _vp, _f, _f, _vp, C.c_int, _vp, _i64, _vp, _vp]),
     "fbsmi_normal_batched": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "fbsmi_categorical_batched": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "fbsmi_linear_path_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_int,
+                                            _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "fbsmi_em_fwd_step_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _i64, _vp, _vp, _vp, _vp, C.c_int, _f, _f, _vp,
+                                            _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "fbsmi_tw_img_gather_batched": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "fbsmi_tw_img_twist_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _vp, C.c_int, _f, _f, _f, _f, _vp, _vp, _vp,
                                              _vp, _i64, _i64, _vp, _vp, _vp]),

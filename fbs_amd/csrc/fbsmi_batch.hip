@@ -10,6 +10,8 @@
 //   fbsmi_em_csgm_step_batched  trajectory b = one step of fbs_amd/csgm.py: fbsmi_em_update, then the next network input
 //   fbsmi_normal_batched        row b = fbsmi_normal(keys[b], n)
 //   fbsmi_categorical_batched   row b = fbsmi_categorical(keys[b], w[b])
+//   fbsmi_linear_path_batched   ensemble b = fbsmi_linear_path on normal(keys[b], (T, D)), written unpacked and in either order
+//   fbsmi_em_fwd_step_batched   ensemble b = fbsmi_em_update on its own image, the path point written unpacked
 //
 // each bit for bit, and the step of the image twisted SMC (whole-image particles; fbs_amd/twisted.py
 // make_image_twisted_batched), which has no single-ensemble kernel to equal: its arithmetic is specified in include/fbsmi.h
@@ -626,9 +628,106 @@ __global__ void __launch_bounds__(kMaxRows) k_categorical_b(const uint32_t* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// forward noising paths of B ensembles (ScoreBridge.fwd_sampler_batched / fwd_ys_sampler_batched): the state is an image
+// (B, D) in image order, its path is written ALREADY UNPACKED -- image position e with o = role[e] >= 0 is element o of the
+// u output, o < 0 element ~o of the v output -- at base + slot * slot_stride + b * b_stride + element.  A NULL role table
+// is the identity layout: every position goes to the u output, du = D.  `bpr` workgroups per ensemble, the threads of an
+// ensemble stride over its positions (any D); a thread touches only its own position: no barrier, no LDS.
+// ------------------------------------------------------------------------------------------------
+struct PathOut {
+    float* u;
+    float* v;            // nullable: the observed half is not wanted
+    int64_t u_slot, u_b, v_slot, v_b;
+};
+
+struct PathArgs {
+    const int32_t* role;   // (nmasks, D), or NULL
+    const float* x0s;      // (B, du)
+    const float* y0s;      // (B, dv)
+    const uint32_t* keys;  // (B, 2)
+    int32_t du, dv, nmasks, bpr;
+    PathOut out;
+};
+
+// where image position e of ensemble b lives: `part` (x0s or y0s row / u or v output), element o clamped into its part
+// whatever the table holds; false when the position has no element (dv == 0 behind a bad table)
+__device__ __forceinline__ bool path_element(const PathArgs& a, int b, int64_t e, bool& unobs, int& o) {
+    const int r = a.role ? a.role[(a.nmasks == 1 ? 0 : (int64_t)b * (a.du + a.dv)) + e] : (int)e;
+    unobs = r >= 0;
+    o = unobs ? r : ~r;
+    const int last = (unobs ? a.du : a.dv) - 1;
+    o = o > last ? last : o;
+    return o >= 0;
+}
+
+__device__ __forceinline__ float path_initial(const PathArgs& a, int b, bool unobs, int o) {
+    return unobs ? a.x0s[(int64_t)b * a.du + o] : a.y0s[(int64_t)b * a.dv + o];
+}
+
+__device__ __forceinline__ void path_store(const PathOut& p, int b, bool unobs, int o, int64_t slot, float x) {
+    if (unobs) p.u[slot * p.u_slot + b * p.u_b + o] = x;
+    else if (p.v) p.v[slot * p.v_slot + b * p.v_b + o] = x;
+}
+
+// ensemble b = k_linear_path (fbsmi_sde.hip) on normal(keys[b], (T, D)), the same expression under the same contraction
+// setting, with the draw made here: point k lands in slot T - k (reverse) or k
+__global__ void __launch_bounds__(64) k_linear_path_b(const PathArgs a, const float* __restrict__ F,
+                                                      const float* __restrict__ S, int T, int reverse) {
+    const int b = blockIdx.x / a.bpr, q = blockIdx.x - b * a.bpr;
+    const int D = a.du + a.dv;
+    const uint32_t k0 = a.keys[2 * b], k1 = a.keys[2 * b + 1];
+    const uint64_t ntot = (uint64_t)T * (uint64_t)D;
+    for (int64_t e = q * 64 + (int)threadIdx.x; e < D; e += a.bpr * 64) {
+        bool unobs;
+        int o;
+        if (!path_element(a, b, e, unobs, o)) continue;
+        float x = path_initial(a, b, unobs, o);
+        path_store(a.out, b, unobs, o, reverse ? T : 0, x);
+        for (int k = 0; k < T; ++k) {
+            const float xi = normal_at(k0, k1, ntot, (uint64_t)k * D + e);
+            x = F[k] * x + S[k] * xi;
+            path_store(a.out, b, unobs, o, reverse ? T - 1 - k : k + 1, x);
+        }
+    }
+}
+
+// ensemble b = one fbsmi_em_update (k_em_update, fbsmi_sde.hip) on its own image: out = (x + f * ddt) + c * xi with
+// xi = element noff + e of normal(keys[b], (ntot,)); net == NULL assembles the initial state from x0s / y0s instead.  The
+// state read and the network read are coalesced (position e of row b); x_out may be x.
+template <int NETDT>
+__global__ void __launch_bounds__(kBlock) k_em_fwd_step_b(const PathArgs a, const float* x, const void* __restrict__ net,
+                                                          float ddt, float c, uint64_t ntot, uint64_t noff, float* x_out,
+                                                          int64_t store_slot) {
+    const int b = blockIdx.x / a.bpr, q = blockIdx.x - b * a.bpr;
+    const int D = a.du + a.dv;
+    uint32_t k0 = 0, k1 = 0;
+    if (net) {
+        k0 = a.keys[2 * b];
+        k1 = a.keys[2 * b + 1];
+    }
+    for (int64_t e = q * kBlock + (int)threadIdx.x; e < D; e += a.bpr * kBlock) {
+        bool unobs;
+        int o;
+        const bool has = path_element(a, b, e, unobs, o);
+        const int64_t at = (int64_t)b * D + e;
+        float out;
+        if (net) {
+            const float f = net_value<NETDT>(net, at);
+            const float m = x[at] + f * ddt;
+            const float nz = c * normal_at(k0, k1, ntot, noff + (uint64_t)e);
+            out = m + nz;
+        } else {
+            out = has ? path_initial(a, b, unobs, o) : 0.0f;
+        }
+        x_out[at] = out;
+        if (store_slot >= 0 && has) path_store(a.out, b, unobs, o, store_slot, out);
+    }
+}
+
 #define FBSMI_NEED(cond, msg) \
     if (!(cond)) return fail(FBSMI_ERR_ARG, msg)
-#define FBSMI_LAUNCH_CHECK()                                                     \
+#define FBSMI_LAUNCH_CHECK()                                                 \
     do {                                                                         \
         hipError_t e_ = hipGetLastError();                                       \
         if (e_ != hipSuccess) return fail(FBSMI_ERR_HIP, hipGetErrorString(e_)); \
@@ -678,6 +777,32 @@ TwArgs tw_args(const fbsmi_em_mask_batch* m, const float* X, const void* net, co
     a.du = m->du; a.dv = m->dv; a.nmasks = m->nmasks; a.n = (int32_t)n;
     a.cx = cx; a.cs = cs; a.dt = dt; a.var_y = var_y;
     return a;
+}
+
+// the checks the two forward-path entry points share, and their launch geometry (`block` threads, at most 64 workgroups
+// per ensemble); everything here reads values only
+int path_args(const char* who, const fbsmi_em_mask_batch* m, int64_t D, const float* x0s, const float* y0s,
+              bool need_initial, const uint32_t* keys, bool need_keys, int64_t B, int block, float* out_u,
+              int64_t u_slot_stride, int64_t u_b_stride, float* out_v, int64_t v_slot_stride, int64_t v_b_stride,
+              PathArgs* a) {
+    const std::string w(who);
+    FBSMI_NEED(!m || (m->role && m->du >= 1 && m->dv >= 0), w + ": a mask needs its role table, du >= 1 and dv >= 0");
+    FBSMI_NEED(D >= 1 && D <= kMaxGrid && (!m || (int64_t)m->du + m->dv == D),
+               w + ": D must be in [1, 2^31 - 1] and equal du + dv of the mask");
+    FBSMI_NEED(B >= 1 && B <= kMaxGrid, w + ": B must be in [1, 2^31 - 1]");
+    FBSMI_NEED(!m || m->nmasks == 1 || m->nmasks == B, w + ": nmasks must be 1 or B");
+    const int64_t dv = m ? m->dv : 0;
+    FBSMI_NEED(!need_initial || (x0s && (dv == 0 || y0s)), w + ": null x0s or y0s");
+    FBSMI_NEED(!need_keys || keys, w + ": null keys");
+    int64_t bpr = (D + block - 1) / block;
+    if (bpr > 64) bpr = 64;
+    FBSMI_NEED(B <= kMaxGrid / bpr, w + ": too many ensembles for one grid");
+    *a = PathArgs{};
+    a->role = m ? m->role : nullptr;
+    a->x0s = x0s; a->y0s = y0s; a->keys = keys;
+    a->du = (int32_t)(D - dv); a->dv = (int32_t)dv; a->nmasks = m ? m->nmasks : 1; a->bpr = (int32_t)bpr;
+    a->out = PathOut{out_u, out_v, u_slot_stride, u_b_stride, v_slot_stride, v_b_stride};
+    return FBSMI_OK;
 }
 
 }  // namespace
@@ -914,6 +1039,47 @@ int fbsmi_categorical_batched(const uint32_t* keys, const float* w, int64_t B, i
     if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "categorical_batched: more than 1024 rows per ensemble");
     const int np = threads_for(n);
     k_categorical_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(keys, w, (int)n, np, out);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_linear_path_batched(const fbsmi_em_mask_batch* mask, int64_t D, const float* F, const float* S, const float* x0s,
+                              const float* y0s, const uint32_t* keys, int64_t B, int32_t T, int reverse, float* out_u,
+                              int64_t u_slot_stride, int64_t u_b_stride, float* out_v, int64_t v_slot_stride,
+                              int64_t v_b_stride, void* stream) {
+    FBSMI_NEED(T >= 0 && (T == 0 || (F && S)) && out_u, "linear_path_batched: T < 0, or null F, S or out_u");
+    PathArgs a;
+    const int rc = path_args("linear_path_batched", mask, D, x0s, y0s, true, keys, true, B, 64, out_u, u_slot_stride,
+                             u_b_stride, out_v, v_slot_stride, v_b_stride, &a);
+    if (rc) return rc;
+    FBSMI_NEED((int64_t)T * D <= kMaxDraw, "linear_path_batched: the noise draw exceeds 2^32 - 4 elements");
+    k_linear_path_b<<<(unsigned)(B * a.bpr), 64, 0, (hipStream_t)stream>>>(a, F, S, (int)T, reverse != 0);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_em_fwd_step_batched(const fbsmi_em_mask_batch* mask, int64_t D, const float* x0s, const float* y0s, const float* x,
+                              const void* net, int net_dtype, float ddt, float c, const uint32_t* keys, int64_t noise_total,
+                              int64_t noise_offset, int64_t B, float* x_out, int64_t store_slot, float* out_u,
+                              int64_t u_slot_stride, int64_t u_b_stride, float* out_v, int64_t v_slot_stride,
+                              int64_t v_b_stride, void* stream) {
+    FBSMI_NEED((!net || x) && (store_slot < 0 || out_u), "em_fwd_step_batched: net without x, or store_slot without out_u");
+    PathArgs a;
+    const int rc = path_args("em_fwd_step_batched", mask, D, x0s, y0s, net == nullptr, keys, net != nullptr, B, kBlock,
+                             out_u, u_slot_stride, u_b_stride, out_v, v_slot_stride, v_b_stride, &a);
+    if (rc) return rc;
+    FBSMI_NEED(net_dtype == 0 || net_dtype == 1, "em_fwd_step_batched: net_dtype must be 0 or 1");
+    if (net) {
+        FBSMI_NEED(noise_offset >= 0 && noise_total >= 0 && noise_offset <= noise_total - D,
+                   "em_fwd_step_batched: the step's noise [noise_offset, noise_offset + D) must lie inside noise_total");
+        FBSMI_NEED(noise_total <= kMaxDraw, "em_fwd_step_batched: the noise draw exceeds 2^32 - 4 elements");
+    }
+    FBSMI_NEED(x_out, "em_fwd_step_batched: null x_out");
+    const dim3 grid((unsigned)(B * a.bpr));
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t nt = (uint64_t)noise_total, no = (uint64_t)noise_offset;
+    if (net_dtype == 0) k_em_fwd_step_b<0><<<grid, kBlock, 0, st>>>(a, x, net, ddt, c, nt, no, x_out, store_slot);
+    else k_em_fwd_step_b<1><<<grid, kBlock, 0, st>>>(a, x, net, ddt, c, nt, no, x_out, store_slot);
     FBSMI_LAUNCH_CHECK();
     return FBSMI_OK;
 }

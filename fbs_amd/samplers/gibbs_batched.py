@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..score import bridge_of
+from ..score import bridge_of, is_own_method
 from .gibbs import bridge_sampler, force_move, gibbs_kernel
 
 MAX_LOCKSTEP_ROWS = 1024                                   # rows of one ensemble in the batched kernels
@@ -63,7 +63,9 @@ def gibbs_kernel_batched(keys, x0s, y0s, us_stars, bs_stars, ts, fwd_sampler, sd
     The ensembles advance in lockstep -- one network call per step, one launch per sampler operation, no host
     synchronisation inside the time loop -- when the closures are one ScoreBridge's own, ``mask_`` is the only keyword,
     explicit_backward is set, the masks have one shape and an ensemble has at most 1024 rows.  Anything else runs the loop
-    above: the same result without the speed-up."""
+    above: the same result without the speed-up.  The forward paths before and after the loop are drawn for all ensembles
+    at once (``ScoreBridge.fwd_sampler_batched``) when ``fwd_sampler`` and ``unpack`` are that bridge's own methods too,
+    and by a call per ensemble for any other closure."""
     keys = np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys, np.uint32).reshape(-1, 2)
     B = keys.shape[0]
     masks = kwargs.get("mask_")
@@ -89,21 +91,28 @@ def gibbs_kernel_batched(keys, x0s, y0s, us_stars, bs_stars, ts, fwd_sampler, sd
 
     T = len(ts) - 1
     sk = sweep_key_schedule(keys, T)
-    # preamble, per ensemble: the forward path (gibbs.py:127-130)
-    uss, vss = [], []
-    for b in range(B):
-        path_x, path_y = unpack(fwd_sampler(sk["fwd"][b], x0s[b], y0(b), **kw(b)), **kw(b))
-        uss.append(torch.flip(path_x, [0]))
-        vss.append(torch.flip(bridge_sampler(sk["bridge"][b], path_y[0], path_y[-1], ts, sde), [0]) if marg_y
-                   else torch.flip(path_y, [0]))
-    us_star = torch.stack(uss, 1).contiguous()                                      # (T + 1, B, p, c)
-    vs = torch.stack(vss, 1).contiguous()                                           # (T + 1, B, q, c)
+    mb = sb.em_mask_batch(masks if per_mask else [masks], B)
+    # the bridge's own forward sampler draws the paths of all ensembles at once (ScoreBridge.fwd_sampler_batched)
+    own_fwd = is_own_method(sb, fwd_sampler, "fwd_sampler") and is_own_method(sb, unpack, "unpack")
+    if own_fwd:                                                                     # preamble (gibbs.py:127-130)
+        us_star, vs = sb.fwd_sampler_batched(sk["fwd"], x0s, y0s, mb)               # (T + 1, B, p, c), (T + 1, B, q, c)
+        if marg_y:
+            vs = torch.stack([torch.flip(bridge_sampler(sk["bridge"][b], vs[T, b], vs[0, b], ts, sde), [0])
+                              for b in range(B)], 1).contiguous()
+    else:                                                                           # the same, per ensemble
+        uss, vss = [], []
+        for b in range(B):
+            path_x, path_y = unpack(fwd_sampler(sk["fwd"][b], x0s[b], y0(b), **kw(b)), **kw(b))
+            uss.append(torch.flip(path_x, [0]))
+            vss.append(torch.flip(bridge_sampler(sk["bridge"][b], path_y[0], path_y[-1], ts, sde), [0]) if marg_y
+                       else torch.flip(path_y, [0]))
+        us_star = torch.stack(uss, 1).contiguous()                                  # (T + 1, B, p, c)
+        vs = torch.stack(vss, 1).contiguous()                                       # (T + 1, B, q, c)
     dev = us_star.device
     bs_np = np.stack([_host_int(bs_stars[b]).reshape(-1) for b in range(B)], 0).astype(np.int32)   # (B, T + 1)
     bs_dev = torch.from_numpy(np.ascontiguousarray(bs_np.T)).to(dev)                # (T + 1, B)
     k_res = ops.keys_to_device(sk["resampling"], dev)                               # the whole sweep's keys, uploaded once
     k_tr = ops.keys_to_device(sk["transition"], dev)
-    mb = sb.em_mask_batch(masks if per_mask else [masks], B)
     unobs = tuple(us_star.shape[2:])
 
     # initial particles and weights (gibbs.py:132-144, csmc.py:151-155)
@@ -123,15 +132,21 @@ def gibbs_kernel_batched(keys, x0s, y0s, us_stars, bs_stars, ts, fwd_sampler, sd
         us, lw = sb.fused_step_batched(us, A, vs[k + 1], vs[k], ts[k], k_tr[k], mb, pins=(bs_dev[k + 1], us_star[k + 1]))
         w = ops.normalise_batched(lw)
 
-    # postamble, per ensemble: forced move, fresh reference path and indices (gibbs.py:152-156, 167-168)
+    # postamble: forced move per ensemble, fresh reference paths and indices (gibbs.py:152-156, 167-168)
     x0n, usn, bsn, acc = [], [], [], []
     for b in range(B):
         idx, _ = force_move(sk["x0"][b], w[b], int(bs_np[b, -1]))
         x0 = us[b][idx.long()]
-        us_next = torch.flip(unpack(fwd_sampler(sk["us"][b], x0, y0(b), **kw(b)), **kw(b))[0], [0])
+        if own_fwd:
+            x0n.append(x0)                                                          # the paths follow, all at once
+        else:
+            us_next = torch.flip(unpack(fwd_sampler(sk["us"][b], x0, y0(b), **kw(b)), **kw(b))[0], [0])
+            x0n.append(us_next[-1])
+            usn.append(us_next)
         bs_next = ops.randint(sk["bs"][b], (T + 1,), 0, nparticles, device=dev)
-        x0n.append(us_next[-1])
-        usn.append(us_next)
         bsn.append(bs_next)
         acc.append(bs_next != bs_dev[:, b])
+    if own_fwd:
+        us_next = sb.fwd_sampler_batched(sk["us"], torch.stack(x0n, 0), y0s, mb, want_vs=False, batch_major=True)[0]
+        return us_next[:, -1].contiguous(), us_next, torch.stack(bsn, 0), torch.stack(acc, 0)
     return torch.stack(x0n, 0), torch.stack(usn, 0), torch.stack(bsn, 0), torch.stack(acc, 0)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..score import bridge_of
+from ..score import bridge_of, is_own_method
 from . import resampling as _resampling
 from .common import MCMCState
 from .gibbs import bridge_sampler, gibbs_init
@@ -207,9 +207,11 @@ def pmcmc_kernel_batched(keys, uTs, log_ells, yss, y0s, ts, fwd_ys_sampler, sde,
                          likelihood_logpdf, resampling, nparticles, delta: float = None, which_u: int = 0, **kwargs):
     """``pmcmc_kernel`` for B ensembles: keys (B, 2), uTs (B, p, c), log_ells (B,), yss (B, T + 1, q, c), y0s one
     observation (q, c) or B of them.  Returns (uTs, log_ells, yss, MCMCState of (B,) tensors), the stacked results of the
-    loop over the ensembles under the contract and the lockstep conditions of ``bootstrap_filter_batched``.  The
-    proposal and ``ref_sampler`` run per ensemble; the filter advances in lockstep and the accept step is taken on the
-    device for all ensembles at once, without reading anything back."""
+    loop over the ensembles under the contract and the lockstep conditions of ``bootstrap_filter_batched``.
+    ``ref_sampler`` runs per ensemble, and so does the proposal unless ``fwd_ys_sampler`` is the bridge's own method: then
+    the observation paths of all ensembles (both draws of a pCN proposal: 2 B paths) are one launch
+    (``ScoreBridge.fwd_ys_sampler_batched``).  The filter advances in lockstep and the accept step is taken on the device
+    for all ensembles at once, without reading anything back."""
     keys = _host_keys(keys)
     B = keys.shape[0]
     y0 = _per_ensemble(y0s, B, yss.dim() - 2)
@@ -230,9 +232,23 @@ def pmcmc_kernel_batched(keys, uTs, log_ells, yss, y0s, ts, fwd_ys_sampler, sde,
         ts_np = np.asarray(ts.detach().cpu() if isinstance(ts, torch.Tensor) else ts, np.float64).reshape(-1)
         coef = torch.as_tensor(np.asarray(sde.mean(ts_np, ts_np[0], 1.0), np.float32), device=dev)
     props, u0s, zs = [], [], []
+    own_fwd = is_own_method(sb, fwd_ys_sampler, "fwd_ys_sampler")
+    if own_fwd and delta is None:                                                   # all proposals in one launch (:297-298)
+        prop_yss = sb.fwd_ys_sampler_batched(sk["prop"], y0s)
+    elif own_fwd:                                                                   # pcn_proposal (:282-288), stacked: both
+        key_rnds = np.stack([ops.split(sk["prop"][b], 2) for b in range(B)], 1)     # draws of all ensembles in one launch
+        y0_t = sb._rows(y0s, B, int(np.prod(yss.shape[2:])), "y0s").reshape((B,) + tuple(yss.shape[2:]))
+        rnds = sb.fwd_ys_sampler_batched(key_rnds.reshape(2 * B, 2), torch.cat([y0_t, y0_t], 0))
+        rnds0, rnds1 = rnds[:B], rnds[B:]
+        mean = (coef.reshape((1, -1) + (1,) * (y0_t.dim() - 1)) * y0_t.unsqueeze(1)).reshape(yss.shape)
+        beta = 2 / (2 + delta)
+        p = yss + math.sqrt(delta / 2) * (rnds0 - mean)
+        prop_yss = beta * p + (1 - beta) * mean + math.sqrt(1 - beta) * (rnds1 - mean)
     for b in range(B):                                                              # preamble, per ensemble (:297-307, :314)
         y0_b = y0(b)
-        if delta is None:
+        if own_fwd:
+            prop_ys = prop_yss[b]
+        elif delta is None:
             prop_ys = fwd_ys_sampler(sk["prop"][b], y0_b)
         else:
             y0_t = y0_b if isinstance(y0_b, torch.Tensor) else torch.as_tensor(np.asarray(y0_b, np.float32), device=dev)
@@ -241,7 +257,8 @@ def pmcmc_kernel_batched(keys, uTs, log_ells, yss, y0s, ts, fwd_ys_sampler, sde,
         props.append(prop_ys)
         u0s.append(ref_sampler(sk["u0"][b], torch.flip(prop_ys, [0])[0], nparticles))
         zs.append(ops.uniform(sk["mh"][b], (), device=dev))
-    prop_yss = torch.stack(props, 0)
+    if not own_fwd:
+        prop_yss = torch.stack(props, 0)
     prop_uTs, prop_log_ell = _pmcmc_lockstep(sb, rname, mb, torch.stack(u0s, 0), torch.flip(prop_yss, [1]), ts,
                                              sk["proposal"], sk["resampling"], nparticles)
     prop_uT = prop_uTs[:, which_u]
@@ -260,8 +277,10 @@ def gibbs_init_batched(keys, y0s, x0_shape, ts, fwd_sampler, sde, unpack, transi
     """``gibbs_init`` for B ensembles: keys (B, 2), y0s one observation or B of them, x0s None or (B, p, c), ``mask_`` one
     mask or a list of B.  Returns (approx_x0 (B, ...), approx_us_star (B, T + 1, p, c) or None for 'debug'), the stacked
     results of the loop over the ensembles under the contract and the lockstep conditions of
-    ``bootstrap_filter_batched``.  With 'filter' and 'smoother' the bootstrap filters advance in lockstep; the forward
-    paths, and the backward smoother, run per ensemble.  'debug' and 'kalman' run the loop."""
+    ``bootstrap_filter_batched``.  With 'filter' and 'smoother' the bootstrap filters advance in lockstep, and so do the
+    forward paths when ``fwd_sampler`` and ``unpack`` are the bridge's own methods (``ScoreBridge.fwd_sampler_batched``;
+    any other closure is called per ensemble); the backward smoother runs per ensemble.  'debug' and 'kalman' run the
+    loop."""
     keys = _host_keys(keys)
     B = keys.shape[0]
     y0 = _per_ensemble(y0s, B, len(tuple(x0_shape)))
@@ -279,16 +298,30 @@ def gibbs_init_batched(keys, y0s, x0_shape, ts, fwd_sampler, sde, unpack, transi
     dev = y00.device if isinstance(y00, torch.Tensor) else ops._default_device()
     ks = [ops.split(keys[b], 6) for b in range(B)]                                  # gibbs.py:40: fwd, bridge, u0, bf, fwd2, bwd
     vss, u0s = [], []
+    # the bridge's own forward sampler draws the paths of all ensembles at once (ScoreBridge.fwd_sampler_batched)
+    own_fwd = is_own_method(sb, fwd_sampler, "fwd_sampler") and is_own_method(sb, unpack, "unpack")
+    if own_fwd:
+        x0_all = torch.zeros((B,) + tuple(x0_shape), dtype=torch.float32, device=dev) if x0s is None else x0s
+        _, vs_all = sb.fwd_sampler_batched(np.stack([ks[b][0] for b in range(B)], 0), x0_all, y0s, mb, batch_major=True)
     for b in range(B):                                                              # preamble, per ensemble (gibbs.py:38-47)
-        x0 = torch.zeros(tuple(x0_shape), dtype=torch.float32, device=dev) if x0s is None else x0s[b]
-        _, path_y = unpack(fwd_sampler(ks[b][0], x0, y0(b), **kw(b)), **kw(b))
-        vss.append(torch.flip(bridge_sampler(ks[b][1], path_y[0], path_y[-1], ts, sde), [0]) if marg_y
-                   else torch.flip(path_y, [0]))
+        if own_fwd:
+            path_y = None if not marg_y else (vs_all[b, -1], vs_all[b, 0])         # its two ends, in forward order
+        else:
+            x0 = torch.zeros(tuple(x0_shape), dtype=torch.float32, device=dev) if x0s is None else x0s[b]
+            _, path_y = unpack(fwd_sampler(ks[b][0], x0, y0(b), **kw(b)), **kw(b))
+        if marg_y:
+            vss.append(torch.flip(bridge_sampler(ks[b][1], path_y[0], path_y[-1], ts, sde), [0]))
+        elif not own_fwd:
+            vss.append(torch.flip(path_y, [0]))
         u0s.append(ops.normal(ks[b][2], (nparticles,) + tuple(x0_shape), device=dev))
-    vss = torch.stack(vss, 0)
+    vss = vs_all if own_fwd and not marg_y else torch.stack(vss, 0)
     sk = filter_key_schedule(np.stack([ks[b][3] for b in range(B)], 0), vss.shape[1] - 1)
     uss, _ = _filter_lockstep(sb, rname, mb, torch.stack(u0s, 0), vss, ts, sk["proposal"], sk["resampling"], nparticles,
                               method == "filter")
+    if own_fwd and method == "filter":                                              # postamble (gibbs.py:49-52), at once
+        approx_x0 = uss[:, 0].contiguous()
+        return approx_x0, sb.fwd_sampler_batched(np.stack([ks[b][4] for b in range(B)], 0), approx_x0, y0s, mb,
+                                                 want_vs=False, batch_major=True)[0]
     x0n, usn = [], []
     for b in range(B):                                                              # postamble, per ensemble (gibbs.py:49-57)
         if method == "filter":

@@ -75,18 +75,21 @@ class EMMaskBatch:
 
 class ScoreBridge:
     def __init__(self, score_fn, dataset, sde, ts, chunk: int = 1024, mode: str = "score",
-                 net_input_dtype=torch.float32, fwd_drift_fn=None):
+                 net_input_dtype=torch.float32, fwd_drift_fn=None, fwd_drift_rows_fn=None):
         """score_fn(x (B, w, h, c), t float) -> (B, w, h, c), float32 or bfloat16.
 
         mode 'score': score_fn is the trained score at forward time t and the reverse drift is
         -sde.drift + dispersion^2 * score (inpainting.py:102-103); mode 'drift': score_fn is the learned
         backward drift itself (sb_imgs/supr.py:84-85) and ``fwd_drift_fn(x, t)`` the learned forward drift
         that ``fwd_sampler`` integrates (supr.py:132-137).  net_input_dtype: dtype the network input is
-        written in (torch.bfloat16 saves the cast pass of an autocast network)."""
+        written in (torch.bfloat16 saves the cast pass of an autocast network).
+        ``fwd_drift_rows_fn(x (rows, w, h, c) float32, t) -> (rows, w, h, c)``, float32 or bfloat16: the same forward drift
+        on a batch of images, one per row; with it ``fwd_sampler_batched`` integrates the paths of B ensembles in
+        lockstep."""
         if mode not in ("score", "drift"):
             raise ValueError(f"unknown mode {mode}")
         self.score_fn, self.dataset, self.sde = score_fn, dataset, sde
-        self.mode, self.fwd_drift_fn = mode, fwd_drift_fn
+        self.mode, self.fwd_drift_fn, self.fwd_drift_rows_fn = mode, fwd_drift_fn, fwd_drift_rows_fn
         self.ts = np.asarray(ts, np.float64)
         self.T = float(self.ts[-1])
         self.nsteps = self.ts.size - 1
@@ -372,9 +375,129 @@ class ScoreBridge:
         from .sdes import make_linear_sde
         return make_linear_sde(self.sde)[2](key_, y0_, self.ts)
 
+    # -- the forward paths of B ensembles in lockstep --------------------------------------------------
+    def _fwd_tables(self, device):
+        """(F, S) of ``simulate_cond_forward(keep_path=True)`` on this bridge's grid (sdes/linear.py:176-178) as float32
+        device tables, uploaded once per device."""
+        tab = self._buf.get(("fwd_tables", device))
+        if tab is None:
+            from .sdes.linear import discretise_linear_sde_np
+            F, Q = discretise_linear_sde_np(self.sde, self.ts[1:], self.ts[:-1])
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
+            tab = self._buf[("fwd_tables", device)] = (up(F), up(np.sqrt(Q)))
+        return tab
+
+    @staticmethod
+    def _path_out(B: int, slots: int, d: int, tail, batch_major: bool, device):
+        """An empty path tensor, (slots, B, *tail) or (B, slots, *tail), with its (slot, ensemble) strides in floats."""
+        if batch_major:
+            return torch.empty((B, slots) + tuple(tail), dtype=torch.float32, device=device), d, slots * d
+        return torch.empty((slots, B) + tuple(tail), dtype=torch.float32, device=device), B * d, d
+
+    def _rows(self, x, B: int, d: int, name: str):
+        """One item or B of them (a tensor or a list) -> (B, d) float32, contiguous, on the device."""
+        if isinstance(x, (list, tuple)):
+            x = torch.stack([torch.as_tensor(v, device=self.dataset.device) for v in x], 0)
+        elif not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x, np.float32), device=self.dataset.device)
+        x = ops._f32c(x, name)
+        if x.numel() == d:
+            x = x.reshape(1, d).expand(B, d).contiguous()
+        if x.numel() != B * d:
+            raise ValueError(f"{name} holds {x.numel()} floats, neither one item of {d} nor {B} of them")
+        return x.reshape(B, d)
+
+    @torch.no_grad()
+    def fwd_sampler_batched(self, keys, x0s, y0s, masks, want_vs: bool = True, batch_major: bool = False):
+        """``fwd_sampler`` for B ensembles, unpacked and reversed in time: keys (B, 2), x0s (B, p, c), y0s one observation
+        (q, c) or B of them, masks one mask or a list of B masks of one shape (or an EMMaskBatch).  Returns (us, vs) with
+
+            us[:, b], vs[:, b] = (flip(part, [0]) for part in unpack(fwd_sampler(keys[b], x0s[b], y0s[b], masks[b]), masks[b]))
+
+        bit for bit -- us (T + 1, B, p, c), vs (T + 1, B, q, c), or (B, T + 1, ...) with batch_major; vs is None without
+        want_vs.  Score mode: one fbsmi_linear_path_batched launch.  Drift mode with ``fwd_drift_rows_fn``: per step,
+        ceil(B / chunk) calls of it on the (B, w, h, c) state and one fbsmi_em_fwd_step_batched launch, nothing read back
+        inside the loop; bit-equal whenever the drift's output row does not depend on which rows share its call.  Drift
+        mode without it: the loop of ``fwd_sampler``."""
+        keys_h = None if isinstance(keys, torch.Tensor) else np.asarray(keys, np.uint32).reshape(-1, 2)
+        B = int(keys.numel() // 2) if keys_h is None else keys_h.shape[0]
+        mb = self.em_mask_batch(masks, B)
+        dev = self.dataset.device
+        c = self.dataset.image_shape[2]
+        T = self.nsteps
+        if self.mode == "drift" and self.fwd_drift_rows_fn is None:
+            if keys_h is None:
+                keys_h = keys.detach().cpu().numpy().view(np.uint32).reshape(-1, 2)
+            y0 = (lambda b: y0s[b]) if (isinstance(y0s, (list, tuple)) or y0s.dim() == 3) else (lambda b: y0s)
+            parts = [self.unpack(self.fwd_sampler(keys_h[b], x0s[b], y0(b), mb.ems[b if mb.nmasks > 1 else 0].mask),
+                                 mb.ems[b if mb.nmasks > 1 else 0].mask) for b in range(B)]
+            us, vs = (torch.flip(torch.stack([p[i] for p in parts], 0), [1]) for i in range(2))
+            if not batch_major:
+                us, vs = us.transpose(0, 1).contiguous(), vs.transpose(0, 1).contiguous()
+            return us, (vs if want_vs else None)
+        x0 = self._rows(x0s, B, mb.du, "x0s")
+        y0 = self._rows(y0s, B, mb.dv, "y0s") if mb.dv else None
+        us, us_slot, us_b = self._path_out(B, T + 1, mb.du, (mb.du // c, c), batch_major, dev)
+        vs, vs_slot, vs_b = self._path_out(B, T + 1, mb.dv, (mb.dv // c, c), batch_major, dev) if want_vs else (None, 0, 0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        if self.mode == "score":
+            F, S = self._fwd_tables(dev)
+            kd = ops.keys_to_device(keys, dev)
+            _lib.call("fbsmi_linear_path_batched", mb.ref, mb.D, F.data_ptr(), S.data_ptr(), x0.data_ptr(), ptr(y0),
+                      kd.data_ptr(), B, T, 1, us.data_ptr(), us_slot, us_b, ptr(vs), vs_slot, vs_b, ops._stream())
+            return us, vs
+        if keys_h is None:
+            keys_h = keys.detach().cpu().numpy().view(np.uint32).reshape(-1, 2)
+        kd = ops.keys_to_device(np.stack([ops.split(keys_h[b], T) for b in range(B)], 1), dev)     # (T, B, 2), uploaded once
+        w, h, _ = self.dataset.image_shape
+        state = torch.empty((B, w, h, c), dtype=torch.float32, device=dev)
+        outs = (us.data_ptr(), us_slot, us_b, ptr(vs), vs_slot, vs_b, ops._stream())
+        _lib.call("fbsmi_em_fwd_step_batched", mb.ref, mb.D, x0.data_ptr(), ptr(y0), None, None, 0, 0.0, 0.0, None, 0, 0, B,
+                  state.data_ptr(), T, *outs)
+        net = None
+        for k in range(T):                                   # euler_maruyama(integration_nsteps=1), sdes/simulators.py:55-74
+            t, t_next = float(self.ts[k]), float(self.ts[k + 1])
+            ddt = abs(t_next - t)
+            for s in range(0, B, self.chunk):
+                f = self.fwd_drift_rows_fn(state[s:s + self.chunk], t)
+                if net is None:
+                    if f.dtype not in _NET_DT:
+                        f = f.float()
+                    net = self._buffer("fwd_net", (B, mb.D), f.dtype, dev)
+                net[s:s + self.chunk] = f.reshape(-1, mb.D)
+            cc = float(np.float32(float(self.sde.dispersion(t)) * float(np.sqrt(ddt))))
+            _lib.call("fbsmi_em_fwd_step_batched", mb.ref, mb.D, None, None, state.data_ptr(), net.data_ptr(),
+                      _NET_DT[net.dtype], float(np.float32(ddt)), cc, kd[k].data_ptr(), mb.D, 0, B, state.data_ptr(),
+                      T - 1 - k, *outs)
+        return us, vs
+
+    @torch.no_grad()
+    def fwd_ys_sampler_batched(self, keys, y0s):
+        """``fwd_ys_sampler`` for B paths in one fbsmi_linear_path_batched launch: keys (B, 2), y0s one observation (q, c) or
+        B of them -> (B, T + 1, q, c) in forward order, row b = fwd_ys_sampler(keys[b], y0s[b]) bit for bit."""
+        kd = ops.keys_to_device(keys, self.dataset.device)
+        B = int(kd.numel() // 2)
+        one = y0s[0] if isinstance(y0s, (list, tuple)) else y0s
+        tail = tuple(one.shape[-2:])
+        d = int(tail[0] * tail[1])
+        y0 = self._rows(y0s, B, d, "y0s")
+        F, S = self._fwd_tables(y0.device)
+        T = self.nsteps
+        out, slot, b_stride = self._path_out(B, T + 1, d, tail, True, y0.device)
+        _lib.call("fbsmi_linear_path_batched", None, d, F.data_ptr(), S.data_ptr(), y0.data_ptr(), None, kd.data_ptr(), B, T,
+                  0, out.data_ptr(), slot, b_stride, None, 0, 0, ops._stream())
+        return out
+
     def ref_sampler(self, key_, _, n, row_slice=None):                                    # :160-161
         shape = (n,) + tuple(self.dataset.unobs_shape)
         return ops.normal(key_, shape, device=self.dataset.device, rows=None if row_slice is None else row_slice[:2])
+
+
+def is_own_method(sb, closure, name: str) -> bool:
+    """Whether `closure` is bridge `sb`'s OWN method `name` (not a subclass override, a wrapper or another bridge's): the
+    test ``bridge_of`` makes, for the closures a caller replaces by the bridge's batched form."""
+    return (isinstance(sb, ScoreBridge) and getattr(closure, "__self__", None) is sb
+            and getattr(closure, "__func__", None) is getattr(ScoreBridge, name))
 
 
 def bridge_of(*closures):

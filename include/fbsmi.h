@@ -819,6 +819,46 @@ int fbsmi_normal_batched(const uint32_t* keys, int64_t B, int64_t n, float* out,
  * tree in LDS, no workspace.  keys (B, 2), w (B, n): device arrays.  Refusals as fbsmi_normalise_batched. */
 int fbsmi_categorical_batched(const uint32_t* keys, const float* w, int64_t B, int64_t n, int32_t* out, void* stream);
 
+/* ---- the forward noising paths of B ensembles in lockstep (ScoreBridge.fwd_sampler_batched / fwd_ys_sampler_batched) ----
+ * The state of ensemble b is an image of D = du + dv floats in image order; its path is written ALREADY UNPACKED.  With
+ * o = role[e] of image position e:  o >= 0 is element o of the u output, o < 0 element ~o of the v output, each addressed
+ * as base + slot * slot_stride + b * b_stride + element (strides in floats, chosen by the caller: (T + 1, B, du) and
+ * (B, T + 1, du) are both one launch, and no concat, unpack, flip or stack follows).  out_v may be NULL: the observed
+ * half is then not written.  mask may be NULL: the identity layout, every position goes to the u output, du = D, y0s is
+ * not read.  With a mask, D must equal du + dv; only its role table is read, and its entries are clamped into their part
+ * before they address memory.  x0s (B, du), y0s (B, dv), keys (B, 2): device arrays.
+ *
+ * Decided on the host before any HIP call, FBSMI_ERR_ARG: a mask without its role table, with du < 1 or dv < 0; D outside
+ * [1, 2^31 - 1] or not du + dv; B outside [1, 2^31 - 1]; nmasks outside {1, B}; a null array the call reads or writes; a
+ * dtype flag outside {0, 1}; a draw longer than 2^32 - 4; more workgroups (min(ceil(D / block), 64) per ensemble) than one
+ * grid holds.
+ *
+ * linear_path: B whole paths in one launch.  Point 0 of ensemble b is the image assembled from x0s[b] and y0s[b] through
+ * role; then x <- F[k] * x + S[k] * xi for k < T (the product F[k] * x, the product S[k] * xi and their sum each rounded
+ * separately), xi = element k * D + e of normal(keys[b], (T * D,)) drawn in the kernel: fbsmi_linear_path on
+ * normal(keys[b], (T, D)) bit for bit.  Point k lands in slot T - k when `reverse` is set, else in slot k.  F, S (T):
+ * float32 device tables shared by the ensembles.  64-thread workgroups; a thread owns one (b, e) and walks the T steps.
+ * Also refused: T < 0, null F or S with T > 0, T * D > 2^32 - 4. */
+int fbsmi_linear_path_batched(const fbsmi_em_mask_batch* mask, int64_t D, const float* F, const float* S, const float* x0s,
+                              const float* y0s, const uint32_t* keys, int64_t B, int32_t T, int reverse, float* out_u,
+                              int64_t u_slot_stride, int64_t u_b_stride, float* out_v, int64_t v_slot_stride,
+                              int64_t v_b_stride, void* stream);
+/* em_fwd_step: one Euler-Maruyama sub-step of B image-shaped paths in one launch; x, x_out (B, D) float32 in image order
+ * (x_out may be x; as (B, w, h, c) it is itself the next network input).
+ *   net == NULL (the first launch): x_out[b] = the image assembled from x0s[b] and y0s[b] through role; x and keys are not
+ *       read.
+ *   otherwise:  m = x + f * ddt,  nz = c * xi,  out = m + nz  -- every operation rounded separately -- with f = net[b][e]
+ *       (float32, or bfloat16 widened; net_dtype 0 / 1) and xi = element noise_offset + e of
+ *       normal(keys[b], (noise_total,)): fbsmi_em_update bit for bit, per ensemble.  x0s, y0s are not read.
+ * When store_slot >= 0 the result also goes to slot store_slot of the path outputs (out_u is then required).
+ * Also refused: null x_out; net without x or keys; net == NULL without x0s (y0s when dv > 0); noise_offset < 0 or
+ * noise_offset + D > noise_total; noise_total > 2^32 - 4. */
+int fbsmi_em_fwd_step_batched(const fbsmi_em_mask_batch* mask, int64_t D, const float* x0s, const float* y0s, const float* x,
+                              const void* net, int net_dtype, float ddt, float c, const uint32_t* keys, int64_t noise_total,
+                              int64_t noise_offset, int64_t B, float* x_out, int64_t store_slot, float* out_u,
+                              int64_t u_slot_stride, int64_t u_b_stride, float* out_v, int64_t v_slot_stride,
+                              int64_t v_b_stride, void* stream);
+
 /* ---- the step of the image twisted SMC for B ensembles in lockstep (fbs_amd/twisted.py make_image_twisted_batched;
  * experiments/imgs/inpainting_twisted.py:97-154; score mode only) ----
  * Particles are whole images: X (B * n, D) float32 in image order, D = du + dv = w * h * c, row b * n + r = particle r of
