@@ -12,6 +12,10 @@
 //   fbsmi_categorical_batched   row b = fbsmi_categorical(keys[b], w[b])
 //   fbsmi_linear_path_batched   ensemble b = fbsmi_linear_path on normal(keys[b], (T, D)), written unpacked and in either order
 //   fbsmi_em_fwd_step_batched   ensemble b = fbsmi_em_update on its own image, the path point written unpacked
+//   fbsmi_force_move_batched    entry b = fbsmi_force_move(keys[b], w[b], k[b])
+//   fbsmi_randint_batched       row b = fbsmi_randint(keys[b], n, lo, hi)
+//   fbsmi_backscan_batched      ensemble b = backward_scanning_pass: normalise, categorical, back-trace, row gather
+//   fbsmi_affine_em_path_batched  ensemble b = fbsmi_affine_em_path on its own keys, target and start, in either order
 //
 // each bit for bit, and the step of the image twisted SMC (whole-image particles; fbs_amd/twisted.py
 // make_image_twisted_batched), which has no single-ensemble kernel to equal: its arithmetic is specified in include/fbsmi.h
@@ -79,12 +83,10 @@ __device__ __forceinline__ float lds_scan_at(const float* a, int np, int e) {
 // ------------------------------------------------------------------------------------------------
 // normalise: blockDim.x = np = next_pow2(n) (at least 64), thread e owns element e
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kMaxRows) k_normalise_b(const float* __restrict__ lw, int n, int np, int log_space,
-                                                          float* __restrict__ out, float* __restrict__ out_lse) {
-    __shared__ float tr[kMaxRows];
-    __shared__ float smax[kMaxRows / 64];
-    const int b = blockIdx.x, e = threadIdx.x;
-    const float l = e < n ? lw[(int64_t)b * n + e] : -__builtin_inff();
+// the logsumexp of one row, l = this thread's element (-inf beyond n); tr (np floats) and smax (np / 64) are scratch.
+// Every thread of the workgroup calls it and gets the same value; tr and smax may be reused after the next barrier.
+__device__ __forceinline__ float lds_row_lse(float l, int n, int np, float* tr, float* smax) {
+    const int e = threadIdx.x;
     const float mw = wave_max(l);
     if ((e & 63) == 0) smax[e >> 6] = mw;
     __syncthreads();
@@ -112,7 +114,16 @@ __global__ void __launch_bounds__(kMaxRows) k_normalise_b(const float* __restric
         a[q] = q < nb ? tr[(q < ntile ? q : 0) * tile + tile - 1] * fbsmi_expf(finite_or_zero(mt[q]) - Mp) : 0.0f;
     const float s01 = a[0] + a[1], s23 = a[2] + a[3];
     const float tot = s01 + s23;
-    const float lse = fbsmi_logf(tot) + Mp;
+    return fbsmi_logf(tot) + Mp;
+}
+
+__global__ void __launch_bounds__(kMaxRows) k_normalise_b(const float* __restrict__ lw, int n, int np, int log_space,
+                                                          float* __restrict__ out, float* __restrict__ out_lse) {
+    __shared__ float tr[kMaxRows];
+    __shared__ float smax[kMaxRows / 64];
+    const int b = blockIdx.x, e = threadIdx.x;
+    const float l = e < n ? lw[(int64_t)b * n + e] : -__builtin_inff();
+    const float lse = lds_row_lse(l, n, np, tr, smax);
     if (e == 0 && out_lse) out_lse[b] = lse;
     if (e < n) {
         const float v = l - lse;
@@ -628,6 +639,142 @@ __global__ void __launch_bounds__(kMaxRows) k_categorical_b(const uint32_t* __re
     }
 }
 
+// entry b of out_i (B) = fbsmi_force_move(keys[b], w[b], k[b]) (gibbs.py:171-214): the rest weights (V_FMREST of
+// fbsmi_prims.hip) scanned in LDS, both sub-keys split here, the tail of k_force_move_finish by the first thread; with
+// out_alpha the tree sum of the V_FMALPHA values clipped to [0, 1].  k is clamped into [0, n) before it addresses memory,
+// and so is the drawn index (which leaves [0, n) only on weights that are not numbers).
+__global__ void __launch_bounds__(kMaxRows) k_force_move_b(const uint32_t* __restrict__ keys, const float* __restrict__ w,
+                                                           const int32_t* __restrict__ kref, int n, int np,
+                                                           int32_t* __restrict__ out_i, float* __restrict__ out_alpha) {
+    __shared__ float sw[kMaxRows], tr[kMaxRows], cdf[kMaxRows];
+    const int b = blockIdx.x, e = threadIdx.x;
+    const int k = clamp_index(kref[b], n - 1);
+    const float we = e < n ? w[(int64_t)b * n + e] : 0.0f;
+    sw[e] = we;
+    __syncthreads();
+    const float w_k = sw[k];
+    const float temp = 1.0f - w_k;
+    float rest = 0.0f;
+    if (e < n) {
+        if (w_k < 1.0f) rest = (e == k ? 0.0f : we) / temp;
+        else rest = (float)(1.0 / (double)n);
+    }
+    tr[e] = rest;
+    lds_upsweep(tr, np, np);
+    cdf[e] = lds_scan_at(tr, np, e);
+    __syncthreads();
+    if (e == 0) {
+        const uint32_t k0 = keys[2 * b], k1 = keys[2 * b + 1];
+        uint32_t a0, a1, b0, b1;
+        split_at(k0, k1, 2, 0, a0, a1);
+        split_at(k0, k1, 2, 1, b0, b1);
+        const float u1 = uniform_at(a0, a1, 1, 0);
+        const int32_t i = clamp_index(searchsorted_left(cdf, n, bisect_levels(n), cdf[n - 1] * (1.0f - u1)), n - 1);
+        const float u = uniform_at(b0, b1, 1, 0);
+        const bool accept = u * (1.0f - sw[i]) < temp;
+        out_i[b] = accept ? i : k;
+    }
+    if (out_alpha) {   // uniform over the workgroup
+        float al = 0.0f;
+        if (e < n) {
+            al = temp * rest / (1.0f - we);
+            al = (al != al) ? 0.0f : al;
+        }
+        tr[e] = al;   // every read of tr above is behind the barrier that follows the scan
+        lds_upsweep(tr, np, np);
+        if (e == 0) {
+            const float root = tr[np - 1];
+            out_alpha[b] = root < 0.0f ? 0.0f : (root > 1.0f ? 1.0f : root);
+        }
+    }
+}
+
+// row b of out (B, n) = fbsmi_randint(keys[b], n, lo, hi): k_randint of fbsmi_prims.hip with the key read per row.
+// `bpr` workgroups per row.
+__global__ void __launch_bounds__(kBlock) k_randint_b(const uint32_t* __restrict__ keys, uint64_t n, int bpr, int32_t lo,
+                                                      int32_t hi, int32_t* __restrict__ out) {
+    const int64_t b = blockIdx.x / bpr;
+    const int q = (int)(blockIdx.x - b * bpr);
+    const uint32_t k0 = keys[2 * b], k1 = keys[2 * b + 1];
+    int32_t* __restrict__ o = out + b * (int64_t)n;
+    for (uint64_t i = (uint64_t)q * kBlock + threadIdx.x; i < n; i += (uint64_t)bpr * kBlock)
+        o[i] = randint_at(k0, k1, n, i, lo, hi);
+}
+
+// ensemble b = backward_scanning_pass (csmc/csmc.py:105-112) on its own arrays: normalise(log_w_T[b], log_space=False)
+// with the arithmetic of k_normalise_b, the draw of k_categorical_b, then the first thread walks the trace
+// Bs[k - 1] = As[k - 1][b][Bs[k]] and parks it in Bs; after a barrier all threads copy the rows path[b][k] = uss[k][b][Bs[k]].
+// As (T, B, n) and uss (T + 1, B, n, du) are time-major, Bs (B, T + 1) and path (B, T + 1, du) batch-major.  Ancestors are
+// clamped into [0, n) before they address memory.
+__global__ void __launch_bounds__(kMaxRows) k_backscan_b(const uint32_t* __restrict__ keys, const float* __restrict__ lwT,
+                                                         const int32_t* __restrict__ As, const float* __restrict__ uss,
+                                                         int64_t B, int n, int np, int T, int64_t du, int32_t* Bs,
+                                                         float* __restrict__ path) {
+    __shared__ float tr[kMaxRows], cdf[kMaxRows];
+    __shared__ float smax[kMaxRows / 64];
+    const int64_t b = blockIdx.x;
+    const int e = threadIdx.x;
+    const float l = e < n ? lwT[b * n + e] : -__builtin_inff();
+    const float lse = lds_row_lse(l, n, np, tr, smax);
+    __syncthreads();   // the row's tree in tr has been read by everyone
+    tr[e] = e < n ? fbsmi_expf(l - lse) : 0.0f;
+    lds_upsweep(tr, np, np);
+    cdf[e] = lds_scan_at(tr, np, e);
+    __syncthreads();
+    int32_t* bs = Bs + b * ((int64_t)T + 1);
+    if (e == 0) {
+        const float u = uniform_at(keys[2 * b], keys[2 * b + 1], 1, 0);
+        int32_t a = clamp_index(searchsorted_left(cdf, n, bisect_levels(n), cdf[n - 1] * (1.0f - u)), n - 1);
+        bs[T] = a;
+        for (int k = T; k >= 1; --k) {
+            a = clamp_index(As[((int64_t)(k - 1) * B + b) * n + a], n - 1);
+            bs[k - 1] = a;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    const int64_t total = ((int64_t)T + 1) * du;
+    float* __restrict__ p = path + b * total;
+    for (int64_t i = e; i < total; i += blockDim.x) {
+        const int64_t k = i / du, c = i - k * du;
+        p[i] = uss[((k * B + b) * n + bs[k]) * du + c];
+    }
+}
+
+// ensemble b = k_affine_em_path (fbsmi_sde.hip) on its own keys (T, 2), target and start: the same expression under the
+// same contraction setting.  Point k lands at out + (reverse ? T - k : k) * slot_stride + b * ens_stride.  `bpr`
+// workgroups of 64 threads per ensemble stride over the coordinates.
+__global__ void __launch_bounds__(64) k_affine_em_path_b(const uint32_t* __restrict__ keys, const float* __restrict__ A,
+                                                         const float* __restrict__ Bt, const float* __restrict__ S,
+                                                         const float* __restrict__ ddt, const float* __restrict__ target,
+                                                         const float* __restrict__ x0, int T, int nsub, int64_t D,
+                                                         int replace_last, int bpr, float* __restrict__ out,
+                                                         int64_t slot_stride, int64_t ens_stride, int reverse) {
+    const int64_t b = blockIdx.x / bpr;
+    const int q = (int)(blockIdx.x - b * bpr);
+    const uint64_t n = (uint64_t)nsub * (uint64_t)D;
+    const uint32_t* __restrict__ kb = keys + b * 2 * (int64_t)T;
+    float* __restrict__ o = out + b * ens_stride;
+    for (int64_t c = (int64_t)q * 64 + threadIdx.x; c < D; c += (int64_t)bpr * 64) {
+        float x = x0[b * D + c];
+        const float tg = target[b * D + c];
+        o[(reverse ? (int64_t)T : 0) * slot_stride + c] = x;
+        for (int k = 0; k < T; ++k) {
+            const uint32_t k0 = kb[2 * k], k1 = kb[2 * k + 1];
+            const float h = ddt[k];
+            const float sq = fbsmi_sqrtf(h);
+            for (int j = 0; j < nsub; ++j) {
+                const int r = k * nsub + j;
+                const float xi = normal_at(k0, k1, n, (uint64_t)j * D + c);
+                const float drift = A[r] * x + Bt[r] * tg;
+                x = (x + drift * h) + (S[r] * sq) * xi;
+            }
+            o[(int64_t)(reverse ? T - 1 - k : k + 1) * slot_stride + c] = x;
+        }
+        if (replace_last) o[(reverse ? 0 : (int64_t)T) * slot_stride + c] = tg;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // forward noising paths of B ensembles (ScoreBridge.fwd_sampler_batched / fwd_ys_sampler_batched): the state is an image
 // (B, D) in image order, its path is written ALREADY UNPACKED -- image position e with o = role[e] >= 0 is element o of the
@@ -1080,6 +1227,60 @@ int fbsmi_em_fwd_step_batched(const fbsmi_em_mask_batch* mask, int64_t D, const 
     const uint64_t nt = (uint64_t)noise_total, no = (uint64_t)noise_offset;
     if (net_dtype == 0) k_em_fwd_step_b<0><<<grid, kBlock, 0, st>>>(a, x, net, ddt, c, nt, no, x_out, store_slot);
     else k_em_fwd_step_b<1><<<grid, kBlock, 0, st>>>(a, x, net, ddt, c, nt, no, x_out, store_slot);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_force_move_batched(const uint32_t* keys, const float* w, const int32_t* k, int64_t B, int64_t n, int32_t* out_i,
+                             float* out_alpha, void* stream) {
+    FBSMI_NEED(keys && w && k && out_i, "force_move_batched: null pointer");
+    FBSMI_NEED(B >= 1 && n >= 1 && B <= kMaxGrid, "force_move_batched: B and n must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "force_move_batched: more than 1024 rows per ensemble");
+    const int np = threads_for(n);
+    k_force_move_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(keys, w, k, (int)n, np, out_i, out_alpha);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_randint_batched(const uint32_t* keys, int64_t B, int64_t n, int32_t lo, int32_t hi, int32_t* out, void* stream) {
+    FBSMI_NEED(B >= 1 && n >= 0, "randint_batched: B must be at least 1 and n at least 0");
+    FBSMI_NEED(keys && (n == 0 || out), "randint_batched: null pointer");
+    FBSMI_NEED(n <= kMaxDraw, "randint_batched: a row exceeds 2^32 - 4 elements");
+    if (n == 0) return FBSMI_OK;
+    int64_t bpr = (n + kBlock - 1) / kBlock;   // a thread per element, at most 64 workgroups per row
+    if (bpr > 64) bpr = 64;
+    FBSMI_NEED(B <= kMaxGrid / bpr, "randint_batched: too many rows for one grid");
+    k_randint_b<<<(unsigned)(B * bpr), kBlock, 0, (hipStream_t)stream>>>(keys, (uint64_t)n, (int)bpr, lo, hi, out);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_backscan_batched(const uint32_t* keys, const float* log_w_T, const int32_t* As, const float* uss, int64_t B,
+                           int64_t n, int32_t T, int64_t du, int32_t* Bs, float* path, void* stream) {
+    FBSMI_NEED(keys && log_w_T && uss && Bs && path && T >= 0 && (T == 0 || As), "backscan_batched: null pointer or T < 0");
+    FBSMI_NEED(B >= 1 && n >= 1 && du >= 1 && B <= kMaxGrid, "backscan_batched: B, n and du must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "backscan_batched: more than 1024 rows per ensemble");
+    const int np = threads_for(n);
+    k_backscan_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(keys, log_w_T, As, uss, B, (int)n, np, (int)T, du, Bs, path);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_affine_em_path_batched(const uint32_t* keys, const float* A, const float* Bt, const float* S, const float* ddt,
+                                 const float* target, const float* x0, int32_t T, int32_t nsub, int64_t D, int replace_last,
+                                 int64_t B, float* out, int64_t slot_stride, int64_t ens_stride, int reverse, void* stream) {
+    FBSMI_NEED(target && x0 && out && T >= 0 && nsub >= 1 && D >= 1 && (T == 0 || (keys && A && Bt && S && ddt)),
+               "affine_em_path_batched: null pointer, T < 0, nsub < 1 or D < 1");
+    FBSMI_NEED(B >= 1 && B <= kMaxGrid, "affine_em_path_batched: B must be in [1, 2^31 - 1]");
+    FBSMI_NEED((int64_t)nsub * D <= kMaxDraw && (int64_t)T * nsub <= kMaxGrid,
+               "affine_em_path_batched: an interval's noise draw exceeds 2^32 - 4 elements, or T * nsub exceeds 2^31 - 1");
+    FBSMI_NEED(slot_stride >= 0 && ens_stride >= 0, "affine_em_path_batched: negative stride");
+    int64_t bpr = (D + 63) / 64;   // a thread per coordinate, at most 64 workgroups per ensemble
+    if (bpr > 64) bpr = 64;
+    FBSMI_NEED(B <= kMaxGrid / bpr, "affine_em_path_batched: too many ensembles for one grid");
+    k_affine_em_path_b<<<(unsigned)(B * bpr), 64, 0, (hipStream_t)stream>>>(keys, A, Bt, S, ddt, target, x0, (int)T, (int)nsub, D,
+                                                                            replace_last != 0, (int)bpr, out, slot_stride,
+                                                                            ens_stride, reverse != 0);
     FBSMI_LAUNCH_CHECK();
     return FBSMI_OK;
 }

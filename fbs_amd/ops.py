@@ -238,10 +238,11 @@ def normalise_batched(log_weights: torch.Tensor, log_space: bool = False, return
     return (out, lse) if return_lse else out
 
 
-def cond_killing_batched(keys, weights: torch.Tensor, i: torch.Tensor, j: torch.Tensor) -> torch.Tensor:
+def cond_killing_batched(keys, weights: torch.Tensor, i: torch.Tensor, j: torch.Tensor, out=None) -> torch.Tensor:
     """Conditional killing resampling (csmc/resamplings.py:40-88) of B ensembles in one launch: row b of the result
     (B, n) int32 has the bits of ``killing(keys[b], weights[b], i[b], j[b], True)``.  keys (B, 2) uint32 on the host or
-    their bits as an int32 device tensor; i, j (B,) integer tensors on the device; n <= 1024."""
+    their bits as an int32 device tensor; i, j (B,) integer tensors on the device; n <= 1024.  ``out``: a contiguous
+    (B, n) int32 device tensor to write into (a slot of a stored ancestor array) instead of a fresh one."""
     w = _f32c(weights, "weights")
     if w.dim() != 2:
         raise ValueError("cond_killing_batched wants weights of shape (B, n)")
@@ -250,7 +251,12 @@ def cond_killing_batched(keys, weights: torch.Tensor, i: torch.Tensor, j: torch.
     ii, jj = (torch.as_tensor(x, device=w.device).to(torch.int32).contiguous() for x in (i, j))
     if kd.numel() != 2 * B or ii.numel() != B or jj.numel() != B:
         raise ValueError("cond_killing_batched: keys (B, 2), i (B,) and j (B,) must match weights (B, n)")
-    idx = torch.empty((B, n), dtype=torch.int32, device=w.device)
+    if out is None:
+        idx = torch.empty((B, n), dtype=torch.int32, device=w.device)
+    else:
+        idx = out
+        if idx.dtype != torch.int32 or tuple(idx.shape) != (B, n) or not idx.is_contiguous() or idx.device != w.device:
+            raise ValueError("cond_killing_batched: out must be a contiguous (B, n) int32 tensor on the weights' device")
     _lib.call("fbsmi_cond_killing_batched", kd.data_ptr(), w.data_ptr(), ii.data_ptr(), jj.data_ptr(), B, n,
               idx.data_ptr(), _stream())
     return idx
@@ -292,6 +298,66 @@ def categorical_batched(keys, weights: torch.Tensor) -> torch.Tensor:
     out = torch.empty(B, dtype=torch.int32, device=w.device)
     _lib.call("fbsmi_categorical_batched", kd.data_ptr(), w.data_ptr(), B, n, out.data_ptr(), _stream())
     return out
+
+
+def force_move_batched(keys, weights: torch.Tensor, k, return_alpha: bool = False):
+    """Forced-move selection (gibbs.py:171-214) of B ensembles in one launch: entry b of the (B,) int32 result has the
+    bits of ``force_move(keys[b], weights[b], k[b])``'s index.  keys (B, 2) uint32 on the host or their bits as an int32
+    device tensor; weights (B, n), n <= 1024; k (B,) integers (a device tensor is not read back).  return_alpha adds the
+    (B,) float32 acceptance sums, which are not computed otherwise."""
+    w = _f32c(weights, "weights")
+    if w.dim() != 2:
+        raise ValueError("force_move_batched wants weights of shape (B, n)")
+    B, n = w.shape
+    kd = keys_to_device(keys, w.device)
+    kk = torch.as_tensor(k, device=w.device).to(torch.int32).reshape(-1).contiguous()
+    if kd.numel() != 2 * B or kk.numel() != B:
+        raise ValueError("force_move_batched: keys (B, 2) and k (B,) must match weights (B, n)")
+    out = torch.empty(B, dtype=torch.int32, device=w.device)
+    alpha = torch.empty(B, dtype=torch.float32, device=w.device) if return_alpha else None
+    _lib.call("fbsmi_force_move_batched", kd.data_ptr(), w.data_ptr(), kk.data_ptr(), B, n, out.data_ptr(),
+              alpha.data_ptr() if return_alpha else None, _stream())
+    return (out, alpha) if return_alpha else out
+
+
+def randint_batched(keys, n: int, minval: int, maxval: int, device=None) -> torch.Tensor:
+    """Row b of the (B, n) int32 result has the bits of ``randint(keys[b], (n,), minval, maxval)``, in one launch.  keys
+    (B, 2) uint32 on the host or their bits as an int32 device tensor."""
+    dev = keys.device if isinstance(keys, torch.Tensor) else (device or _default_device())
+    kd = keys_to_device(keys, dev)
+    B, n = kd.numel() // 2, int(n)
+    out = torch.empty((B, n), dtype=torch.int32, device=dev)
+    _lib.call("fbsmi_randint_batched", kd.data_ptr(), B, n, int(minval), int(maxval), out.data_ptr(), _stream())
+    return out
+
+
+def backscan_batched(keys, log_w_T: torch.Tensor, As: torch.Tensor, uss: torch.Tensor):
+    """``backward_scanning_pass`` (csmc/csmc.py) of B ensembles in one launch.  keys (B, 2) uint32 on the host or their bits
+    as an int32 device tensor; log_w_T (B, n), n <= 1024; As (T, B, n) int32 and uss (T + 1, B, n, ...) float32 time-major,
+    as the forward pass stores them.  -> (path (B, T + 1, ...), Bs (B, T + 1) int32); ensemble b has the bits of
+    ``backward_scanning_pass(keys[b], As[:, b], uss[:, b], log_w_T[b])``."""
+    lw = _f32c(log_w_T, "log_w_T")
+    u = _f32c(uss, "uss")
+    if lw.dim() != 2 or u.dim() < 3:
+        raise ValueError("backscan_batched wants log_w_T (B, n) and uss (T + 1, B, n, ...)")
+    B, n = lw.shape
+    T = int(u.shape[0]) - 1
+    if T < 0 or tuple(u.shape[1:3]) != (B, n):
+        raise ValueError("backscan_batched: uss must be (T + 1, B, n, ...) with log_w_T's B and n")
+    tail = tuple(u.shape[3:])
+    du = int(np.prod(tail, dtype=np.int64)) if tail else 1
+    A = As.to(torch.int32).contiguous()
+    _require_cuda(A, "As")
+    if tuple(A.shape) != (T, B, n):
+        raise ValueError("backscan_batched: As must be (T, B, n)")
+    kd = keys_to_device(keys, lw.device)
+    if kd.numel() != 2 * B:
+        raise ValueError("backscan_batched: keys (B, 2) must match log_w_T (B, n)")
+    Bs = torch.empty((B, T + 1), dtype=torch.int32, device=lw.device)
+    path = torch.empty((B, T + 1) + tail, dtype=torch.float32, device=lw.device)
+    _lib.call("fbsmi_backscan_batched", kd.data_ptr(), lw.data_ptr(), A.data_ptr() if T else None, u.data_ptr(), B, n, T, du,
+              Bs.data_ptr(), path.data_ptr(), _stream())
+    return path, Bs
 
 
 def searchsorted(a: torch.Tensor, q: torch.Tensor) -> torch.Tensor:

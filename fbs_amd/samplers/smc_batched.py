@@ -5,7 +5,8 @@ The ensembles share the time grid, the SDE and the network, so every SMC step of
 B * nparticles rows between single launches of the batched sampler kernels (fbs_amd/csrc/fbsmi_batch.hip), instead of B
 calls on `nparticles` rows each among a dozen launches per ensemble.  Every function here is the loop of its
 single-ensemble namesake in ``smc.py`` / ``gibbs.py`` over the ensembles, with the same keys, run that way, and falls back
-to that loop when the lockstep conditions do not hold.
+to that loop when the lockstep conditions do not hold.  ``gibbs_init_batched`` also draws the Doob bridges of ``marg_y``
+(its default) for all ensembles in one launch.
 """
 from __future__ import annotations
 
@@ -14,12 +15,13 @@ import math
 import numpy as np
 import torch
 
-from .. import ops
+from .. import _lib, ops
 from ..score import bridge_of, is_own_method
+from ..sdes.simulators import doob_bridge_simulator_batched
 from . import resampling as _resampling
 from .common import MCMCState
-from .gibbs import bridge_sampler, gibbs_init
-from .gibbs_batched import MAX_LOCKSTEP_ROWS, _is_mask
+from .gibbs import gibbs_init
+from .gibbs_batched import MAX_LOCKSTEP_ROWS, _is_mask, _take
 from .smc import (bootstrap_backward_smoother, bootstrap_filter, pcn_proposal, pmcmc_filter_step, pmcmc_kernel)
 
 
@@ -93,11 +95,6 @@ def _lockstep(transition_sampler, weight_closure, resampling, nparticles, kwargs
 def _host_ts(ts):
     """The grid as host floats, read once: the time loop then never waits for the device."""
     return [float(t) for t in (ts.detach().cpu().numpy() if isinstance(ts, torch.Tensor) else np.asarray(ts)).reshape(-1)]
-
-
-def _take(us, inds):
-    """us[b][inds[b]] for every ensemble."""
-    return us[torch.arange(us.shape[0], device=us.device)[:, None], inds.long()]
 
 
 def _filter_lockstep(sb, rname, mb, us, vss, ts, key_proposal, key_resampling, nparticles, return_last):
@@ -279,8 +276,9 @@ def gibbs_init_batched(keys, y0s, x0_shape, ts, fwd_sampler, sde, unpack, transi
     results of the loop over the ensembles under the contract and the lockstep conditions of
     ``bootstrap_filter_batched``.  With 'filter' and 'smoother' the bootstrap filters advance in lockstep, and so do the
     forward paths when ``fwd_sampler`` and ``unpack`` are the bridge's own methods (``ScoreBridge.fwd_sampler_batched``;
-    any other closure is called per ensemble); the backward smoother runs per ensemble.  'debug' and 'kalman' run the
-    loop."""
+    any other closure is called per ensemble); with marg_y the Doob bridges of all ensembles are one launch
+    (``doob_bridge_simulator_batched``) and the initial particles of all ensembles are one draw; the backward smoother
+    runs per ensemble.  'debug' and 'kalman' run the loop."""
     keys = _host_keys(keys)
     B = keys.shape[0]
     y0 = _per_ensemble(y0s, B, len(tuple(x0_shape)))
@@ -297,26 +295,30 @@ def gibbs_init_batched(keys, y0s, x0_shape, ts, fwd_sampler, sde, unpack, transi
     y00 = y0(0)
     dev = y00.device if isinstance(y00, torch.Tensor) else ops._default_device()
     ks = [ops.split(keys[b], 6) for b in range(B)]                                  # gibbs.py:40: fwd, bridge, u0, bf, fwd2, bwd
-    vss, u0s = [], []
+    key_of = lambda i: np.stack([ks[b][i] for b in range(B)], 0)
     # the bridge's own forward sampler draws the paths of all ensembles at once (ScoreBridge.fwd_sampler_batched)
     own_fwd = is_own_method(sb, fwd_sampler, "fwd_sampler") and is_own_method(sb, unpack, "unpack")
-    if own_fwd:
+    if own_fwd:                                                                     # preamble (gibbs.py:38-47)
         x0_all = torch.zeros((B,) + tuple(x0_shape), dtype=torch.float32, device=dev) if x0s is None else x0s
-        _, vs_all = sb.fwd_sampler_batched(np.stack([ks[b][0] for b in range(B)], 0), x0_all, y0s, mb, batch_major=True)
-    for b in range(B):                                                              # preamble, per ensemble (gibbs.py:38-47)
-        if own_fwd:
-            path_y = None if not marg_y else (vs_all[b, -1], vs_all[b, 0])         # its two ends, in forward order
-        else:
+        _, vss = sb.fwd_sampler_batched(key_of(0), x0_all, y0s, mb, batch_major=True)
+        ends = (vss[:, -1], vss[:, 0])                                              # the paths' two ends, in forward order
+    else:                                                                           # the same, per ensemble
+        path_ys = []
+        for b in range(B):
             x0 = torch.zeros(tuple(x0_shape), dtype=torch.float32, device=dev) if x0s is None else x0s[b]
-            _, path_y = unpack(fwd_sampler(ks[b][0], x0, y0(b), **kw(b)), **kw(b))
+            path_ys.append(unpack(fwd_sampler(ks[b][0], x0, y0(b), **kw(b)), **kw(b))[1])
         if marg_y:
-            vss.append(torch.flip(bridge_sampler(ks[b][1], path_y[0], path_y[-1], ts, sde), [0]))
-        elif not own_fwd:
-            vss.append(torch.flip(path_y, [0]))
-        u0s.append(ops.normal(ks[b][2], (nparticles,) + tuple(x0_shape), device=dev))
-    vss = vs_all if own_fwd and not marg_y else torch.stack(vss, 0)
-    sk = filter_key_schedule(np.stack([ks[b][3] for b in range(B)], 0), vss.shape[1] - 1)
-    uss, _ = _filter_lockstep(sb, rname, mb, torch.stack(u0s, 0), vss, ts, sk["proposal"], sk["resampling"], nparticles,
+            ends = (torch.stack([p[0] for p in path_ys], 0), torch.stack([p[-1] for p in path_ys], 0))
+        else:
+            vss = torch.stack([torch.flip(p, [0]) for p in path_ys], 0)
+    if marg_y:                                                                      # the bridges of all ensembles: one launch
+        vss = doob_bridge_simulator_batched(key_of(1), sde, ends[0], ends[1], ts, integration_nsteps=100, replace=True,
+                                            reverse=True)
+    u0s = torch.empty((B, nparticles) + tuple(x0_shape), dtype=torch.float32, device=dev)
+    _lib.call("fbsmi_normal_batched", ops.keys_to_device(key_of(2), dev).data_ptr(), B, u0s[0].numel(), u0s.data_ptr(),
+              ops._stream())
+    sk = filter_key_schedule(key_of(3), vss.shape[1] - 1)
+    uss, _ = _filter_lockstep(sb, rname, mb, u0s, vss, ts, sk["proposal"], sk["resampling"], nparticles,
                               method == "filter")
     if own_fwd and method == "filter":                                              # postamble (gibbs.py:49-52), at once
         approx_x0 = uss[:, 0].contiguous()

@@ -219,13 +219,14 @@ class ScoreBridge:
         return mb
 
     @torch.no_grad()
-    def fused_step_batched(self, us, A, v, v_prev, t_prev, keys, masks, pins=None, want_us=True):
+    def fused_step_batched(self, us, A, v, v_prev, t_prev, keys, masks, pins=None, want_us=True, out_us=None):
         """``fused_step`` for B ensembles at the same time step: one fbsmi_em_concat_batched launch, the network in
         `chunk`-row pieces over the flat B * n rows (a chunk may straddle ensembles), one fbsmi_em_finish_batched launch.
         us (B, n, p, c); A (B, n) ancestors local to each ensemble, or None; v, v_prev (B, q, c); keys (B, 2) (host uint32,
         or their bits on the device: ensemble b draws normal(keys[b], (n, p, c)) as a call of its own would); masks one
         mask, a list of B masks of one shape, or an EMMaskBatch; pins = (rows (B,) int32 with -1 for none, values
-        (B, p, c)) or None.  want_us=False: weights only (keys and pins are not read).
+        (B, p, c)) or None.  want_us=False: weights only (keys and pins are not read).  out_us: a contiguous float32
+        device tensor of B * n * p * c elements that receives us_new (a slot of a stored particle array; not `us` itself).
         -> (us_new (B, n, p, c) or None, lw (B, n)); ensemble b has the bits of its own ``fused_step`` whenever the
         network's output row does not depend on which rows share its call."""
         us3 = ops._f32c(us, "us")
@@ -253,7 +254,14 @@ class ScoreBridge:
                 net = self._buffer("net", (B * n, mb.D), y.dtype, dev)
             net[s:s + self.chunk] = y.reshape(-1, mb.D)
         mode, cx, cs, sd = self._coef(t_prev)
-        us_new = torch.empty((B, n, mb.du), dtype=torch.float32, device=dev) if want_us else None
+        us_new = None
+        if want_us and out_us is not None:
+            if out_us.dtype != torch.float32 or out_us.device != dev or not out_us.is_contiguous() or \
+                    out_us.numel() != B * n * mb.du:
+                raise ValueError("out_us must be a contiguous float32 tensor of B * n * du elements on the particles' device")
+            us_new = out_us.view(B, n, mb.du)
+        elif want_us:
+            us_new = torch.empty((B, n, mb.du), dtype=torch.float32, device=dev)
         lw = torch.empty((B, n), dtype=torch.float32, device=dev)
         kd = ops.keys_to_device(keys, dev) if want_us else None
         pin_row = pin_val = None

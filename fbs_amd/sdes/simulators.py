@@ -112,3 +112,36 @@ def doob_bridge_simulator(key, sde: LinearSDE, x0, xT, ts, integration_nsteps: i
               xTt.reshape(-1).data_ptr(), x0t.reshape(-1).data_ptr(), T, nsub, D, int(bool(replace)), out.data_ptr(),
               ops._stream())
     return out.reshape((T + 1,) + shape)
+
+
+def doob_bridge_simulator_batched(keys, sde: LinearSDE, x0s, xTs, ts, integration_nsteps: int = 1, replace: bool = False,
+                                  reverse: bool = False, time_major: bool = False):
+    """``doob_bridge_simulator`` for B bridges on one grid in ONE launch (fbsmi_affine_em_path_batched): keys (B, 2), x0s
+    and xTs (B, ...) device tensors.  The tables are built and uploaded once per call, the ``split(key, T)`` of every
+    bridge is done on the host.  -> (B, T + 1, ...), or (T + 1, B, ...) with time_major; bridge b has the bits of
+    ``doob_bridge_simulator(keys[b], sde, x0s[b], xTs[b], ts, integration_nsteps, replace)``, its points in reverse
+    order with ``reverse`` (point k in slot T - k: what ``torch.flip(., [0])`` would give)."""
+    ts_np = _as_np(ts).reshape(-1)
+    T = ts_np.size - 1
+    nsub = int(integration_nsteps)
+    keys = np.asarray(keys.detach().cpu() if isinstance(keys, torch.Tensor) else keys, np.uint32).reshape(-1, 2)
+    B = keys.shape[0]
+    x0t = ops._f32c(x0s if isinstance(x0s, torch.Tensor) else torch.stack(list(x0s), 0), "x0s")
+    xTt = ops._f32c(xTs if isinstance(xTs, torch.Tensor) else torch.stack(list(xTs), 0), "xTs")
+    if x0t.shape[0] != B or xTt.shape != x0t.shape:
+        raise ValueError("doob_bridge_simulator_batched: keys (B, 2), x0s (B, ...) and xTs (B, ...) must match")
+    dev = x0t.device
+    shape = tuple(x0t.shape[1:])
+    D = x0t[0].numel()
+    tab = doob_bridge_tables(sde, ts_np, nsub)
+    step_keys = np.stack([ops.split(keys[b], T) for b in range(B)], 0) if T else np.zeros((B, 0, 2), np.uint32)
+    up = lambda a: torch.from_numpy(a).to(dev)
+    keys_t = ops.keys_to_device(step_keys, dev)
+    At, Bt, St, ht = up(tab["A"]), up(tab["B"]), up(tab["S"]), up(tab["ddt"])
+    out = torch.empty((T + 1, B, D) if time_major else (B, T + 1, D), dtype=torch.float32, device=dev)
+    slot_stride, ens_stride = (B * D, D) if time_major else (D, (T + 1) * D)
+    ptr = lambda t: t.data_ptr() if T else None
+    _lib.call("fbsmi_affine_em_path_batched", ptr(keys_t), ptr(At), ptr(Bt), ptr(St), ptr(ht), xTt.data_ptr(),
+              x0t.data_ptr(), T, nsub, D, int(bool(replace)), B, out.data_ptr(), slot_stride, ens_stride, int(bool(reverse)),
+              ops._stream())
+    return out.reshape(((T + 1, B) if time_major else (B, T + 1)) + shape)

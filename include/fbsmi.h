@@ -859,6 +859,45 @@ int fbsmi_em_fwd_step_batched(const fbsmi_em_mask_batch* mask, int64_t D, const 
                               int64_t u_slot_stride, int64_t u_b_stride, float* out_v, int64_t v_slot_stride,
                               int64_t v_b_stride, void* stream);
 
+/* ---- the rest of a Gibbs sweep for B ensembles in lockstep (fbs_amd/samplers/gibbs_batched.py): the forced move, the
+ * fresh reference indices, the backward scanning pass and the Doob bridge of marg_y.  Each is its single-ensemble entry
+ * point per ensemble, bit for bit, in one launch.  keys, w, k, log_w_T, As, uss, target, x0: device arrays. ----
+ *
+ * force_move: out_i[b] = fbsmi_force_move(keys[b], w[b], k[b], n)'s index (gibbs.py:171-214).  With w_k = w[b][k],
+ * temp = 1 - w_k:  rest_e = (e == k ? 0 : w_e) / temp when w_k < 1, else float32(1.0 / n);  cdf = the canonical-tree scan
+ * of rest (fbsmi_cumsum's);  (ka, kb) = split(keys[b], 2);  i = searchsorted_left(cdf, cdf[n - 1] * (1 - uniform(ka, ())));
+ * u = uniform(kb, ());  out_i = u * (1 - w_i) < temp ? i : k.  out_alpha, nullable, receives
+ * clip(tree-sum_e nan_to_zero(temp * rest_e / (1 - w_e)), 0, 1) and costs nothing when NULL.  One workgroup per ensemble,
+ * 1 <= n <= 1024.  k[b] outside [0, n) is clamped before it addresses memory, and so is i.  Refusals as
+ * fbsmi_normalise_batched. */
+int fbsmi_force_move_batched(const uint32_t* keys, const float* w, const int32_t* k, int64_t B, int64_t n, int32_t* out_i,
+                             float* out_alpha, void* stream);
+/* Row b of out (B, n) = fbsmi_randint(keys[b], n, lo, hi), bit for bit, in one launch; any n (min(ceil(n / 256), 64)
+ * workgroups per row).  FBSMI_ERR_ARG for a null pointer, B < 1, n < 0, n > 2^32 - 4 or more workgroups than one grid
+ * holds; n == 0 launches nothing. */
+int fbsmi_randint_batched(const uint32_t* keys, int64_t B, int64_t n, int32_t lo, int32_t hi, int32_t* out, void* stream);
+/* backscan: ensemble b = backward_scanning_pass(keys[b], As[:, b], uss[:, b], log_w_T[b]) (csmc.py:230-270):
+ *   w = fbsmi_normalise(log_w_T[b], log_space = 0) with the arithmetic of fbsmi_normalise_batched;
+ *   Bs[b][T] = fbsmi_categorical(keys[b], w);  Bs[b][k - 1] = As[k - 1][b][Bs[b][k]] for k = T .. 1 (fbsmi_backtrace);
+ *   path[b][k] = uss[k][b][Bs[b][k]] for k = 0 .. T.
+ * As (T, B, n) int32 and uss (T + 1, B, n, du) are TIME-major, the way the forward pass produces them; Bs (B, T + 1) int32
+ * and path (B, T + 1, du) are batch-major.  One workgroup per ensemble: one thread walks the trace and parks it in Bs,
+ * after a barrier all threads copy the rows.  Every index is clamped into [0, n) before it addresses memory.  T = 0 is
+ * allowed (As is then not read).  FBSMI_ERR_ARG for a null pointer, T < 0, B, n or du < 1; FBSMI_ERR_UNSUPPORTED for
+ * n > 1024. */
+int fbsmi_backscan_batched(const uint32_t* keys, const float* log_w_T, const int32_t* As, const float* uss, int64_t B,
+                           int64_t n, int32_t T, int64_t du, int32_t* Bs, float* path, void* stream);
+/* affine_em_path: ensemble b = fbsmi_affine_em_path(keys[b], A, Bt, S, ddt, target[b], x0[b], T, nsub, D, replace_last),
+ * the same expression under the same contraction setting (the numeric specification restated at
+ * fbsmi_lg_sweep_set_bridge); the tables A, Bt, S (T * nsub) and ddt (T) are shared by the ensembles.  keys (B, T, 2),
+ * target, x0 (B, D).  Point k of ensemble b is written at out + (reverse ? T - k : k) * slot_stride + b * ens_stride
+ * (strides in floats): the reversed, time-major observation path of a sweep needs no flip and no stack.  64-thread
+ * workgroups, min(ceil(D / 64), 64) per ensemble, any D >= 1.  FBSMI_ERR_ARG for a null pointer the call reads, T < 0,
+ * nsub < 1, D < 1, B outside [1, 2^31 - 1], nsub * D > 2^32 - 4, a negative stride or more workgroups than one grid holds. */
+int fbsmi_affine_em_path_batched(const uint32_t* keys, const float* A, const float* Bt, const float* S, const float* ddt,
+                                 const float* target, const float* x0, int32_t T, int32_t nsub, int64_t D, int replace_last,
+                                 int64_t B, float* out, int64_t slot_stride, int64_t ens_stride, int reverse, void* stream);
+
 /* ---- the step of the image twisted SMC for B ensembles in lockstep (fbs_amd/twisted.py make_image_twisted_batched;
  * experiments/imgs/inpainting_twisted.py:97-154; score mode only) ----
  * Particles are whole images: X (B * n, D) float32 in image order, D = du + dv = w * h * c, row b * n + r = particle r of
