@@ -10,6 +10,8 @@ reverse-SDE trajectory with the observed pixels re-noised every step; `*-csgm.np
 every SMC step is two HIP kernels around one network evaluation (PyTorch-ROCm).  With `--batch B` the test images of the
 gibbs*, filter and pmcmc* methods advance in groups of B, one network evaluation per step for the group (fbs_amd.samplers
 gibbs_kernel_batched, gibbs_init_batched, pmcmc_kernel_batched); every image keeps the keys of the sequential run.  With
+`--batch_init --init_method smoother` the initialiser's backward smoother advances in lockstep too, on the network outputs
+its filter kept (`--init_smoother` chooses otherwise).  With
 `--method csgm --batch B` the (image, sample) trajectories of the run advance in groups of B (fbs_amd.csgm
 make_image_csgm_batched), each with the key of the sequential run; with `--method twisted --batch B` the (image, sample)
 twisted-SMC runs do (fbs_amd.twisted make_image_twisted_batched: the same keys and draws, its own specified arithmetic).
@@ -62,6 +64,7 @@ def main(argv=None):
     p.add_argument('--chunk', type=int, default=4096, help='Particles per network call (a power of two: MIOpen ships kernels for those batch sizes; bigger calls are faster per particle).')
     p.add_argument('--batch', type=int, default=1, help="'filter', 'gibbs*' and 'pmcmc*' methods: test images that advance together, one network call per step for all of them; 'csgm': (image, sample) trajectories that advance together, one launch and one network call per step; 'twisted': (image, sample) twisted-SMC runs that advance together, six launches and two network passes per step (1: one at a time).")
     p.add_argument('--batch_init', action='store_true', help="With --batch and a gibbs* method: the images' gibbs_init filters advance together too (gibbs_init_batched); by default gibbs_init runs per image.")
+    p.add_argument('--init_smoother', type=str, default=None, choices=('loop', 'lockstep', 'reuse'), help="With --batch_init and --init_method smoother: how the backward smoother runs behind the batched filter (gibbs_init_batched's `smoother`). Default 'reuse': no network call in the backward pass.")
     p.add_argument('--outdir', type=str, default='./imgs/results')
     p.add_argument('--quiet', action='store_true')
     args = p.parse_args(argv)
@@ -153,9 +156,10 @@ def main(argv=None):
                 masks.append(mask), y0s.append(test_y0), heads.append(head)
             to_img = lambda b, x0: ds.concat(x0.unsqueeze(0), y0s[b], masks[b])[0].cpu().numpy()
             keys_of = lambda i: np.stack([job[4][i] for job in group], 0)
+            # the smoother behind a batched init reuses the filter's network outputs unless --init_smoother says otherwise
             init = lambda keys_, method: gibbs_init_batched(keys_, y0s, x_shape, ts, sb.fwd_sampler, sde, sb.unpack,
                                                             nparticles=args.nparticles, method=method, marg_y=args.marg,
-                                                            mask_=masks, **cl)[0]
+                                                            smoother=args.init_smoother or 'reuse', mask_=masks, **cl)[0]
             restored = np.zeros((nb, args.nsamples, resolution, resolution, nchannels), np.float32)
             if is_filter:
                 for i in range(args.nsamples):

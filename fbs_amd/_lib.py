@@ -311,6 +311,9 @@ SIGNATURES = {
     "fbsmi_backscan_batched": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),
     "fbsmi_affine_em_path_batched": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, C.c_int, _i64, _vp, _i64,
                                                _i64, C.c_int, _vp]),
+    "fbsmi_em_translp_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _i64, _vp, C.c_int, C.c_int, _f, _f, _f, _f, _vp,
+                                           _i64, _i64, _i64, _vp, _vp]),
+    "fbsmi_backsim_pick_batched": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "fbsmi_tw_img_gather_batched": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "fbsmi_tw_img_twist_batched": (C.c_int, [C.POINTER(EMMaskBatchStruct), _vp, _vp, C.c_int, _f, _f, _f, _f, _vp, _vp, _vp,
                                              _vp, _i64, _i64, _vp, _vp, _vp]),

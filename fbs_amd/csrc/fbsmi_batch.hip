@@ -16,6 +16,8 @@
 //   fbsmi_randint_batched       row b = fbsmi_randint(keys[b], n, lo, hi)
 //   fbsmi_backscan_batched      ensemble b = backward_scanning_pass: normalise, categorical, back-trace, row gather
 //   fbsmi_affine_em_path_batched  ensemble b = fbsmi_affine_em_path on its own keys, target and start, in either order
+//   fbsmi_em_translp_batched    ensemble b = fbsmi_em_transition_logpdf on its own particles, network rows and target
+//   fbsmi_backsim_pick_batched  ensemble b = one step of backward simulation: reweight, normalise, categorical, row copy
 //
 // each bit for bit, and the step of the image twisted SMC (whole-image particles; fbs_amd/twisted.py
 // make_image_twisted_batched), which has no single-ensemble kernel to equal: its arithmetic is specified in include/fbsmi.h
@@ -872,6 +874,102 @@ __global__ void __launch_bounds__(kBlock) k_em_fwd_step_b(const PathArgs a, cons
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward simulation of B ensembles (samplers/smc_batched.py bootstrap_backward_smoother_batched, samplers/csmc/csmc.py
+// backward_sampling_pass_batched): a step is k_em_translp_b, then k_backsim_pick_b
+// ------------------------------------------------------------------------------------------------
+struct TranslpArgs {
+    const float* us;       // row (b, r) at us + b * us_ens + r * du
+    const void* net;       // (B * n, D)
+    const float* u;        // the target of ensemble b at u + b * u_ens
+    float* lw;             // (B, n)
+    const int32_t* u_off;  // (nmasks, du)
+    int64_t us_ens, u_ens;
+    int32_t du, D, nmasks, n;
+    float cx, cs, dt, sd;
+};
+
+// row (b, r) = fbsmi_em_transition_logpdf of ensemble b alone: the lw loop of k_em_finish_b over the du unobserved elements,
+// base the row's own us, target the ensemble's u.  One workgroup per row of the flat B * n axis.
+template <int NETDT, int MODE>
+__global__ void __launch_bounds__(kBlock) k_em_translp_b(const TranslpArgs a) {
+    __shared__ float seg[kMaxSeg];
+    const int64_t row = blockIdx.x;
+    const int b = (int)(row / a.n), r = (int)(row - (int64_t)b * a.n);
+    const int du = a.du;
+    const int32_t* __restrict__ u_off = a.u_off + (a.nmasks == 1 ? 0 : (int64_t)b * du);
+    const float* __restrict__ x = a.us + (int64_t)b * a.us_ens + (int64_t)r * du;
+    const float* __restrict__ u = a.u + (int64_t)b * a.u_ens;
+    const int64_t net_row = row * a.D;
+    const int nseg = (du + 255) >> 8;
+    const int nsp = next_pow2(nseg);
+    const float var = a.sd * a.sd;
+    const float lognorm = fbsmi_logf(6.2831855f * var);
+    for (int i = threadIdx.x; i < nsp; i += kBlock) seg[i] = 0.0f;
+    __syncthreads();
+    for (int s0 = 0; s0 < du; s0 += 4 * kBlock) {   // uniform trip count: every wave takes part in every round
+        const int j0 = s0 + (int)threadIdx.x * 4;
+        float t[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            t[k] = 0.0f;
+            if (j0 + k < du) {
+                const float sv = net_value<NETDT>(a.net, net_row + clamp_index(u_off[j0 + k], a.D - 1));
+                const float bv = x[j0 + k];
+                const float dr = reverse_drift<MODE>(a.cx, a.cs, bv, sv);
+                const float m = bv + dr * a.dt;
+                t[k] = tw_nlp(u[j0 + k], m, var, lognorm);
+            }
+        }
+        tw_segment(t, seg, s0, nseg);
+    }
+    lds_upsweep(seg, nsp, nsp);
+    if (threadIdx.x == 0) a.lw[row] = seg[nsp - 1];
+}
+
+// ensemble b: g = lw[b], with log_w g = (g - max(g)) + log_w[b] (csmc.py:206-208); w = normalise(g, log_space = 0) with the
+// arithmetic of k_normalise_b; i = the draw and search of k_categorical_b on w; idx[b * idx_stride] = i and all threads copy
+// the row us[b][i] to out[b].  blockDim.x = np; i is clamped into [0, n) before it addresses memory.
+__global__ void __launch_bounds__(kMaxRows) k_backsim_pick_b(const uint32_t* __restrict__ keys, const float* __restrict__ lw,
+                                                             const float* __restrict__ log_w, const float* __restrict__ us,
+                                                             int64_t us_ens, int n, int np, int64_t du, int32_t* __restrict__ idx,
+                                                             int64_t idx_stride, float* __restrict__ out, int64_t out_ens) {
+    __shared__ float tr[kMaxRows], cdf[kMaxRows];
+    __shared__ float smax[kMaxRows / 64];
+    __shared__ int32_t s_pick;
+    const int64_t b = blockIdx.x;
+    const int e = threadIdx.x;
+    float g = e < n ? lw[b * n + e] : -__builtin_inff();
+    if (log_w) {   // uniform over the workgroup
+        const float mw = wave_max(g);
+        if ((e & 63) == 0) smax[e >> 6] = mw;
+        __syncthreads();
+        float m = -__builtin_inff();
+        for (int q = 0; q < (np >> 6); ++q) m = fmaxf(m, smax[q]);
+        __syncthreads();   // smax has been read by everyone: lds_row_lse writes it again
+        if (e < n) {
+            const float c = g - m;
+            g = c + log_w[b * n + e];
+        }
+    }
+    const float lse = lds_row_lse(g, n, np, tr, smax);
+    __syncthreads();   // the row's tree in tr has been read by everyone
+    tr[e] = e < n ? fbsmi_expf(g - lse) : 0.0f;
+    lds_upsweep(tr, np, np);
+    cdf[e] = lds_scan_at(tr, np, e);
+    __syncthreads();
+    if (e == 0) {
+        const float u = uniform_at(keys[2 * b], keys[2 * b + 1], 1, 0);
+        s_pick = clamp_index(searchsorted_left(cdf, n, bisect_levels(n), cdf[n - 1] * (1.0f - u)), n - 1);
+    }
+    __syncthreads();
+    const int64_t i = s_pick;
+    if (e == 0) idx[b * idx_stride] = (int32_t)i;
+    const float* __restrict__ src = us + b * us_ens + i * du;
+    float* __restrict__ o = out + b * out_ens;
+    for (int64_t c = e; c < du; c += blockDim.x) o[c] = src[c];
+}
+
 #define FBSMI_NEED(cond, msg) \
     if (!(cond)) return fail(FBSMI_ERR_ARG, msg)
 #define FBSMI_LAUNCH_CHECK()                                                 \
@@ -1262,6 +1360,46 @@ int fbsmi_backscan_batched(const uint32_t* keys, const float* log_w_T, const int
     if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "backscan_batched: more than 1024 rows per ensemble");
     const int np = threads_for(n);
     k_backscan_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(keys, log_w_T, As, uss, B, (int)n, np, (int)T, du, Bs, path);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_em_translp_batched(const fbsmi_em_mask_batch* mask, const float* us, int64_t us_ens_stride, const void* net,
+                             int net_dtype, int mode, float cx, float cs, float dt, float sd, const float* u,
+                             int64_t u_ens_stride, int64_t B, int64_t n, float* lw, void* stream) {
+    FBSMI_NEED(mask && mask->u_off && us && net && u && lw, "em_translp_batched: null pointer");
+    FBSMI_NEED(B >= 1 && n >= 1 && mask->du >= 1 && mask->dv >= 0, "em_translp_batched: B, n and du must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "em_translp_batched: more than 1024 rows per ensemble");
+    FBSMI_NEED(mask->nmasks == 1 || mask->nmasks == B, "em_translp_batched: nmasks must be 1 or B");
+    FBSMI_NEED((net_dtype == 0 || net_dtype == 1) && (mode == 0 || mode == 1), "em_translp_batched: bad net_dtype or mode");
+    FBSMI_NEED(us_ens_stride >= 0 && u_ens_stride >= 0, "em_translp_batched: negative stride");
+    FBSMI_NEED(B * n <= kMaxGrid, "em_translp_batched: too many rows for one grid");
+    if (mask->du > kMaxSeg * 256) return fail(FBSMI_ERR_UNSUPPORTED, "em_translp_batched: unobserved part too long");
+    TranslpArgs a = {};
+    a.us = us; a.net = net; a.u = u; a.lw = lw; a.u_off = mask->u_off;
+    a.us_ens = us_ens_stride; a.u_ens = u_ens_stride;
+    a.du = mask->du; a.D = mask->du + mask->dv; a.nmasks = mask->nmasks; a.n = (int32_t)n;
+    a.cx = cx; a.cs = cs; a.dt = dt; a.sd = sd;
+    const dim3 grid((unsigned)(B * n));
+    hipStream_t st = (hipStream_t)stream;
+    if (net_dtype == 0 && mode == 0) k_em_translp_b<0, 0><<<grid, kBlock, 0, st>>>(a);
+    else if (net_dtype == 0) k_em_translp_b<0, 1><<<grid, kBlock, 0, st>>>(a);
+    else if (mode == 0) k_em_translp_b<1, 0><<<grid, kBlock, 0, st>>>(a);
+    else k_em_translp_b<1, 1><<<grid, kBlock, 0, st>>>(a);
+    FBSMI_LAUNCH_CHECK();
+    return FBSMI_OK;
+}
+
+int fbsmi_backsim_pick_batched(const uint32_t* keys, const float* lw, const float* log_w, const float* us,
+                               int64_t us_ens_stride, int64_t B, int64_t n, int64_t du, int32_t* idx, int64_t idx_stride,
+                               float* out, int64_t out_ens_stride, void* stream) {
+    FBSMI_NEED(keys && lw && us && idx && out, "backsim_pick_batched: null pointer");
+    FBSMI_NEED(B >= 1 && n >= 1 && du >= 1 && B <= kMaxGrid, "backsim_pick_batched: B, n and du must be at least 1");
+    if (n > kMaxRows) return fail(FBSMI_ERR_UNSUPPORTED, "backsim_pick_batched: more than 1024 rows per ensemble");
+    FBSMI_NEED(us_ens_stride >= 0 && idx_stride >= 0 && out_ens_stride >= 0, "backsim_pick_batched: negative stride");
+    const int np = threads_for(n);
+    k_backsim_pick_b<<<(unsigned)B, np, 0, (hipStream_t)stream>>>(keys, lw, log_w, us, us_ens_stride, (int)n, np, du, idx,
+                                                                  idx_stride, out, out_ens_stride);
     FBSMI_LAUNCH_CHECK();
     return FBSMI_OK;
 }

@@ -360,6 +360,51 @@ def backscan_batched(keys, log_w_T: torch.Tensor, As: torch.Tensor, uss: torch.T
     return path, Bs
 
 
+def backsim_pick_batched(keys, lw: torch.Tensor, us: torch.Tensor, log_w=None, out=None, idx=None):
+    """One step of backward simulation for B ensembles in one launch (fbsmi_backsim_pick_batched): with g = lw[b], or
+    (g - max(g)) + log_w[b] when log_w is given, ensemble b draws i = categorical(keys[b], normalise(g)) and picks the row
+    us[b][i].  keys (B, 2) uint32 on the host or their bits as an int32 device tensor; lw, log_w (B, n), n <= 1024; us
+    (B, n, ...) float32 whose ensembles are contiguous (n, ...) blocks a fixed stride apart (a time slice of a stored
+    (B, T + 1, n, ...) or (T + 1, B, n, ...) array is read in place).  ``out``: a (B, ...) float32 view with contiguous
+    rows a fixed stride apart (a slot of a (B, T + 1, ...) trajectory), ``idx``: a (B,) int32 view (a column of a
+    (B, T + 1) array); fresh tensors when omitted.  -> (rows (B, ...), indices (B,) int32); ensemble b has the bits of
+    ``normalise`` + ``categorical`` + the row gather on its own arrays."""
+    lw2 = _f32c(lw, "lw")
+    if lw2.dim() != 2:
+        raise ValueError("backsim_pick_batched wants lw of shape (B, n)")
+    B, n = lw2.shape
+    dev = lw2.device
+    _require_cuda(us, "us")
+    if us.dtype != torch.float32 or us.dim() < 2 or tuple(us.shape[:2]) != (B, n):
+        raise ValueError("backsim_pick_batched: us must be float32 (B, n, ...)")
+    tail = tuple(us.shape[2:])
+    du = int(np.prod(tail, dtype=np.int64)) if tail else 1
+    if not us[0].is_contiguous() or (B > 1 and us.stride(0) < 0):
+        us = us.contiguous()
+    us_stride = int(us.stride(0)) if B > 1 else n * du
+    lg = None
+    if log_w is not None:
+        lg = _f32c(log_w, "log_w")
+        if tuple(lg.shape) != (B, n):
+            raise ValueError("backsim_pick_batched: log_w must match lw (B, n)")
+    kd = keys_to_device(keys, dev)
+    if kd.numel() != 2 * B:
+        raise ValueError("backsim_pick_batched: keys (B, 2) must match lw (B, n)")
+    if out is None:
+        out = torch.empty((B,) + tail, dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B,) + tail or out.device != dev or not out[0].is_contiguous() \
+            or (B > 1 and out.stride(0) < du):
+        raise ValueError("backsim_pick_batched: out must be float32 (B, ...) on lw's device with contiguous rows")
+    if idx is None:
+        idx = torch.empty(B, dtype=torch.int32, device=dev)
+    if idx.dtype != torch.int32 or tuple(idx.shape) != (B,) or idx.device != dev or (B > 1 and idx.stride(0) < 1):
+        raise ValueError("backsim_pick_batched: idx must be int32 (B,) on lw's device")
+    _lib.call("fbsmi_backsim_pick_batched", kd.data_ptr(), lw2.data_ptr(), lg.data_ptr() if lg is not None else None,
+              us.data_ptr(), us_stride, B, n, du, idx.data_ptr(), int(idx.stride(0)) if B > 1 else 1, out.data_ptr(),
+              int(out.stride(0)) if B > 1 else du, _stream())
+    return out, idx
+
+
 def searchsorted(a: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     a = _f32c(a, "a").reshape(-1)
     qq = _f32c(q, "q")

@@ -102,6 +102,44 @@ def backward_sampling_pass(key, transition_logpdf, vs, ts, uss, log_ws, *args, *
     return torch.stack(xs[::-1], 0), torch.stack(Bs[::-1], 0).to(torch.int32)
 
 
+def backward_sampling_pass_batched(keys, transition_logpdf, vss, ts, uss, log_wss, **kwargs):
+    """``backward_sampling_pass`` for B ensembles: keys (B, 2), vss (B, T + 1, q, c), uss (B, T + 1, n, p, c), log_wss
+    (B, T + 1, n), ``mask_`` one mask or a list of B.  Returns (xs (B, T + 1, p, c), Bs (B, T + 1) int32), equal to the
+    stacked results of
+
+        [backward_sampling_pass(keys[b], transition_logpdf, vss[b], ts, uss[b], log_wss[b], mask_=masks[b]) for b in range(B)]
+
+    bit for bit whenever the score function's output row does not depend on which other rows share its call.  The
+    ensembles advance in lockstep under the conditions of ``bootstrap_backward_smoother_batched``: per step one network
+    call on B * n rows (the forward pass evaluated the network on gathered ancestors, not on the stored particles, so
+    there is nothing to reuse), one fbsmi_em_translp_batched and one fbsmi_backsim_pick_batched launch, the final draw one
+    more of the latter; the keys are uploaded once and nothing is read back inside the loop.  Anything else runs the loop
+    above."""
+    from ..smc_batched import _backsim_lockstep, _host_keys, _host_ts, _masks_of
+    keys = _host_keys(keys)
+    B = keys.shape[0]
+    lock = _backsim_lockstep(transition_logpdf, uss.shape[2], kwargs, B)
+    if lock is None:
+        _, _, kw = _masks_of(kwargs, B)
+        outs = [backward_sampling_pass(keys[b], transition_logpdf, vss[b], ts, uss[b], log_wss[b], **kw(b)) for b in range(B)]
+        return torch.stack([o[0] for o in outs], 0), torch.stack([o[1] for o in outs], 0)
+    sb, mb = lock
+    dev = uss.device
+    T = int(uss.shape[1]) - 1
+    uss, vss = ops._f32c(uss, "uss"), ops._f32c(vss, "vss")
+    lws = ops._f32c(log_wss, "log_wss").transpose(0, 1).contiguous()                # (T + 1, B, n)
+    ts_h = _host_ts(ts)
+    kd = ops.keys_to_device(np.stack([ops.split(keys[b], T + 1) for b in range(B)], 1), dev)    # :194, (T + 1, B, 2), once
+    xs = torch.empty((B, T + 1) + tuple(uss.shape[3:]), dtype=torch.float32, device=dev)
+    Bs = torch.empty((B, T + 1), dtype=torch.int32, device=dev)
+    ops.backsim_pick_batched(kd[T], lws[T], uss[:, T], out=xs[:, T], idx=Bs[:, T])  # :200-201
+    for s in range(T):                                                              # :214, in reverse time
+        t = T - 1 - s
+        Gamma_log_w = sb.transition_logpdf_batched(xs[:, t + 1], uss[:, t], vss[:, t], ts_h[t], mb)      # :205
+        ops.backsim_pick_batched(kd[s], Gamma_log_w, uss[:, t], log_w=lws[t], out=xs[:, t], idx=Bs[:, t])   # :206-209
+    return xs, Bs
+
+
 def backward_scanning_pass(key, As, xss, log_w_T):
     """Backward scanning pass (csmc.py:230-270): B_T ~ Cat(w_T), B_{k-1} = A_k[B_k]."""
     B_T = barker_move(key, normalise(log_w_T))                                     # :257

@@ -6,7 +6,8 @@ B * nparticles rows between single launches of the batched sampler kernels (fbs_
 calls on `nparticles` rows each among a dozen launches per ensemble.  Every function here is the loop of its
 single-ensemble namesake in ``smc.py`` / ``gibbs.py`` over the ensembles, with the same keys, run that way, and falls back
 to that loop when the lockstep conditions do not hold.  ``gibbs_init_batched`` also draws the Doob bridges of ``marg_y``
-(its default) for all ensembles in one launch.
+(its default) for all ensembles in one launch.  ``bootstrap_backward_smoother_batched`` is the backward smoother of all
+ensembles, two launches per step round one network call -- or round none, on the network outputs the filter kept.
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ import torch
 from .. import _lib, ops
 from ..score import bridge_of, is_own_method
 from ..sdes.simulators import doob_bridge_simulator_batched
+from . import gibbs_batched as _gibbs_batched
 from . import resampling as _resampling
 from .common import MCMCState
 from .gibbs import gibbs_init
@@ -97,10 +99,22 @@ def _host_ts(ts):
     return [float(t) for t in (ts.detach().cpu().numpy() if isinstance(ts, torch.Tensor) else np.asarray(ts)).reshape(-1)]
 
 
-def _filter_lockstep(sb, rname, mb, us, vss, ts, key_proposal, key_resampling, nparticles, return_last):
-    """The time loop of ``bootstrap_filter`` (smc.py:55-71) for all ensembles.  us (B, n, p, c) the initial particles."""
+def net_store_fits(nsteps: int, B: int, n: int, D: int, itemsize: int, cap: int = None) -> bool:
+    """Whether the network outputs of a whole filter, nsteps * B * n * D elements of `itemsize` bytes, may be kept for the
+    backward smoother (``gibbs_init_batched(smoother='reuse')``): at most ``LOCKSTEP_STORE_BYTES`` (or `cap`) bytes.  A
+    store above it is not made, and the smoother evaluates the network again."""
+    cap = _gibbs_batched.LOCKSTEP_STORE_BYTES if cap is None else cap
+    return int(nsteps) * int(B) * int(n) * int(D) * int(itemsize) <= int(cap)
+
+
+def _filter_lockstep(sb, rname, mb, us, vss, ts, key_proposal, key_resampling, nparticles, return_last, net_store=None):
+    """The time loop of ``bootstrap_filter`` (smc.py:55-71) for all ensembles.  us (B, n, p, c) the initial particles.
+    net_store: a dict that receives, under 'net', the network output of every step, (T, B * n, D) in the network's dtype
+    (step k ran on concat(filtering[k], vs[k]) at ts[k]; with return_last=False only, where no step gathers ancestors),
+    or None when ``net_store_fits`` refuses its size."""
     dev = us.device
     nsteps = vss.shape[1] - 1
+    kept = None
     vs = vss.transpose(0, 1).contiguous()                                          # (T + 1, B, q, c)
     ts_h = _host_ts(ts)
     k_prop = ops.keys_to_device(key_proposal, dev)                                  # the whole run's keys, uploaded once
@@ -111,6 +125,12 @@ def _filter_lockstep(sb, rname, mb, us, vss, ts, key_proposal, key_resampling, n
     pending = None                                                                  # ancestors not gathered yet
     for k in range(nsteps):
         us_new, lw = sb.fused_step_batched(us, pending, vs[k + 1], vs[k], ts_h[k], k_prop[k], mb)
+        if net_store is not None and not return_last:
+            net = sb._buf["net"]                                                    # (B * n, D), written by the call above
+            if k == 0 and net_store_fits(nsteps, 1, net.shape[0], net.shape[1], net.element_size()):
+                kept = torch.empty((nsteps,) + tuple(net.shape), dtype=net.dtype, device=dev)
+            if kept is not None:
+                kept[k].copy_(net)
         w, c = ops.normalise_batched(lw, return_lse=True)
         nell = nell - (c - logn)
         inds = ops.resample_batched(w, k_res[k], rname)
@@ -120,7 +140,84 @@ def _filter_lockstep(sb, rname, mb, us, vss, ts, key_proposal, key_resampling, n
         us, pending = _take(us_new, inds), None
         if not return_last:
             filtering.append(us)
+    if net_store is not None:
+        net_store["net"] = kept
     return (us if return_last else torch.stack(filtering, 1)), nell
+
+
+def smoother_key_schedule(keys, nsteps: int) -> dict:
+    """Every key ``bootstrap_backward_smoother`` uses, for B smoothers, on the host: smc.py:109 draws the index of u_T
+    with the PARENT key, and :108, :110 split its second half into one key per step.  -> (B, 2) array 'last' (the parent
+    keys) and (nsteps, B, 2) array 'steps', both uint32; steps[s] is the key of the s-th backward step, the one that
+    picks time nsteps - 1 - s."""
+    keys = _host_keys(keys)
+    B, T = keys.shape[0], int(nsteps)
+    steps = np.zeros((T, B, 2), np.uint32)
+    for b in range(B):
+        steps[:, b] = ops.split(ops.split(keys[b], 2)[1], T)
+    return {"last": keys.copy(), "steps": steps}
+
+
+def _backsim_lockstep(transition_logpdf, nrows: int, kwargs, B: int):
+    """(bridge, mask batch) when the backward pass of B ensembles can advance in lockstep, else None: the closure is one
+    ScoreBridge's own ``transition_logpdf``, ``mask_`` is the only keyword, masks of one shape, at most 1024 rows."""
+    sb = getattr(transition_logpdf, "__self__", None)
+    if set(kwargs) != {"mask_"} or int(nrows) > MAX_LOCKSTEP_ROWS or not is_own_method(sb, transition_logpdf,
+                                                                                      "transition_logpdf"):
+        return None
+    masks, per_mask, kw = _masks_of(kwargs, B)
+    ems = [sb._em_mask(kw(b)["mask_"]) for b in range(B)]
+    if any((e.du, e.dv) != (ems[0].du, ems[0].dv) for e in ems):
+        return None
+    return sb, sb.em_mask_batch(masks if per_mask else [masks], B)
+
+
+def bootstrap_backward_smoother_batched(keys, filter_uss, vss, ts, transition_logpdf, network_outputs=None, **kwargs):
+    """``bootstrap_backward_smoother`` for B ensembles: keys (B, 2), filter_uss (B, T + 1, n, p, c) as
+    ``bootstrap_filter_batched(return_last=False)`` returns them, vss (B, T + 1, q, c), ``mask_`` one mask or a list of B.
+    Returns the trajectories (B, T + 1, p, c), equal to
+
+        torch.stack([bootstrap_backward_smoother(keys[b], filter_uss[b], vss[b], ts, transition_logpdf, mask_=masks[b])])
+
+    bit for bit whenever the score function's output row does not depend on which other rows share its call.
+
+    The ensembles advance in lockstep when the closure is one ScoreBridge's own ``transition_logpdf``, ``mask_`` is the
+    only keyword, the masks have one shape and n <= 1024: per step one network call on B * n rows
+    (``ScoreBridge.transition_logpdf_batched``) and two launches -- fbsmi_em_translp_batched, then
+    fbsmi_backsim_pick_batched, which writes the picked row straight into the preallocated trajectory where the next step
+    reads it as its target -- with every key uploaded once and nothing read back inside the loop.  Anything else runs the
+    loop above.
+
+    network_outputs (T, B * n, D): the network's output on concat(filter_uss[:, t], vss[:, t]) at ts[t] for every t, in
+    its own dtype -- what the filter that produced filter_uss computed at its step t.  With it the lockstep pass makes
+    no network call at all; the loop ignores it."""
+    keys = _host_keys(keys)
+    B = keys.shape[0]
+    n = int(filter_uss.shape[2])
+    lock = _backsim_lockstep(transition_logpdf, n, kwargs, B)
+    if lock is None:
+        _, _, kw = _masks_of(kwargs, B)
+        return torch.stack([bootstrap_backward_smoother(keys[b], filter_uss[b], vss[b], ts, transition_logpdf, **kw(b))
+                            for b in range(B)], 0)
+    sb, mb = lock
+    dev = filter_uss.device
+    T = int(filter_uss.shape[1]) - 1
+    if network_outputs is not None and (network_outputs.dim() != 3 or int(network_outputs.shape[0]) != T):
+        raise ValueError("network_outputs must be (T, B * n, D)")
+    filter_uss = ops._f32c(filter_uss, "filter_uss")
+    vss = ops._f32c(vss, "vss")
+    ts_h = _host_ts(ts)
+    sk = smoother_key_schedule(keys, T)
+    k_steps = ops.keys_to_device(sk["steps"], dev)                                  # the whole pass's keys, uploaded once
+    traj = torch.empty((B, T + 1) + tuple(filter_uss.shape[3:]), dtype=torch.float32, device=dev)
+    last = ops.randint_batched(sk["last"], 1, 0, n, device=dev)                     # :109, (B, 1)
+    traj[:, T] = _take(filter_uss[:, T], last)[:, 0]
+    for s in range(T):                                                              # filter_us[-2::-1], vs[-2::-1], ts[-2::-1]
+        t = T - 1 - s
+        lw = sb.transition_logpdf_batched(traj[:, t + 1], filter_uss[:, t], vss[:, t], ts_h[t], mb,
+                                          net=None if network_outputs is None else network_outputs[t])     # :101
+        ops.backsim_pick_batched(k_steps[s], lw, filter_uss[:, t], out=traj[:, t])  # :103-104 and the row gather
+    return traj
 
 
 def bootstrap_filter_batched(transition_sampler, measurement_cond_pdf, vss, ts, init_sampler, keys, nparticles, resampling,
@@ -270,15 +367,26 @@ def pmcmc_kernel_batched(keys, uTs, log_ells, yss, y0s, ts, fwd_ys_sampler, sde,
 
 
 def gibbs_init_batched(keys, y0s, x0_shape, ts, fwd_sampler, sde, unpack, transition_sampler, transition_logpdf,
-                       likelihood_logpdf, nparticles, method: str = 'smoother', marg_y: bool = True, x0s=None, **kwargs):
+                       likelihood_logpdf, nparticles, method: str = 'smoother', marg_y: bool = True, x0s=None,
+                       smoother: str = 'loop', **kwargs):
     """``gibbs_init`` for B ensembles: keys (B, 2), y0s one observation or B of them, x0s None or (B, p, c), ``mask_`` one
     mask or a list of B.  Returns (approx_x0 (B, ...), approx_us_star (B, T + 1, p, c) or None for 'debug'), the stacked
     results of the loop over the ensembles under the contract and the lockstep conditions of
     ``bootstrap_filter_batched``.  With 'filter' and 'smoother' the bootstrap filters advance in lockstep, and so do the
     forward paths when ``fwd_sampler`` and ``unpack`` are the bridge's own methods (``ScoreBridge.fwd_sampler_batched``;
     any other closure is called per ensemble); with marg_y the Doob bridges of all ensembles are one launch
-    (``doob_bridge_simulator_batched``) and the initial particles of all ensembles are one draw; the backward smoother
-    runs per ensemble.  'debug' and 'kalman' run the loop."""
+    (``doob_bridge_simulator_batched``) and the initial particles of all ensembles are one draw.  'debug' and 'kalman'
+    run the loop.
+
+    ``smoother`` says how the backward smoother of method 'smoother' runs behind the lockstep filter:
+    'loop' (the default), per ensemble: B * T network calls of `nparticles` rows; 'lockstep',
+    ``bootstrap_backward_smoother_batched``: T network calls for all ensembles; 'reuse', the same with the network
+    outputs the filter computed -- step t of the smoother evaluates the network on concat(filter_us[t], vs[t]) at ts[t],
+    the input of the filter's step t -- kept in a (T, B * nparticles, D) array of the network's dtype, so the backward
+    pass makes no network call.  A store above ``LOCKSTEP_STORE_BYTES`` is not made and 'reuse' runs 'lockstep'.  The
+    three give the same bits under the contract above."""
+    if smoother not in ("loop", "lockstep", "reuse"):
+        raise ValueError(f"Unknown smoother {smoother}")
     keys = _host_keys(keys)
     B = keys.shape[0]
     y0 = _per_ensemble(y0s, B, len(tuple(x0_shape)))
@@ -318,8 +426,14 @@ def gibbs_init_batched(keys, y0s, x0_shape, ts, fwd_sampler, sde, unpack, transi
     _lib.call("fbsmi_normal_batched", ops.keys_to_device(key_of(2), dev).data_ptr(), B, u0s[0].numel(), u0s.data_ptr(),
               ops._stream())
     sk = filter_key_schedule(key_of(3), vss.shape[1] - 1)
+    # the filter's network outputs serve the smoother only when it evaluates the same bridge
+    store = {} if (method == "smoother" and smoother == "reuse"
+                   and is_own_method(sb, transition_logpdf, "transition_logpdf")) else None
     uss, _ = _filter_lockstep(sb, rname, mb, u0s, vss, ts, sk["proposal"], sk["resampling"], nparticles,
-                              method == "filter")
+                              method == "filter", net_store=store)
+    if method == "smoother" and smoother != "loop":                                 # postamble (gibbs.py:56-57), at once
+        return uss[:, -1, 0].contiguous(), bootstrap_backward_smoother_batched(
+            key_of(5), uss, vss, ts, transition_logpdf, network_outputs=None if store is None else store["net"], **kwargs)
     if own_fwd and method == "filter":                                              # postamble (gibbs.py:49-52), at once
         approx_x0 = uss[:, 0].contiguous()
         return approx_x0, sb.fwd_sampler_batched(np.stack([ks[b][4] for b in range(B)], 0), approx_x0, y0s, mb,

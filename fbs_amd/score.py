@@ -219,6 +219,65 @@ class ScoreBridge:
         return mb
 
     @torch.no_grad()
+    def _network_batched(self, us3, A32, vp, t_prev, mb: EMMaskBatch) -> torch.Tensor:
+        """nn(concat(us[b][A[b]], v_prev[b]), T - t) for every row of every ensemble -> (B * n, D) in the network's own
+        output dtype: one fbsmi_em_concat_batched launch, then the network in `chunk`-row pieces over the flat B * n rows
+        (a chunk may straddle ensembles).  us3 (B, n, du) float32 contiguous, A32 (B, n) int32 or None, vp (B, dv).  The
+        result is the bridge's shared 'net' buffer: the next network evaluation overwrites it."""
+        B, n = int(us3.shape[0]), int(us3.shape[1])
+        self._cache = None                                   # the shared network buffer is about to be rewritten
+        dev = us3.device
+        w, h, c = self.dataset.image_shape
+        img = self._buffer("img", (B * n, w, h, c), self.net_input_dtype, dev)
+        _lib.call("fbsmi_em_concat_batched", mb.ref, us3.data_ptr(), A32.data_ptr() if A32 is not None else None,
+                  vp.data_ptr(), B, n, _NET_DT[self.net_input_dtype], img.data_ptr(), ops._stream())
+        tf = self.T - float(t_prev)
+        net = None
+        for s in range(0, B * n, self.chunk):
+            y = self.score_fn(img[s:s + self.chunk], tf)
+            if net is None:
+                if y.dtype not in _NET_DT:
+                    y = y.float()
+                net = self._buffer("net", (B * n, mb.D), y.dtype, dev)
+            net[s:s + self.chunk] = y.reshape(-1, mb.D)
+        return net
+
+    @staticmethod
+    def _ensemble_blocks(x, B: int, name: str):
+        """x (B, ...) float32 on the device -> (tensor, stride in floats between its ensembles): read in place when every
+        x[b] is contiguous and the ensembles are a fixed non-negative stride apart, copied otherwise."""
+        ops._require_cuda(x, name)
+        if x.dtype != torch.float32 or not x[0].is_contiguous() or (B > 1 and x.stride(0) < x[0].numel()):
+            x = ops._f32c(x, name)
+        return x, (int(x.stride(0)) if B > 1 else int(x[0].numel()))
+
+    @torch.no_grad()
+    def transition_logpdf_batched(self, u, us, v_prev, t_prev, masks, net=None):
+        """``transition_logpdf`` for B ensembles at the same time step: u (B, p, c) the targets, us (B, n, p, c) the
+        particles, v_prev (B, q, c); masks one mask, a list of B masks of one shape, or an EMMaskBatch.  -> lw (B, n) with
+        lw[b] = transition_logpdf(u[b], us[b], v_prev[b], t_prev, masks[b]) bit for bit whenever the network's output row
+        does not depend on which rows share its call.  One fbsmi_em_translp_batched launch; u and us may be time slices
+        of stored (B, T + 1, ...) arrays and are then read in place.  Without ``net`` the network runs on
+        concat(us, v_prev) as in ``fused_step_batched``; with ``net`` (B * n, D), its output on that input kept from an
+        earlier call, there is no network call and v_prev is not read."""
+        B, n = int(us.shape[0]), int(us.shape[1])
+        mb = self.em_mask_batch(masks, B)
+        us_b, us_stride = self._ensemble_blocks(us, B, "us")
+        u_b, u_stride = self._ensemble_blocks(u, B, "u")
+        if us_b[0].numel() != n * mb.du or u_b[0].numel() != mb.du:
+            raise ValueError(f"us rows and u must hold the masks' unobserved part, {mb.du} floats")
+        if net is None:
+            net = self._network_batched(ops._f32c(us_b, "us").reshape(B, n, -1), None,
+                                        ops._f32c(v_prev, "v_prev").reshape(B, -1), t_prev, mb)
+        elif net.dtype not in _NET_DT or not net.is_contiguous() or net.numel() != B * n * mb.D or net.device != us_b.device:
+            raise ValueError("net must be a contiguous float32 or bfloat16 (B * n, D) tensor on the particles' device")
+        mode, cx, cs, sd = self._coef(t_prev)
+        lw = torch.empty((B, n), dtype=torch.float32, device=us_b.device)
+        _lib.call("fbsmi_em_translp_batched", mb.ref, us_b.data_ptr(), us_stride, net.data_ptr(), _NET_DT[net.dtype], mode,
+                  cx, cs, self.dt, sd, u_b.data_ptr(), u_stride, B, n, lw.data_ptr(), ops._stream())
+        return lw
+
+    @torch.no_grad()
     def fused_step_batched(self, us, A, v, v_prev, t_prev, keys, masks, pins=None, want_us=True, out_us=None):
         """``fused_step`` for B ensembles at the same time step: one fbsmi_em_concat_batched launch, the network in
         `chunk`-row pieces over the flat B * n rows (a chunk may straddle ensembles), one fbsmi_em_finish_batched launch.
@@ -235,24 +294,11 @@ class ScoreBridge:
         mb = self.em_mask_batch(masks, B)
         if us3.shape[2] != mb.du:
             raise ValueError(f"us rows hold {us3.shape[2]} floats, the masks' unobserved part {mb.du}")
-        self._cache = None                                   # the shared network buffer is about to be rewritten
         dev = us3.device
         A32 = A.to(torch.int32).contiguous() if A is not None else None
         vv, vp = ops._f32c(v, "v").reshape(B, -1), ops._f32c(v_prev, "v_prev").reshape(B, -1)
-        w, h, c = self.dataset.image_shape
-        img = self._buffer("img", (B * n, w, h, c), self.net_input_dtype, dev)
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.call("fbsmi_em_concat_batched", mb.ref, us3.data_ptr(), ptr(A32), vp.data_ptr(), B, n,
-                  _NET_DT[self.net_input_dtype], img.data_ptr(), ops._stream())
-        tf = self.T - float(t_prev)
-        net = None
-        for s in range(0, B * n, self.chunk):
-            y = self.score_fn(img[s:s + self.chunk], tf)
-            if net is None:
-                if y.dtype not in _NET_DT:
-                    y = y.float()
-                net = self._buffer("net", (B * n, mb.D), y.dtype, dev)
-            net[s:s + self.chunk] = y.reshape(-1, mb.D)
+        net = self._network_batched(us3, A32, vp, t_prev, mb)
         mode, cx, cs, sd = self._coef(t_prev)
         us_new = None
         if want_us and out_us is not None:

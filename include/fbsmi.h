@@ -898,6 +898,36 @@ int fbsmi_affine_em_path_batched(const uint32_t* keys, const float* A, const flo
                                  const float* target, const float* x0, int32_t T, int32_t nsub, int64_t D, int replace_last,
                                  int64_t B, float* out, int64_t slot_stride, int64_t ens_stride, int reverse, void* stream);
 
+/* ---- backward simulation for B ensembles in lockstep (bootstrap_backward_smoother_batched, smc.py:91-112;
+ * backward_sampling_pass_batched, csmc.py:167-227): a step is one em_translp launch and one backsim_pick launch for all
+ * ensembles, and nothing is read back between them. ----
+ *
+ * em_translp: lw[b][r] = fbsmi_em_transition_logpdf of ensemble b alone, bit for bit:
+ *   tree-sum over the unobserved index j in [0, du) of nlp(u[b][j], x + drift * dt, sd * sd),  x = us[b][r][j],
+ *   drift = (cx * x) + (cs * s) (mode 0) or s (mode 1),  s = net[(b * n + r) * D + u_off[j]] (float32, or bfloat16 widened;
+ *   net_dtype 0 / 1), with nlp and the tree-sum as defined for the image twisted SMC below (the summation of
+ *   fbsmi_em_finish_batched's log-weights).  Row (b, r) of the particles is at us + b * us_ens_stride + r * du and the
+ *   target of ensemble b at u + b * u_ens_stride (strides in floats): a time slice of a batch-major (B, T + 1, n, du) or a
+ *   time-major (T + 1, B, n, du) particle array, and a slot of a (B, T + 1, du) trajectory, are read in place.  net
+ *   (B * n, D), lw (B, n).  One workgroup of 256 threads per row; table entries are clamped into [0, D) before they
+ *   address memory.  FBSMI_ERR_ARG for a null pointer, B < 1, n < 1, du < 1, nmasks outside {1, B}, a flag outside {0, 1},
+ *   a negative stride and B * n > 2^31 - 1; FBSMI_ERR_UNSUPPORTED for n > 1024 and du > 2^20.  Nothing is launched then. */
+int fbsmi_em_translp_batched(const fbsmi_em_mask_batch* mask, const float* us, int64_t us_ens_stride, const void* net,
+                             int net_dtype, int mode, float cx, float cs, float dt, float sd, const float* u,
+                             int64_t u_ens_stride, int64_t B, int64_t n, float* lw, void* stream);
+/* backsim_pick: for ensemble b,
+ *   g = lw[b];  with log_w given:  m = max_r g[r],  g[r] = (g[r] - m) + log_w[b][r]  (two roundings, in this order);
+ *   w = fbsmi_normalise(g, log_space = 0) with the arithmetic of fbsmi_normalise_batched;
+ *   i = fbsmi_categorical(keys[b], w), clamped into [0, n);  idx[b * idx_stride] = i;
+ *   out[b * out_ens_stride + c] = us[b * us_ens_stride + i * du + c] for c in [0, du).
+ * keys (B, 2), lw and log_w (B, n) contiguous, log_w nullable; strides in floats / ints: idx may be a column of a
+ * (B, T + 1) array and out a slot of a (B, T + 1, du) trajectory.  One workgroup of next_pow2(n) (at least 64) threads
+ * per ensemble, everything in LDS; every thread reaches every barrier.  FBSMI_ERR_ARG for a null pointer (but log_w),
+ * B, n or du < 1, or a negative stride; FBSMI_ERR_UNSUPPORTED for n > 1024. */
+int fbsmi_backsim_pick_batched(const uint32_t* keys, const float* lw, const float* log_w, const float* us,
+                               int64_t us_ens_stride, int64_t B, int64_t n, int64_t du, int32_t* idx, int64_t idx_stride,
+                               float* out, int64_t out_ens_stride, void* stream);
+
 /* ---- the step of the image twisted SMC for B ensembles in lockstep (fbs_amd/twisted.py make_image_twisted_batched;
  * experiments/imgs/inpainting_twisted.py:97-154; score mode only) ----
  * Particles are whole images: X (B * n, D) float32 in image order, D = du + dv = w * h * c, row b * n + r = particle r of
