@@ -21,6 +21,10 @@ vector in ravel_pytree order) and a dataset (`../datasets/mnist.npz`, `datasets/
 this environment.  If the files are there they are used (fbs_amd.unet.UNet.load_flat_params); otherwise the network is
 randomly initialised and the test image is uniform noise -- the sampler runs the same either way (PNG output is left
 out: matplotlib is not a dependency).
+
+With `--metrics` every group's restored block is scored on the device against its test image before it is saved
+(fbs_amd.image_metrics): `<result file>-metrics.npz` holds `psnr` and `ssim` per sample and, for the gibbs* and pmcmc* chains,
+`autocorr_best`, the best variable's autocorrelation curve.  examples/tabulate_imgs.py tabulates the result files.
 """
 import argparse
 import os
@@ -66,6 +70,8 @@ def main(argv=None):
     p.add_argument('--batch_init', action='store_true', help="With --batch and a gibbs* method: the images' gibbs_init filters advance together too (gibbs_init_batched); by default gibbs_init runs per image.")
     p.add_argument('--init_smoother', type=str, default=None, choices=('loop', 'lockstep', 'reuse'), help="With --batch_init and --init_method smoother: how the backward smoother runs behind the batched filter (gibbs_init_batched's `smoother`). Default 'reuse': no network call in the backward pass.")
     p.add_argument('--outdir', type=str, default='./imgs/results')
+    p.add_argument('--metrics', action='store_true', help="Score every restored image on the device against its test image (fbs_amd.image_metrics) and write <result file>-metrics.npz next to it: psnr and ssim (nsamples,), and for the gibbs* and pmcmc* chains autocorr_best (lags,).")
+    p.add_argument('--metrics_max_lags', type=int, default=20, help='With --metrics: lags of autocorr_best (at most nsamples).')
     p.add_argument('--quiet', action='store_true')
     args = p.parse_args(argv)
 
@@ -119,6 +125,21 @@ def main(argv=None):
     cl = dict(transition_sampler=sb.transition_sampler, transition_logpdf=sb.transition_logpdf,
               likelihood_logpdf=sb.likelihood_logpdf)
     os.makedirs(args.outdir, exist_ok=True)
+
+    def save_metrics(paths, test_imgs, blocks):
+        # --metrics: the restored blocks (len(paths), nsamples, H, W, C) against their test images, one call for all of them
+        from fbs_amd.image_metrics import chain_autocorrelation, psnr_ssim
+        blocks = torch.from_numpy(np.ascontiguousarray(blocks)).to(dev)
+        psnr, ssim = psnr_ssim(torch.stack(list(test_imgs), 0), blocks)
+        extra = [{} for _ in paths]
+        if 'gibbs' in args.method or 'pmcmc' in args.method:                         # a chain: Figure 8's best variable
+            lags = max(1, min(args.metrics_max_lags, args.nsamples))
+            best = chain_autocorrelation(blocks.reshape(len(paths), args.nsamples, -1), lags)[1].cpu().numpy()
+            extra = [dict(autocorr_best=best[b]) for b in range(len(paths))]
+        psnr, ssim = psnr.cpu().numpy(), ssim.cpu().numpy()
+        for b, path in enumerate(paths):
+            np.savez(path + '-metrics', psnr=psnr[b], ssim=ssim[b], **extra[b])
+
     out = None
     if args.batch > 1 and ('gibbs' in args.method or args.method == 'filter' or 'pmcmc' in args.method):
         # Groups of --batch test images advance together (gibbs_kernel_batched, gibbs_init_batched, pmcmc_kernel_batched):
@@ -146,14 +167,14 @@ def main(argv=None):
         for g0 in range(0, len(jobs), args.batch):
             group = jobs[g0:g0 + args.batch]                                       # the last group may be smaller
             nb = len(group)
-            masks, y0s, heads = [], [], []
+            masks, y0s, heads, test_imgs = [], [], [], []
             for k, k_img, k_mask, _, _ in group:
                 test_img = ops.uniform(k_img, (resolution, resolution, nchannels), device=dev)
                 mask = ds.gen_mask(k_mask)
                 _, test_y0 = ds.unpack(test_img, mask)
                 head = os.path.join(args.outdir, f'{args.dataset}-{task}-{args.sde}-{args.nparticles}-{k}')
                 np.savez(head + '-true', test_img=test_img.cpu().numpy())
-                masks.append(mask), y0s.append(test_y0), heads.append(head)
+                masks.append(mask), y0s.append(test_y0), heads.append(head), test_imgs.append(test_img)
             to_img = lambda b, x0: ds.concat(x0.unsqueeze(0), y0s[b], masks[b])[0].cpu().numpy()
             keys_of = lambda i: np.stack([job[4][i] for job in group], 0)
             # the smoother behind a batched init reuses the filter's network outputs unless --init_smoother says otherwise
@@ -199,6 +220,8 @@ def main(argv=None):
                         restored[b, i] = to_img(b, x0s[b])
                     if not args.quiet:
                         print(f'{task} | pMCMC {delta} x{nb} | iter: {i}, acc_prob: {float(st.acceptance_prob.mean()):.3f}')
+            if args.metrics:
+                save_metrics([head + suffix for head in heads], test_imgs, restored)
             for b in range(nb):
                 np.save(heads[b] + suffix, restored[b])
             out = restored[-1]
@@ -221,7 +244,8 @@ def main(argv=None):
             _, test_y0 = ds.unpack(test_img, mask)
             head = os.path.join(args.outdir, f'{args.dataset}-{task}-{args.sde}-{args.nparticles}-{k}')
             np.savez(head + '-true', test_img=test_img.cpu().numpy())
-            images.append((head, mask, test_y0, np.zeros((args.nsamples, resolution, resolution, nchannels), np.float32)))
+            images.append((head, mask, test_y0, np.zeros((args.nsamples, resolution, resolution, nchannels), np.float32),
+                           test_img))
             for i in range(args.nsamples):
                 key, subkey = ops.split(key)
                 jobs.append((len(images) - 1, i, subkey))
@@ -230,11 +254,13 @@ def main(argv=None):
             x0s = sampler(np.stack([j[2] for j in group], 0), [images[j[0]][2] for j in group],
                           [images[j[0]][1] for j in group])
             for b, (m, i, _) in enumerate(group):
-                _, mask, test_y0, restored = images[m]
+                _, mask, test_y0, restored, _ = images[m]
                 restored[i] = ds.concat(x0s[b].unsqueeze(0), test_y0, mask)[0].cpu().numpy()
             if not args.quiet:
                 print(f'{task} | cSGM x{len(group)} | trajectories: {g0 + len(group)} / {len(jobs)}')
-        for head, _, _, restored in images:
+        if args.metrics:
+            save_metrics([im[0] + '-csgm' for im in images], [im[4] for im in images], np.stack([im[3] for im in images], 0))
+        for head, _, _, restored, _ in images:
             np.save(head + '-csgm', restored)
             out = restored
         return out
@@ -263,7 +289,8 @@ def main(argv=None):
             _, test_y0 = ds.unpack(test_img, mask)
             head = os.path.join(args.outdir, f'{args.dataset}-{task}-{args.sde}-{args.nparticles}-{k}')
             np.savez(head + '-true', test_img=test_img.cpu().numpy())
-            images.append((head, mask, test_y0, np.zeros((args.nsamples, resolution, resolution, nchannels), np.float32)))
+            images.append((head, mask, test_y0, np.zeros((args.nsamples, resolution, resolution, nchannels), np.float32),
+                           test_img))
             for i in range(args.nsamples):
                 key, subkey = ops.split(key)
                 jobs.append((len(images) - 1, i, subkey))
@@ -275,7 +302,9 @@ def main(argv=None):
                 images[m][3][i] = samples[b].cpu().numpy()
             if not args.quiet:
                 print(f'{task} | twisted x{len(group)} | runs: {g0 + len(group)} / {len(jobs)}')
-        for head, _, _, restored in images:
+        if args.metrics:
+            save_metrics([im[0] + '-twisted' for im in images], [im[4] for im in images], np.stack([im[3] for im in images], 0))
+        for head, _, _, restored, _ in images:
             np.save(head + '-twisted', restored)
             out = restored
         return out
@@ -297,7 +326,7 @@ def main(argv=None):
                 x0, _ = gibbs_init(subkey, test_y0, x_shape, ts, sb.fwd_sampler, sde, sb.unpack, nparticles=args.nparticles,
                                    method='filter', marg_y=args.marg, mask_=mask, **cl)
                 restored[i] = to_img(x0)
-            np.save(head + f'-filter{"-marg" if args.marg else ""}', restored)
+            suffix = f'-filter{"-marg" if args.marg else ""}'
         elif 'gibbs' in args.method:
             key, subkey = ops.split(key)
             x0, us_star = gibbs_init(subkey, test_y0, x_shape, ts, sb.fwd_sampler, sde, sb.unpack,
@@ -312,7 +341,7 @@ def main(argv=None):
                 restored[i] = to_img(x0)
                 if not args.quiet:
                     print(f'{task} | Gibbs | iter: {i}, acc: {float(acc.float().mean()):.3f}')
-            np.save(head + f'-gibbs{"-eb" if eb else ""}{"-ef" if ef else ""}{"-marg" if args.marg else ""}', restored)
+            suffix = f'-gibbs{"-eb" if eb else ""}{"-ef" if ef else ""}{"-marg" if args.marg else ""}'
         elif args.method == 'twisted':                                               # inpainting_twisted.py:148-191
             from fbs_amd.twisted import make_image_twisted
 
@@ -329,7 +358,7 @@ def main(argv=None):
                 restored[i] = sample.cpu().numpy()
                 if not args.quiet:
                     print(f'{task} | twisted | iter: {i}')
-            np.save(head + '-twisted', restored)
+            suffix = '-twisted'
         elif args.method == 'csgm':                                                  # inpainting_csgm.py:147-158
             from fbs_amd.csgm import make_image_csgm
             sampler = make_image_csgm(lambda x, t: run(net, x, t), ds, sde, ts)
@@ -338,7 +367,7 @@ def main(argv=None):
                 restored[i] = to_img(sampler(subkey, test_y0, mask))
                 if not args.quiet:
                     print(f'{task} | cSGM | iter: {i}')
-            np.save(head + '-csgm', restored)
+            suffix = '-csgm'
         elif 'pmcmc' in args.method:
             key, subkey = ops.split(key)
             x0, log_ell, ys = torch.zeros(x_shape, device=dev), 0., sb.fwd_ys_sampler(subkey, test_y0)
@@ -350,9 +379,12 @@ def main(argv=None):
                 restored[i] = to_img(x0)
                 if not args.quiet:
                     print(f'{task} | pMCMC {delta} | iter: {i}, acc_prob: {float(st.acceptance_prob):.3f}')
-            np.save(head + f'-pmcmc-{delta}', restored)
+            suffix = f'-pmcmc-{delta}'
         else:
             raise ValueError(f'Unknown method {args.method}')
+        if args.metrics:
+            save_metrics([head + suffix], [test_img], restored[None])
+        np.save(head + suffix, restored)
         out = restored
     return out
 

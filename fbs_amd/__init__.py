@@ -7,7 +7,7 @@ fallback: without the HIP extension or a GPU every operation raises.
 """
 from . import _lib  # noqa: F401
 from .ops import PRNGKey, split  # noqa: F401
-from . import ops, sdes, samplers  # noqa: F401
+from . import image_metrics, ops, sdes, samplers  # noqa: F401
 from .linear_gaussian import LinearGaussianBridge  # noqa: F401
 from .gaussian_sb import (GaussianSBBridge, SBKalman, SBKalmanSmoother, sb_kalman_conditional_sampler,  # noqa: F401
                           sb_kalman_path_sampler)
@@ -15,7 +15,7 @@ from .lg_twisted import GaussianTwisted  # noqa: F401
 from .lg_csgm import GaussianCSGM  # noqa: F401
 from .lg_kalman import LGKalman, LGKalmanSmoother, kalman_conditional_sampler, kalman_path_sampler  # noqa: F401
 
-__all__ = ["ops", "sdes", "samplers", "LinearGaussianBridge", "GaussianSBBridge", "GaussianTwisted", "GaussianCSGM", "LGKalman",
+__all__ = ["ops", "sdes", "samplers", "image_metrics", "LinearGaussianBridge", "GaussianSBBridge", "GaussianTwisted", "GaussianCSGM", "LGKalman",
            "LGKalmanSmoother", "kalman_conditional_sampler", "kalman_path_sampler", "SBKalman", "SBKalmanSmoother",
            "sb_kalman_conditional_sampler", "sb_kalman_path_sampler", "PRNGKey", "split", "build"]
 

@@ -977,6 +977,33 @@ int fbsmi_tw_img_propose_batched(const fbsmi_em_mask_batch* mask, const float* X
                                  const uint32_t* keys, int64_t B, int64_t n, float* X_new, float* tl, float* pl,
                                  int out_dtype, void* X_new_net, void* stream);
 
+/* ---- image metrics (fbs_amd/image_metrics.py; the paper's Tables 2 and 3 and Figure 8) ----
+ * All statistics are float64; the inputs are float32, so their products are exact in float64.  No operation is fused.
+ *
+ * psnr_ssim: true_imgs (G, H, W, C), restored (G, S, H, W, C), psnr and ssim (G, S) float64; image (g, s) is scored
+ * against true image g.  clip = 1 first maps every value v of both images to 0 for v < 0 and 1 for v > 1; data_range is 1.
+ *   PSNR = 10 log10(1 / mse),  mse = (sum of (x - y)^2 over the H W C elements) / (H W C);  mse == 0 gives +inf.
+ *   SSIM, per channel, over the (H - 6)(W - 6) 7x7 windows that lie inside the image, n = 49:
+ *     ux = sum x / n, uy = sum y / n,  vx = n/(n-1) (sum xx / n - ux ux), vy and vxy likewise (sample covariances),
+ *     C1 = 0.01^2, C2 = 0.03^2,  S = ((2 ux uy + C1)(2 vxy + C2)) / ((ux ux + uy uy + C1)(vx + vy + C2)),
+ *   the mean of S over the windows, then the mean over the channels.  Equal images give exactly 1.
+ * Every sum has a fixed order that depends on (H, W, C) alone: the result for image (g, s) has the same bits in any call.
+ * ws: fbsmi_img_psnr_ssim_workspace_bytes(G * S, H, W, C) bytes of device scratch (0 for an unsupported shape).
+ * FBSMI_ERR_ARG for a null pointer, G or S < 1, clip outside {0, 1} or more than 2^31 - 1 workgroups;
+ * FBSMI_ERR_UNSUPPORTED outside 7 <= H, W <= 256 and 1 <= C <= 4.  Nothing is launched then. */
+size_t fbsmi_img_psnr_ssim_workspace_bytes(int64_t GS, int32_t H, int32_t W, int32_t C);
+int fbsmi_img_psnr_ssim_batched(const float* true_imgs, const float* restored, int64_t G, int64_t S, int32_t H, int32_t W,
+                                int32_t C, int clip, double* psnr, double* ssim, void* ws, void* stream);
+/* chain autocorrelation: chains (M, S, D) float32, ac (M, L, D) and best (M, L) float64, 1 <= L <= S.  For variable d of
+ * chain m, with c_t = x_t - (sum_t x_t) / S and sums over t ascending:
+ *   ac[k] = ((sum over t < S - k of c_t c_{t+k}) / (S - k)) / ((sum_t c_t c_t) / S)
+ * (the unbiased estimator, as a direct sum).  A variable whose S samples all have the same bits is constant: its ac is NaN
+ * at every lag.  best[m][k] = the minimum over the non-NaN variables of max(ac[m][k][d], 0), NaN when there is none.
+ * FBSMI_ERR_ARG for a null pointer, M, S or D < 1 or L outside [1, S]; FBSMI_ERR_UNSUPPORTED for M > 65535, S > 2^20 or
+ * D > 2^24. */
+int fbsmi_chain_autocorr_batched(const float* chains, int64_t M, int64_t S, int64_t D, int64_t L, double* ac, double* best,
+                                 void* stream);
+
 /* HIP-event timing hooks: average duration in microseconds of the propagate ("Euler") kernel
  * over the launches since the last reset; 0 launches -> returns 0. Only measured when
  * fbsmi_lg_sweep_profile(s, 1) was set (events force non-graph launches). */
