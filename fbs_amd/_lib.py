@@ -13,7 +13,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = [os.path.join(_HERE, "csrc", n) for n in ("fbsmi_prims.hip", "fbsmi_lg.hip", "fbsmi_sde.hip", "fbsmi_nn.hip", "fbsmi_em.hip",
                                                   "fbsmi_tw.hip", "fbsmi_csgm.hip", "fbsmi_bs.hip", "fbsmi_kf.hip", "fbsmi_kf_em.hip",
-                                                  "fbsmi_batch.hip", "fbsmi_metrics.hip")]
+                                                  "fbsmi_batch.hip", "fbsmi_metrics.hip", "fbsmi_train.hip")]
 _DEPS = _SRC + [os.path.join(_HERE, "csrc", "fbsmi_device.h"), os.path.join(_HERE, "csrc", "fbsmi_host.h"),
                 os.path.join(_HERE, "csrc", "fbsmi_em_path.h"), os.path.join(_HERE, "csrc", "fbsmi_kf_em.h"),
                 os.path.join(_HERE, "..", "include", "fbsmi.h"), os.path.join(_HERE, "..", "include", "fbsmi_math.h"),
@@ -324,6 +324,14 @@ SIGNATURES = {
     "fbsmi_img_psnr_ssim_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32, _i32]),
     "fbsmi_img_psnr_ssim_batched": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, C.c_int, _vp, _vp, _vp, _vp]),
     "fbsmi_chain_autocorr_batched": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "fbsmi_uniform_host": (C.c_int, [_u32, _u32, _i64, _vp]),
+    "fbsmi_dsm_noise_batched": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, _vp, _vp]),
+    "fbsmi_dsm_loss_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "fbsmi_dsm_loss_batched": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i64, _i64, _vp, _vp,
+                                         _vp, _vp, _vp]),
+    "fbsmi_sqnorm_workspace_bytes": (C.c_size_t, [_i64]),
+    "fbsmi_sqnorm": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "fbsmi_adam_ema_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _vp, _f, C.c_int, _f, _vp]),
     # include/fbsmi_nn.h
     "fbsmi_nn_linear_attention": (C.c_int, [_vp, _vp, C.c_int, _i64, _i32, _i32, _i32, _vp]),
     "fbsmi_nn_qkv_linear_attention": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),

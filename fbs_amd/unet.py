@@ -726,15 +726,22 @@ class UNet(nn.Module):
 
     @torch.no_grad()
     def export_flat_params(self) -> torch.Tensor:
-        parts = []
-        for _, p, kind in self.flat_param_spec():
-            if kind == 'conv':
-                parts.append(p.permute(2, 3, 1, 0).reshape(-1))
-            elif kind == 'dense':
-                parts.append(p.t().reshape(-1))
-            else:
-                parts.append(p.reshape(-1))
-        return torch.cat([q.detach().float().cpu() for q in parts])
+        return ravel_flat_params([(p, kind) for _, p, kind in self.flat_param_spec()])
+
+
+def ravel_flat_params(pieces) -> torch.Tensor:
+    """[(tensor in torch layout, kind)] in flat_param_spec order -> the flat host vector in the flax layouts ('conv'
+    (kh,kw,in,out), 'dense' (in,out), 'vec'): the one place that spells the checkpoint order, for the parameters and for
+    any vector laid out like them (the trainer's EMA)."""
+    parts = []
+    for p, kind in pieces:
+        if kind == 'conv':
+            parts.append(p.permute(2, 3, 1, 0).reshape(-1))
+        elif kind == 'dense':
+            parts.append(p.t().reshape(-1))
+        else:
+            parts.append(p.reshape(-1))
+    return torch.cat([q.detach().float().cpu() for q in parts])
 
 
 def make_st_nn(nn_module: UNet, param=None, device=None):

@@ -1004,6 +1004,71 @@ int fbsmi_img_psnr_ssim_batched(const float* true_imgs, const float* restored, i
 int fbsmi_chain_autocorr_batched(const float* chains, int64_t M, int64_t S, int64_t D, int64_t L, double* ac, double* best,
                                  void* stream);
 
+/* ---- the denoising score-matching trainer (fbs_amd/sdes/losses.py make_linear_sde_law_loss, fbs_amd/train.py) ----
+ * fbs/sdes/linear.py:230-360 and fbs/nn/utils.py:60-83 round the network.  Every product, sum and quotient below is one
+ * float32 operation rounded on its own (-ffp-contract=off); tree_sum is the root of the pairwise tree over the zero-padded
+ * element index, the tree of fbsmi_sum, whatever the tiling.  bfloat16 values are widened exactly on load and rounded to
+ * nearest even on store.  Everything is refused on the host before any HIP call, and nothing is launched then. */
+
+/* fbsmi_uniform(key, n) on the HOST, bit for bit (out_host: a host array of n floats): the trainer's random times, drawn
+ * without a device round trip.  FBSMI_ERR_ARG for n < 0 or a null array with n > 0. */
+int fbsmi_uniform_host(uint32_t k0, uint32_t k1, int64_t n, float* out_host);
+
+/* Row b of xt (B, D) = F[b] * x0[e] + sq[b] * xi[e]  (two products, one sum), x0 = row idx[b] of data (row b when idx is
+ * NULL; the entries of idx must be valid rows of data, they are not checked) and xi = element e of normal(keys[b], (D,)),
+ * drawn in the kernel: the batch gather, the draw and simulate_cond_forward(keep_path=False) in one pass, no (B, D) copy of
+ * the batch and no noise array.  F, sq (B) float32, keys (B, 2) device arrays.  out_dtype 0: xt float32; 1: bfloat16.
+ * Up to 64 workgroups per row.  When D is a multiple of 8 and data, xt are 16-byte aligned a thread owns four consecutive
+ * elements in each half of the row (the two words of four cipher calls): 16-byte loads of data, 16-byte stores of a float32
+ * xt, 8-byte stores of a bfloat16 xt; element-wise otherwise.  The kernel is bound by the cipher and the normal transform.
+ * FBSMI_ERR_ARG for a null pointer (but idx), B < 1, D < 1, D > 2^32 - 4, out_dtype outside {0, 1}, or more workgroups than
+ * one grid holds. */
+int fbsmi_dsm_noise_batched(const float* data, const int32_t* idx, const uint32_t* keys, const float* F, const float* sq,
+                            int64_t B, int64_t D, int out_dtype, void* xt, void* stream);
+
+/* The loss mean_b(mean_e((net - cond_score)^2) Q_b) and its derivative with respect to net, in one pass over net (B, D;
+ * net_dtype 0 float32, 1 bfloat16).  With cond_score = -(xt - F x0) / Q and sq = sqrt(Q) the summand is r^2 with
+ *     r = sq[b] * net[b][e] + e_be,
+ *   mode 0 (drawn):  e_be = element e of normal(keys[b], (D,)), exactly the xi of fbsmi_dsm_noise_batched; xt, data, idx
+ *                    and F are not read;
+ *   mode 1 (stored): e_be = (xt[b][e] - F[b] * x0[e]) / sq[b], a correctly rounded quotient, from a float32 xt (B, D) and
+ *                    x0 = row idx[b] of data (row b when idx is NULL); keys is not read.  The path layout needs this form:
+ *                    its points are sums of several draws.  The difference xt - F x0 cancels for small times: below
+ *                    t ~ 0.02 its rounding error alone exceeds 1e-5 relative in the loss, in the reference's own
+ *                    float32 evaluation as much as here.
+ *   S_b = tree_sum_e(r^2) -> row_sums[b] (row_sums may be NULL);   loss[0] = inv * tree_sum_b(S_b), inv = float32(1 / (B D))
+ *   from the host;   dnet[b][e] = gc[b] * r in net's dtype, gc[b] = float32(2 sq[b] / (B D)) from the host.
+ * S_b and row b of dnet depend on row b alone: they have the same bits for any B and any position of the row.
+ * Two launches: aligned chunks of 2048 elements of a row, spread over up to 64 workgroups per row, write dnet and their
+ * subtree roots into workspace (fbsmi_dsm_loss_workspace_bytes(B, D) bytes; 0 for a refused shape); one workgroup finishes
+ * the trees.  16-byte accesses when D is a multiple of 8 and the arrays are 16-byte aligned, element-wise otherwise.
+ * FBSMI_ERR_ARG for a null pointer the mode reads or writes, B < 1, D < 1, D > 2^32 - 4, net_dtype or mode outside {0, 1},
+ * or more workgroups than one grid holds. */
+size_t fbsmi_dsm_loss_workspace_bytes(int64_t B, int64_t D);
+int fbsmi_dsm_loss_batched(const void* net, int net_dtype, int mode, const uint32_t* keys, const float* xt, const float* data,
+                           const int32_t* idx, const float* F, const float* sq, const float* gc, float inv, int64_t B,
+                           int64_t D, void* dnet, float* row_sums, float* loss, void* workspace, void* stream);
+
+/* out[0] = tree_sum_i(x[i] * x[i]) of a flat float32 vector, in one pass over it (squaring through fbsmi_math_map and
+ * fbsmi_sum would be two, and a vector of scratch).  workspace: fbsmi_sqnorm_workspace_bytes(n) bytes.
+ * FBSMI_ERR_ARG for a null pointer or n < 1. */
+size_t fbsmi_sqnorm_workspace_bytes(int64_t n);
+int fbsmi_sqnorm(const float* x, int64_t n, float* out, void* workspace, void* stream);
+
+/* optax.chain(clip_by_global_norm(max_norm), adam(lr, b1, b2, eps)) and the reference's ema_kernel in one pass over the flat
+ * float32 vectors p, g, m, v, ema (n); g is read only.
+ *     s = 1 if gnorm2 is NULL or sqrt(gnorm2[0]) < max_norm, else max_norm / sqrt(gnorm2[0])   (gnorm2: a device scalar)
+ *     g' = g * s;   m = b1 * m + (1 - b1) * g';   v = b2 * v + (1 - b2) * (g' * g')
+ *     u = (m / bc1) / (sqrt(v / bc2) + eps);   p = p - lr * u
+ *     ema_mode 0: ema untouched (it may be NULL);  1: ema = p;  2: ema = decay * ema + (1 - decay) * p   (the new p)
+ * 1 - b1, 1 - b2 and 1 - decay are float32 differences; lr, bc1 = 1 - b1^t and bc2 = 1 - b2^t are float32 values the host
+ * computed in float64 and rounded once.  sqrt and the quotients are correctly rounded.
+ * FBSMI_ERR_ARG for a null pointer, n < 1, ema_mode outside {0, 1, 2}, bc1 or bc2 not positive, or max_norm not positive
+ * with gnorm2 given. */
+int fbsmi_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float b1, float b2,
+                        float eps, float bc1, float bc2, const float* gnorm2, float max_norm, int ema_mode, float decay,
+                        void* stream);
+
 /* HIP-event timing hooks: average duration in microseconds of the propagate ("Euler") kernel
  * over the launches since the last reset; 0 launches -> returns 0. Only measured when
  * fbsmi_lg_sweep_profile(s, 1) was set (events force non-graph launches). */
