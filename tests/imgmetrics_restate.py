@@ -123,9 +123,12 @@ def best_curve(ac):
 IMAGE_KINDS = ("noisy", "flat", "outside", "equal")
 # (H, W, C): one window; a row of windows; odd with three channels; MNIST; past a wave and no multiple of it; the extreme
 # aspect ratios; then both sides of the band edge, which depends on the width (a staged plane holds 6144 // W rows): at
-# W = 256 one band up to H = 24, at W = 96 up to H = 64
+# W = 256 one band up to H = 24, at W = 96 up to H = 64; then the largest plane (14 bands, the LDS maximum of 58 KiB); one
+# band of 250 window rows with exactly 6144 staged floats, 10 segments of 25 rows (the longest running-sum drift); four
+# channels, one segment and 127 idle threads; the 64 x 64 x 3 configuration
 IMAGE_SHAPES = ((7, 7, 1), (7, 9, 1), (8, 13, 3), (28, 28, 1), (33, 65, 3), (256, 7, 1), (7, 256, 2),
-                (24, 256, 1), (25, 256, 1), (64, 96, 1), (65, 96, 1))
+                (24, 256, 1), (25, 256, 1), (64, 96, 1), (65, 96, 1),
+                (256, 256, 1), (256, 24, 1), (40, 129, 4), (64, 64, 3))
 
 
 def make_images(kind, G, S, shape, seed=0):

@@ -3,8 +3,8 @@ of tests/imgmetrics_restate.py, and examples/imgs_restore.py --metrics.
 
 Bounds (absolute).  SSIM 1e-10: the float64 cancellation in E[xx] - ux^2 is at most about 49 * 1.1e-16 * 0.25 ~ 1e-15, which
 against C2 = 9e-4 is about 1e-12; the bound is 100 times that and five orders below the smallest formula mistake
-(tests/test_image_metrics_host.py).  PSNR 1e-9 dB: a sum of at most 196 608 terms has a relative error of at most 2e-11,
-times 10 / ln 10 = 4.3.  Autocorrelation 1e-9: the inputs are random walks, far from the cancellation of a nearly constant
+(tests/test_image_metrics_host.py).  PSNR 1e-9 dB: a sum of at most 262 144 terms (256 x 256 x 4) has a relative error of at most 2.9e-11,
+times 10 / ln 10 = 4.3: about 1.2e-10 dB.  Autocorrelation 1e-9: the inputs are random walks, far from the cancellation of a nearly constant
 variable.  The restatements are pinned to the specification's formulas, not to skimage or numpyro.
 """
 import os

@@ -39,7 +39,7 @@ def test_noise_equals_the_restatement(dev, D):
             got = dsm_noise_batched(data, idx, keys, F, sq, torch.float32).cpu().numpy()
             assert np.array_equal(bits(got), bits(want)), (B, tag)
             got16 = _bf16_np(dsm_noise_batched(data, idx, keys, F, sq, torch.bfloat16))
-            assert np.array_equal(bits(got16), bits(R.bf16_round(want))), (B, tag, "bf16")
+            assert np.array_equal(bits(got16), bits(R.bf16_round_full(want))), (B, tag, "bf16")
 
 
 def _loss_case(c, B, mode, dt16):
@@ -79,7 +79,7 @@ def test_loss_equals_the_restatements(dev, D, mode, dt16):
         loss, dnet, S, w = _run_loss(dev, c, B, mode, dt16)
         wS, wloss, wd = R.loss_f32(w["net"], w["e"], w["sq"], w["gc"], w["inv"])
         if dt16:
-            wd = R.bf16_round(wd)
+            wd = R.bf16_round_full(wd)
         assert np.array_equal(bits(S), bits(wS)), B
         assert np.array_equal(bits(loss), bits(np.array([wloss], np.float32))), B
         assert np.array_equal(bits(dnet), bits(wd)), B
@@ -109,7 +109,7 @@ def test_stored_loss_without_idx_reads_row_b_of_data(dev, D, dt16):
         wS, wloss, wd = R.loss_f32(net, e, sq, gc, inv)
         assert np.array_equal(bits(S.cpu().numpy()), bits(wS)), B
         assert np.array_equal(bits(loss.cpu().numpy()), bits(np.array([wloss], np.float32))), B
-        assert np.array_equal(bits(dnet.float().cpu().numpy()), bits(R.bf16_round(wd) if dt16 else wd)), B
+        assert np.array_equal(bits(dnet.float().cpu().numpy()), bits(R.bf16_round_full(wd) if dt16 else wd)), B
         ref = R.loss_f64(net, xt, c["data"][:B], F, sq)
         assert abs(float(loss[0]) - ref) / ref < REL, B
 

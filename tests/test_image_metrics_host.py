@@ -16,7 +16,7 @@ NAMES = ("fbsmi_img_psnr_ssim_workspace_bytes", "fbsmi_img_psnr_ssim_batched", "
 
 @pytest.mark.parametrize("shape", R.IMAGE_SHAPES)
 def test_ssim_forms_agree(shape):
-    """uniform_filter plus crop against the explicit loop over windows: 1e-12 (measured: at most 6.3e-14)."""
+    """uniform_filter plus crop against the explicit loop over windows: 1e-12 (measured: at most 1.2e-13)."""
     worst = 0.0
     for kind in R.IMAGE_KINDS:
         t, r = R.make_images(kind, 1, 1, shape)

@@ -29,6 +29,17 @@ def bf16_round(x):
     return r.astype(np.uint32).view(f32).reshape(np.shape(x))
 
 
+def bf16_round_full(x):
+    """bf16_round on all of float32: to nearest even, overflow to infinity, and any NaN in gives a NaN out (bf16_round adds
+    the rounding increment to a NaN's payload too, which carries 0x7fffffff over into -0)."""
+    x = np.ascontiguousarray(x, f32)
+    u = x.view(np.uint32).astype(np.uint64)
+    r = (((u + 0x7fff + ((u >> 16) & 1)) >> 16) << 16) & 0xffffffff
+    quiet = ((u >> 16) | 0x40) << 16                       # the kernel's choice; only "is a NaN" is specified
+    r = np.where((u & 0x7fffffff) > 0x7f800000, quiet, r)
+    return r.astype(np.uint32).view(f32).reshape(np.shape(x))
+
+
 def noise_f32(data, idx, keys, F, sq):
     """fbsmi_dsm_noise_batched: (xt (B, D) float32, xi (B, D))."""
     B, D = len(keys), data.shape[1]
@@ -79,12 +90,14 @@ def loss_f64(net, xt, x0, F, sq, mistake=None):
     return float(np.mean(per_row * w))
 
 
-def clip_by_global_norm_f64(g, max_norm, mistake=None):
-    """optax.clip_by_global_norm.  mistake 'by_value' clips every entry to [-max_norm, max_norm]."""
+def clip_by_global_norm_f64(g, max_norm, mistake=None, gnorm2=None):
+    """optax.clip_by_global_norm.  mistake 'by_value' clips every entry to [-max_norm, max_norm].  gnorm2: the squared norm
+    when it is given and not g's own (fbsmi_adam_ema_step reads it from a device scalar): 0 leaves g alone, inf gives
+    zeros, and NaN makes every entry NaN, since where(norm < max_norm, g, ...) then takes the scaled branch."""
     g = np.asarray(g, np.float64)
     if mistake == 'by_value':
         return np.clip(g, -max_norm, max_norm)
-    n = math.sqrt(float(np.sum(g * g)))
+    n = math.sqrt(float(np.sum(g * g)) if gnorm2 is None else float(gnorm2))
     return g if n < max_norm else g / n * max_norm
 
 
@@ -150,21 +163,40 @@ def lin_tables(ts, count):
     return F, sq, (2.0 * sq.astype(np.float64) / count).astype(f32)
 
 
+def idx_of(B):
+    """B rows of the NDATA data rows: IDX, then a seeded draw with repeats."""
+    if B <= len(IDX):
+        return IDX[:B]
+    more = np.random.default_rng(4242).integers(0, NDATA, B - len(IDX)).astype(np.int32)
+    return np.concatenate([IDX, more])
+
+
+def times_of(B):
+    """B times in [0.02, 2]: TIMES, then an even grid over the same interval."""
+    if B <= len(TIMES):
+        return TIMES[:B]
+    return np.concatenate([TIMES, np.linspace(0.02, 2.0, B - len(TIMES))])
+
+
 @functools.lru_cache(maxsize=None)
 def case(D, B=5):
-    """Inputs and float32 expectations for B rows of D elements: a dict of read-only arrays."""
+    """Inputs and float32 expectations for B rows of D elements: a dict of read-only arrays.  With more rows than data has
+    (B > NDATA) only the gathered layout exists: "xt" is left out and "xi", which depends on the keys alone, stays."""
     rng = np.random.default_rng(1000 + D)
     data = rng.uniform(0, 1, (NDATA, D)).astype(f32)
     keys = O.split(O.PRNGKey(77 + D), B)
-    F, sq, gc = lin_tables(TIMES[:B], B * D)
+    F, sq, gc = lin_tables(times_of(B), B * D)
     inv = f32(1.0 / (B * D))
     net = rng.normal(size=(B, D)).astype(f32)
     net16 = bf16_round(net)
-    out = dict(D=D, B=B, data=data, keys=keys, F=F, sq=sq, gc=gc, inv=inv, net=net, net16=net16)
-    for tag, idx in (("", None), ("_idx", IDX[:B])):
-        xt, xi = noise_f32(data, idx, keys, F, sq)
-        out["xt" + tag], out["xi" + tag] = xt, xi
-    out["x0_idx"] = data[IDX[:B]]
+    idx = idx_of(B)
+    out = dict(D=D, B=B, data=data, keys=keys, F=F, sq=sq, gc=gc, inv=inv, net=net, net16=net16, idx=idx)
+    out["xt_idx"], out["xi_idx"] = noise_f32(data, idx, keys, F, sq)
+    if B <= NDATA:
+        out["xt"], out["xi"] = noise_f32(data, None, keys, F, sq)
+    else:
+        out["xi"] = out["xi_idx"]
+    out["x0_idx"] = data[idx]
     for a in out.values():
         if isinstance(a, np.ndarray):
             a.setflags(write=False)
